@@ -1,8 +1,13 @@
 """bench.py -- env-steps/s of the batched rollout + A2C update on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
      or plainly -- without a torchrun environment the script re-launches itself with N ranks)
+
+A plain run sets up, runs W untimed and K timed steps and prints the result line (headline, ms_per_step, config).
+--full adds the side measurements below, each of which takes runs of its own after the timed region.
+--dump-outputs DIR writes what the last timed step computed (weights, optimiser slots, the batch's actions, values,
+rewards, returns, advantages, episode statistics) as DIR/<name>.npy, float32 / float64, 64 MB at most in all.
 
 Workload (BASELINE.json configs[1]): CACC catch-up, 8 agents x 4096 lock-stepped replicas per GPU,
 IA2C-FP (config/config_ia2c_fp_catchup.ini), fp32, synthetic (Philox initial conditions, random-init
@@ -13,13 +18,15 @@ A "step" = one n_step batch of the hot path over all replicas: 60 lock-steps of
 the bootstrap value, the n-step return scan and ONE A2C update (unroll + loss + backward +
 [RCCL all-reduce] + clip/RMSProp).  metric = agents x replicas x lock-steps / second, whole job.
 
-Extra objects on the JSON line (tier contract):
+Extra objects on the JSON line with --full (tier contract):
   roofline      the DOMINANT kernel of the batch, the fused MFMA LSTM lock-step: algorithmic flops per launch / average
                 launch duration measured live with HIP events, against the dense fp32 matrix peak; see `roofline.how`.
   roofline_env_step[_large_E]   the CACC step kernel (north_star's HBM roofline): algorithmic bytes per launch (B_alg,
                 DESIGN.md) / average launch duration, at the workload size and at E = 2^21.
   cpu_baseline  the reference-equivalent E=1 CPU loop (oracle/trainer_ref.py, kind "port") timed
                 on one host core on a bounded sample (rank 0, N=1 only).
+  other_configs the other BASELINE configs, each measured like the headline (N=1, default --config only).
+  grad_allreduce  the gradient all-reduce timed on its own (N > 1 or NMARL_BENCH_FORCE_DIST=1).
 """
 import argparse
 import configparser
@@ -40,6 +47,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+# TunableOp's own pick for the default workload's three library GEMM shapes on an MI355X (a default run's results file, as
+# written): tuning them cold costs ~25 s per process, nearly all of it in trying several hundred candidates.  Read before the
+# first GEMM; TunableOp rejects a table whose validators (PyTorch, HIP, hipBLASLt, rocBLAS, gfx arch) do not match this
+# machine, and any shape it does not hold is tuned at first use as before.
+GEMM_TABLE = os.path.join(ROOT, 'config', 'tunableop_gfx950.csv')
 
 HBM_PEAK_GBPS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_AGENT = 8
@@ -76,7 +88,15 @@ def parse():
     ap.add_argument('--other-steps', type=int, default=10, help='timed n_step batches per other config')
     ap.add_argument('--cpu-batches', type=int, default=100,
                     help='n_step batches of the E=1 CPU baseline (100 = 6000 env steps of BASELINE configs[0], ~10 s on one core)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the rooflines, the update breakdown, the env step at large E, the CPU '
+                         'baseline, the other BASELINE configs and the gradient all-reduce (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def measure_step_kernel(env, actions_tape, reps=20, encode=None):
@@ -764,6 +784,39 @@ def self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, model, trainer):
+    """`--dump-outputs DIR`: what the timed path handed back in its last step -- the weights and optimiser slots after the
+    update, the batch's actions, values, normalised rewards, n-step returns, advantages, bootstrap values, global rewards
+    and the episode statistics -- as DIR/<name>.npy (float32; float64 where the device keeps float64).  At most
+    DUMP_BYTES in all: an array larger than its share is replaced by a fixed sample (RandomState(0), sorted flat indices),
+    so two runs with the same arguments write the same elements."""
+    m = model
+    trainer.flush()                     # the last batch's status, as a caller reading statistics would see it
+    arrays = {'params': m.policy.params.flat, 'rms_slot': m.policy.params.ms, 'actions': m.buf_act, 'values': m.buf_v,
+              'rewards': m.buf_r, 'returns': getattr(m, 'R', None), 'advantages': getattr(m, 'Adv', None),
+              'bootstrap_values': trainer.R_end, 'global_rewards': trainer.buf_g, 'episode_stats': trainer.fin}
+    host = {}
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            a = t.detach().cpu().numpy()
+            host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    budget, left = DUMP_BYTES, len(host)
+    for name, a in sorted(host.items(), key=lambda kv: kv[1].nbytes):
+        share = budget // left - 256                # (room for the .npy header)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        path = os.path.join(out_dir, name + '.npy')
+        np.save(path, a)
+        budget -= os.path.getsize(path)
+        left -= 1
+
+
 def make_job(args, cp, device, rank, world, group):
     """(env, model, trainer) of one rank: E replicas with global replica ids rank*E ... (Philox streams)."""
     from deeprl_network_amd.agents import models
@@ -829,6 +882,9 @@ def main():
             os.environ['NMARL_INKERNEL_HANDOFF'] = '0'
     torch.cuda.set_device(local_rank)
     device = torch.device('cuda', local_rank)
+    if os.environ.get('PYTORCH_TUNABLEOP_ENABLED') == '1' and os.path.exists(GEMM_TABLE):
+        import torch.cuda.tunable as tunable
+        tunable.read_file(GEMM_TABLE)
     group = None
     use_dist = world > 1 or os.environ.get('NMARL_BENCH_FORCE_DIST') == '1'
     if use_dist:
@@ -873,6 +929,9 @@ def main():
         dist.all_gather(every, mine)
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in every]
         elapsed = max(float(x.item()) for x in every)                  # MAX over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, trainer)
+    if use_dist and args.full:
         # the path's one collective, timed on its own after the timed region: the flat gradient all-reduce of an update
         g = model.policy.params.grad_wire
         for _ in range(3):
@@ -928,7 +987,7 @@ def main():
                    'step_definition': 'one n_step batch: %d lock-steps (2 LSTM steps each, quirk Q1) + bootstrap + '
                                       '1 A2C update over all replicas' % n_step},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- `roofline`: the DOMINANT kernel of the batch = the fused MFMA LSTM lock-step (fp32 matrix pipe)
         if model.n_lstm == 64:
             try:
@@ -1107,6 +1166,7 @@ def main():
                     out['other_configs'].append(run_other_config(args, cfg_name, device))
                 except Exception as ex:      # never lose the headline line to a side measurement
                     out['other_configs'].append({'workload': cfg_name, 'error': repr(ex)})
+    if rank == 0:
         print(json.dumps(_ordered(out)))
     if use_dist:
         dist.barrier()

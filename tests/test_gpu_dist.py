@@ -126,7 +126,7 @@ def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` WITHOUT a torchrun environment (how the driver may call it) spawns its own two
     ranks and rank 0 prints exactly one JSON line with n_gpus = 2."""
     hooks = {} if torch.cuda.device_count() >= 2 else {'NMARL_BENCH_ONE_DEVICE': '1', 'NMARL_DIST_BACKEND': 'gloo'}
-    p, lines = _bench(hooks, '--gpus', '2', '--steps', '2', '--warmup', '1', '--envs', '256', '--no-cpu-baseline')
+    p, lines = _bench(hooks, '--gpus', '2', '--steps', '2', '--warmup', '1', '--envs', '256', '--no-cpu-baseline', '--full')
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])
@@ -140,7 +140,7 @@ def test_bench_self_launches_eight_ranks():
     with seven ranks waiting at the barrier, rank-offset replica ids, eight-way gradient all-reduce.  Rank 0 prints ONE
     line that explains itself: n_gpus, per-rank ms per step, the all-reduce time."""
     hooks = {} if torch.cuda.device_count() >= 8 else {'NMARL_BENCH_ONE_DEVICE': '1', 'NMARL_DIST_BACKEND': 'gloo'}
-    p, lines = _bench(hooks, '--gpus', '8', '--steps', '2', '--warmup', '1', '--envs', '128', '--no-cpu-baseline')
+    p, lines = _bench(hooks, '--gpus', '8', '--steps', '2', '--warmup', '1', '--envs', '128', '--no-cpu-baseline', '--full')
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])

@@ -1,50 +1,27 @@
 """The synthetic Monaco-like network: what is pinned to the reference (tables, masks, action / observation widths),
 the independence of the two transcriptions (oracle vs product), and the properties of the specified dynamics."""
+import json
 import os
-import sys
-import types
 
 import numpy as np
-import pytest
 
 from helpers import net_config
 from oracle.realnet_ref import DET_CAP, N_GROUP, Q_MAX, TOPO, NetBatchRef, NetParams, gather_net
 
-REF = '/root/reference'
+# NODES / PHASES of the reference (real_net_env.py:21-69) and the masks RealNetEnv builds from them (152-195), as
+# tests/golden/make_golden_tables.py read them from a reference checkout
+TABLES = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_tables.json')))['real_net']
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason='reference checkout not present (GPU box)')
 def test_tables_and_masks_equal_the_reference():
-    """NODES / PHASES (real_net_env.py:21-69) and the masks RealNetEnv builds from them (152-195), by importing the
-    reference module itself (SUMO / plotting imports stubbed: only module-level constants and pure methods are used)."""
-    saved = dict(sys.modules)
-    try:
-        for m in ('seaborn', 'matplotlib', 'matplotlib.pyplot', 'traci', 'traci.exceptions', 'sumolib'):
-            sys.modules[m] = types.ModuleType(m)
-        sys.modules['seaborn'].set_color_codes = lambda *a, **k: None
-        sys.modules['sumolib'].checkBinary = lambda x: x
-        sys.modules['traci'].exceptions = types.SimpleNamespace(FatalTraCIError=Exception)
-        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle', 'tf1_shim'))
-        sys.path.insert(0, REF)
-        for k in [k for k in sys.modules if k == 'envs' or k.startswith('envs.')]:
-            del sys.modules[k]
-        from envs.real_net_env import NODES, PHASES, RealNetEnv
-        names = sorted(NODES)
-        assert names == TOPO.names
-        for i, n in enumerate(names):
-            assert list(PHASES[NODES[n][0]]) == list(TOPO.phases[i])
-            assert [names.index(x) for x in NODES[n][1]] == TOPO.nbrs_listed[i]
-        env = RealNetEnv.__new__(RealNetEnv)                     # no SUMO: run only the pure map builders
-        env.node_names, env.n_node = names, len(names)
-        env._init_neighbor_map()
-        env._init_distance_map()
-        np.testing.assert_array_equal(env.neighbor_mask, TOPO.neighbor_mask)
-        np.testing.assert_array_equal(env.distance_mask, TOPO.distance_mask)
-    finally:
-        sys.path[:] = [p for p in sys.path if p != REF and not p.endswith('tf1_shim')]
-        for k in [k for k in sys.modules if k not in saved]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+    """Node names, phase lists, listed neighbourhoods and the two masks of the oracle's topology equal the reference's."""
+    names = TABLES['names']
+    assert names == TOPO.names
+    for i in range(len(names)):
+        assert TABLES['phases'][i] == list(TOPO.phases[i])
+        assert TABLES['nbrs_listed'][i] == TOPO.nbrs_listed[i]
+    np.testing.assert_array_equal(np.array(TABLES['neighbor_mask']), TOPO.neighbor_mask)
+    np.testing.assert_array_equal(np.array(TABLES['distance_mask']), TOPO.distance_mask)
 
 
 def test_shapes_of_the_heterogeneous_system():

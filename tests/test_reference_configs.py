@@ -1,31 +1,31 @@
 """Drop-in of the ini schema: every CACC / large-grid config shipped by the REFERENCE parses unchanged into the
 kernel parameter structs, and the matching model class constructs with the reference's parameter count.
-Needs the reference checkout (authoring container); skipped on the GPU box."""
+The reference's configs are read from tests/golden/reference_tables.json (raw key / value strings of every ini,
+written by tests/golden/make_golden_tables.py from a reference checkout)."""
 import configparser
-import glob
+import json
 import os
 
 import numpy as np
 import pytest
 
-REF_CFG = '/root/reference/config'
-FILES = sorted(glob.glob(os.path.join(REF_CFG, '*.ini')))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+CONFIGS = json.load(open(os.path.join(GOLDEN, 'reference_tables.json')))['configs']
+FILES = sorted(CONFIGS)
 # parameter counts of the reference's graphs (SURVEY.md 8a + tests/golden/nn_*.npz)
 PARAMS = {('ia2c', 8): 274400, ('ia2c_fp', 8): 409568, ('ma2c_nc', 8): 598496, ('ma2c_ic3', 8): 307680,
           ('ma2c_cu', 8): 269920, ('ma2c_dial', 8): 365536, ('ma2c_ic3', 25): 1021990, ('ma2c_nc', 25): 2093670,
           ('ma2c_cu', 25): 856550, ('ma2c_dial', 25): 1351270}
 
-pytestmark = pytest.mark.skipif(not FILES, reason='reference checkout not present')
 
-
-@pytest.mark.parametrize('path', FILES, ids=[os.path.basename(f) for f in FILES])
+@pytest.mark.parametrize('path', FILES, ids=FILES)
 def test_reference_ini_parses_and_model_builds(path):
     from cpu_emulation import cpu_ops
     from deeprl_network_amd.agents import models
     from deeprl_network_amd.envs.cacc_env import _params_from_config, line_graph
     from deeprl_network_amd.envs.large_grid_env import grid_masks, grid_params_from_config
     cp = configparser.ConfigParser()
-    cp.read(path)
+    cp.read_dict(CONFIGS[path])
     env_cfg = cp['ENV_CONFIG']
     scenario, agent = env_cfg.get('scenario'), env_cfg.get('agent')
     if scenario == 'atsc_real_net':

@@ -6,7 +6,7 @@
 #   NMARL_BPTT_HEAD_DY        the one-launch BPTT expands dy8 itself (nmarl_lstm_bptt_seq_dy)                      vs  dL/dh as a tensor
 #   NMARL_BPTT_HEAD_DY_COUPLED  the same for the coupled BPTT kernels (nmarl_bptt_coupled_t.dy8)                    vs  dL/dh as a tensor
 cd "$(dirname "$0")/.."
-run() { env "${@:3}" python bench.py --no-cpu-baseline --no-other-configs --steps 20 --warmup 4 --config config/config_$1.ini 2>/dev/null | python -c "
+run() { env "${@:3}" python bench.py --full --no-cpu-baseline --no-other-configs --steps 20 --warmup 4 --config config/config_$1.ini 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; u=d.get('update') or {}
 print('%-28s %-18s %7.3f ms %6.1f M | lock-step %6.2f us | rollout %7.1f us | update %s us' % ('$2', '$1', d['ms_per_step'], d['value']/1e6, r.get('us_per_launch',0), r.get('rollout_graph_us') or 0, ('%.1f' % u['update_graph_us']) if u.get('update_graph_us') else 'n/a'))"; }

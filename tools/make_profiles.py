@@ -35,7 +35,7 @@ shutil.copy(os.path.join(src, '%s_bench_default.json' % tag), os.path.join(dst, 
 with open(os.path.join(dst, '%s_bench_kernel_stats.md' % tag), 'w') as f:
     f.write('# rocprofv3 --kernel-trace --stats summaries (round %s)\n\n' % tag[1:].lstrip('0'))
     f.write('command (per config, after one untraced run that writes the TunableOp GEMM choices): `rocprofv3 --kernel-trace --stats '
-            '-d /tmp/prof_<cfg> -o bench -- python bench.py --no-cpu-baseline --steps 5 --warmup 2 --config config/config_<cfg>.ini`, '
+            '-d /tmp/prof_<cfg> -o bench -- python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --config config/config_<cfg>.ini`, '
             'then `python tools/rocpd_stats.py /tmp/prof_<cfg>/bench_results.db --steps 7 --update` for the per-batch view '
             '(tools/prof_all.sh; sources under gpurun_out/ are scratch).  The default config\'s trace also contains the side '
             'measurements bench.py makes after the timed region (cacc_step_kernel<256,...> at E = 2^21, 60-launch graphs of the '
@@ -58,8 +58,8 @@ with open(os.path.join(dst, '%s_bench_kernel_stats.md' % tag), 'w') as f:
 
 # ---- other configs
 with open(os.path.join(dst, '%s_other_configs.md' % tag), 'w') as f:
-    f.write('# All benchmarked configs (round %s)\n\n`python bench.py --no-cpu-baseline --steps 10 --config config/config_<cfg>.ini` on one '
-            'MI355X (tools/prof_all.sh; the default row: `python bench.py --steps 20`); agent-steps/s = agents x replicas x lock-steps / s '
+    f.write('# All benchmarked configs (round %s)\n\n`python bench.py --full --no-cpu-baseline --steps 10 --config config/config_<cfg>.ini` on one '
+            'MI355X (tools/prof_all.sh; the default row: `python bench.py --full --steps 20`); agent-steps/s = agents x replicas x lock-steps / s '
             'over rollout + update.  Round-1 numbers from profiles/r01r_other_configs.md.\n\n' % tag[1:].lstrip('0'))
     f.write('| config | agents x replicas | round 1 M/s | this round M/s | ms / batch | LSTM lock-step kernel (roofline.kernel) | us / launch | frac of fp32 MFMA peak |\n'
             '|---|---|---:|---:|---:|---|---:|---:|\n')

@@ -34,8 +34,8 @@ def main(tag):
         json.dump(d0, f, indent=1)
         f.write('\n')
     out = ['# All benchmarked configs (round %s)\n' % tag.lstrip('r0'),
-           '`python bench.py --no-cpu-baseline --steps 10 --config config/config_<cfg>.ini` on one MI355X (`tools/prof_all.sh %s`; the '
-           'default row: `python bench.py --steps 20 --warmup 5`); agent-steps/s = agents x replicas x lock-steps / s over rollout + '
+           '`python bench.py --full --no-cpu-baseline --steps 10 --config config/config_<cfg>.ini` on one MI355X (`tools/prof_all.sh %s`; the '
+           'default row: `python bench.py --full --steps 20 --warmup 5`); agent-steps/s = agents x replicas x lock-steps / s over rollout + '
            'update.  `us / launch` = the LSTM lock-step launch inside the rollout (difference of two un-profiled rollout-graph '
            'timings, bench.py `roofline.how`).  "first" = the first measurement pass of this round (before the one-launch coupled '
            'step, the permuted column tiles and the in-kernel grid encoder).  The default line was sampled on six boxes of the pool '
@@ -67,7 +67,7 @@ def main(tag):
         f.write('\n'.join(out) + '\n')
     ks = ['# rocprofv3 --kernel-trace --stats summaries (round %s)' % tag.lstrip('r0'),
           'command (per config, after one untraced run that writes the TunableOp GEMM choices): `rocprofv3 --kernel-trace --stats -d '
-          '/tmp/prof_<cfg> -o bench -- python bench.py --no-cpu-baseline --steps 5 --warmup 2 --config config/config_<cfg>.ini`, then '
+          '/tmp/prof_<cfg> -o bench -- python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --config config/config_<cfg>.ini`, then '
           '`python tools/rocpd_stats.py /tmp/prof_<cfg>/bench_results.db --steps 7 --update` for the per-batch view '
           '(`tools/prof_cfg.sh`, `tools/prof_all.sh %s`).  The `calls=` column counts every launch of the traced process: the 7 '
           'batches AND bench.py\'s roofline side measurements (e.g. the 2^21-replica env step, the 60-launch LSTM graphs), so `/7` is '

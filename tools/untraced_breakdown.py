@@ -43,7 +43,7 @@ def rows(tag, o):
 
 
 print('# Untraced time breakdown of a batch (round %s)\n' % TAG[1:].lstrip('0'))
-print('Source: one `python bench.py --steps 20 --warmup 5` line (same process, same box as `%s_bench_default.json`); no profiler attached -- '
+print('Source: one `python bench.py --full --steps 20 --warmup 5` line (same process, same box as `%s_bench_default.json`); no profiler attached -- '
       'rocprofv3 serialises the graph\'s launches and reads ~5-10 %% longer per kernel (`%s_bench_kernel_stats.md` is the traced view).\n' % (TAG, TAG))
 for line in rows('%s -- %.1f M env-steps/s' % (d['config']['workload'], d['value'] / 1e6), d):
     print(line)
