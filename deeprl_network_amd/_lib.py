@@ -187,6 +187,11 @@ SIGNATURES = {
     'nmarl_lstm_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_step_x': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
                           _i64, _p, _i64, _p, _i64, C.POINTER(Head), _p],
+    'nmarl_lstm_wimage_bf16x3': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
+    'nmarl_lstm_step_x_bf16x3': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64,
+                                 _p, _p, _i64, _p, _i64, _p, _i64, C.POINTER(Head), _p],
+    'nmarl_lstm_step_x_enc_bf16x3': [_i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
+                                     C.POINTER(Head), C.POINTER(StepEnc), _p],
     'nmarl_lstm_msg_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_step_sync_words': [_i64, _i32],
     'nmarl_lstm_step_x_msg': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,

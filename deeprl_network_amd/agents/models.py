@@ -69,6 +69,9 @@ class IA2C:
         self.n_step = model_config.getint('batch_size')
         self.n_fc = model_config.getint('num_fc')
         self.n_lstm = model_config.getint('num_lstm')
+        # optional (absent: 'fp32', so every reference ini runs unchanged): the rollout's LSTM product arithmetic, see
+        # BatchedPolicy -- 'bf16x3' is opt-in and exists for the x-side uncoupled nets only
+        self.lstm_precision = ops.check_precision(model_config.get('lstm_precision', fallback='fp32').strip(), 'lstm_precision')
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -85,7 +88,7 @@ class IA2C:
         self.policy = self.policy_cls(self.n_feat, self.n_a, self.neighbor_mask, n_fc=self.n_fc,
                                       n_h=self.n_lstm, device=self.device, n_feat_ls=self.n_feat_ls,
                                       n_a_ls=None if self.identical_agent else self.n_a_ls,
-                                      obs_order=None if self._is_ma2c() else obs_order)
+                                      obs_order=None if self._is_ma2c() else obs_order, precision=self.lstm_precision)
         self.policy.params.init_reference_order()       # consumes np.random like the reference's ortho_init
         self.n_s = self.n_s_ls[0]
         N, E, H, T = self.n_agent, self.E, self.n_lstm, self.n_step

@@ -227,7 +227,8 @@ class BatchedPolicy:
     name = 'policy'
     fused_coupled = True          # coupled policies: use agents/sequence.py in the update
 
-    def __init__(self, n_feat, n_a, neighbor_mask, n_fc=64, n_h=64, device='cuda', n_feat_ls=None, n_a_ls=None, obs_order=None):
+    def __init__(self, n_feat, n_a, neighbor_mask, n_fc=64, n_h=64, device='cuda', n_feat_ls=None, n_a_ls=None, obs_order=None,
+                 precision='fp32'):
         """n_feat / n_a: own observation width / action count of an agent -- the maxima when agents differ.
         obs_order (IA2C family only): per agent the neighbours in the order the ENV concatenates them into that agent's
         observation (the ATSC envs list them north-east-south-west, atsc_env.py:263-271; None: ascending index, CACC).  The
@@ -241,7 +242,10 @@ class BatchedPolicy:
         ragged variables occupy the matching rows / columns of the padded tensors (ParamStore Layouts), actions an agent
         does not have carry a -1e30 logit bias (probability exactly 0: never drawn, no entropy, no gradient), and
         entries of variables the reference does not create (fingerprint / message layers of an agent without
-        neighbours) are masked out of the update."""
+        neighbours) are masked out of the update.
+        precision: arithmetic of the rollout's LSTM products (ops.PRECISIONS) -- 'fp32' exact; 'bf16x3' (opt-in, x-side
+        uncoupled nets only) the split-bf16 main product of the step kernel.  The update is fp32 either way."""
+        self.precision = ops.check_precision(precision, 'lstm_precision')
         self.device = torch.device(device)
         self.nbr_idx, self.nbr_cnt = ops.neighbor_table(neighbor_mask, self.device)
         self.N = len(self.nbr_cnt)
@@ -264,6 +268,10 @@ class BatchedPolicy:
         self.n_obs = n_feat * (1 + self.m_max)          # gathered observation slab width
         self.n_na = n_a * self.m_max                    # neighbour one-hot width
         self.params = ParamStore(self.N, self._phases(), self.device)
+        if self.precision != 'fp32' and (self.coupled or not self.xside):
+            why = 'a coupled net (its message term)' if self.coupled else 'not an x-side step (n_h = 64, input width a multiple of 32)'
+            raise ValueError('lstm_precision = %s: %s (%s) is fp32-only -- %s; bf16x3 exists for IA2C, IA2C-FP and ConseNet'
+                             % (self.precision, type(self).__name__, self.name, why))
 
     # -- helpers for the ragged reference shapes
     def _m(self, i):
@@ -384,7 +392,7 @@ class BatchedPolicy:
             z1, z2, xs = self._recur_addends(enc, h, second=second)
             wh, b = self.params[self.k_wh], self.params[self.k_b]
             if self.n_h == ops.FUSED_H:
-                ops.lstm_step_fused(h, wh, b, z1, z2, c, done, None, c_out, h_out, xs=xs)
+                ops.lstm_step_fused(h, wh, b, z1, z2, c, done, None, c_out, h_out, xs=xs, **self._prec_kw)
             else:
                 hk = h if done_is_zero else h * (1.0 - done).view(1, -1, 1)
                 z = torch.bmm(hk, wh) if z2 is None else torch.baddbmm(z2, hk, wh)
@@ -407,7 +415,7 @@ class BatchedPolicy:
                 z1, z2, xs = self._recur_addends(enc, h, save=save, fuse_msg=self.msg_inplace_ok or h_out.data_ptr() != h.data_ptr())
                 p = self.params
                 ops.lstm_step_policy(h, p[self.k_wh], p[self.k_b], z1, z2, c, done, c_out, h_out, p['pi_w'], p['pi_b'],
-                                     pi_out, act_out, xs=xs, gates=gates, **draw)
+                                     pi_out, act_out, xs=xs, gates=gates, **self._prec_kw, **draw)
             else:
                 self.step(enc, h, c, done, h_out, c_out, done_is_zero)
                 pi_out.copy_(self.pi(h_out))
@@ -485,13 +493,14 @@ class BatchedPolicy:
             elif ob is not None:
                 # the encoders run inside the launch: ob = dict(x = compact observation [E,N,5], fp = previous policies [N,E,4]);
                 # `enc` = where their output (the LSTM input) is kept for the update, or None
-                z1, z2, xs = None, None, (self._enc_spec(ob['x'], ob['fp'], enc, ob.get('env'), ob.get('bits')), self.params[self.k_wx], self._img)
+                z1, z2, xs = None, None, (self._enc_spec(ob['x'], ob['fp'], enc, ob.get('env'), ob.get('bits')), self.params[self.k_wx],
+                                          self._step_img)
             else:
                 z1, z2, xs = self._recur_addends(enc, h)
             p = self.params
             ops.lstm_step_policy_value(h, p[self.k_wh], p[self.k_b], z1, z2, c, done, p['pi_w'], p['pi_b'], pi_out, act_out,
                                        p['v_w'], p['v_b'], self.nbr_idx, self.n_a, v_out, xs=xs, h_out=h_out, c_out=c_out,
-                                       gates=gates, defer_action_term=defer_action_term, **draw)
+                                       gates=gates, defer_action_term=defer_action_term, **self._prec_kw, **draw)
         return act_out
 
     @property
@@ -554,7 +563,7 @@ class BatchedPolicy:
                 z1, z2, xs = self._recur_addends(enc, h, second=True, fuse_msg=True)
                 p = self.params
                 ops.lstm_step_value(h, p[self.k_wh], p[self.k_b], z1, z2, c, done, c_out, h_out, p['v_w'], p['v_b'],
-                                    action, self.nbr_idx, self.n_a, v_out, xs=xs)
+                                    action, self.nbr_idx, self.n_a, v_out, xs=xs, **self._prec_kw)
             else:
                 self.step(enc, h, c, done, h_out, c_out, done_is_zero, second=True)
                 self.value(h_out, ops.nbr_onehot(action, self.nbr_idx, self.n_a), out=v_out)
@@ -622,12 +631,23 @@ class BatchedPolicy:
         activations (dict of [N,E,*] tensors) the policy step's message terms are written to.  fuse_msg: the caller is a
         head step (policy / value), whose kernel can compute the message term itself (`_msg`)."""
         if self.xside:
-            return None, None, (enc, self.params[self.k_wx], self._img)
+            return None, None, (enc, self.params[self.k_wx], self._step_img)
         return enc, None, None
 
     # -- x-side product inside the fused step (uncoupled nets: the LSTM input is the encoders' output itself)
     k_wx = None
     _img = None
+    _img_x3 = None          # precision 'bf16x3': the split image the rollout's step kernels read (_img stays: the update is fp32)
+
+    @property
+    def _prec_kw(self):
+        """The step ops' precision argument -- passed only when it is not the default (the ops' fp32 signature stays as it was)."""
+        return {} if self.precision == 'fp32' else {'precision': self.precision}
+
+    @property
+    def _step_img(self):
+        """The weight image of the rollout's step kernels (lstm_step_x): the split image under bf16x3."""
+        return self._img_x3 if self.precision == 'bf16x3' else self._img
 
     @property
     def xside(self):
@@ -640,6 +660,8 @@ class BatchedPolicy:
         batched engine does it at the first lock-step of a batch and before the update's forward pass)."""
         if self.xside:
             self._img = ops.lstm_wimage(self.params[self.k_wx], self.params[self.k_wh], out=self._img)
+            if self.precision == 'bf16x3':
+                self._img_x3 = ops.lstm_wimage(self.params[self.k_wx], self.params[self.k_wh], out=self._img_x3, precision='bf16x3')
             if self.msg_kind and ops.msg_supported(self.msg_kind, self.m_max, self.n_h):
                 self._msg_img = ops.lstm_msg_wimage(self.params['w_msg'], out=self._msg_img)
 

@@ -625,6 +625,56 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, cons
         NMARL_MFMA16(A1.w, q0, q1, q2, q3)                                                \
     }
 
+// ---- PREC 1 (bf16x3, opt-in): every fp32 operand a = hi + lo with hi = bf16_rne(a), lo = bf16_rne(a - hi); a product is
+// hi_a hi_b + hi_a lo_b + lo_a hi_b on v_mfma_f32_16x16x32_bf16 (each bf16 x bf16 product exact in fp32, fp32 accumulation;
+// the dropped lo_a lo_b and the two roundings leave ~3 * 2^-18 |a||b| per product).  A chunk's 32 k rows are ONE k-block:
+// lane (c, grp) holds A[row c][k = 8 grp + j] and B[k = 8 grp + j][col c], and MFMA k index 8 grp + j is chunk row 4 grp + j
+// (j < 4), 16 + 4 grp + j - 4 (j >= 4) -- exactly the rows the lane's fp32 A registers A0 / A1 already hold, so the A fragment
+// is those registers split in place; the image (nmarl_lstm_wimage_bf16x3) stores B in the same k order.
+// Chunk image (same 40 KB as the fp32 one, so the staging ring is unchanged): lane (c, grp) owns X3_PITCH dwords at
+// (16 grp + c) X3_PITCH; tile t's hi fragment is dwords 8 t .. 8 t + 3, its lo fragment 8 t + 4 .. 8 t + 7 -- one ds_read_b128
+// each; X3_PITCH = 4 x odd keeps the 16 lanes of a group on disjoint banks.
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+constexpr int X3_PITCH = 132;
+static_assert(63 * X3_PITCH + 128 <= CH_FLOATS, "bf16x3 chunk image fits the fp32 chunk");
+
+__device__ __forceinline__ void split_bf16x3(const float4 a0, const float4 a1, bf16x8& hi, bf16x8& lo) {
+    const float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const __bf16 h = (__bf16)v[j];          // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
+        hi[j] = h;
+        lo[j] = (__bf16)(v[j] - (float)h);      // exact difference, rounded once
+    }
+}
+
+// the three split products of one column tile: small terms first
+#define NMARL_MFMA3(ACC, ah, al, bh, bl)                                                  \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, ACC, 0, 0, 0);                  \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, ACC, 0, 0, 0);                  \
+    ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, ACC, 0, 0, 0);
+
+// a whole chunk: 16 tiles x 3 MFMAs, the next tile's two ds_read_b128 in flight while one tile multiplies (one tile of look-ahead:
+// a second one pushes the policy + value forms, which hold the x-side addend through the K loop, into scratch)
+__device__ __forceinline__ void chunk_bf16x3(f32x4 (&acc)[16], const float* buf, const float4 a0, const float4 a1) {
+    bf16x8 ah, al;
+    split_bf16x3(a0, a1, ah, al);
+    const bf16x8* q = reinterpret_cast<const bf16x8*>(buf);      // lane base applied: q[2 t] = hi, q[2 t + 1] = lo of tile t
+    bf16x8 p0 = q[0], p1 = q[1], r0 = q[2], r1 = q[3];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 16; t += 2) {
+        NMARL_MFMA3(acc[t], ah, al, p0, p1)
+        __builtin_amdgcn_sched_barrier(0);
+        if (t + 2 < 16) { p0 = q[2 * t + 4]; p1 = q[2 * t + 5]; }
+        __builtin_amdgcn_sched_barrier(0);
+        NMARL_MFMA3(acc[t + 1], ah, al, r0, r1)
+        __builtin_amdgcn_sched_barrier(0);
+        if (t + 2 < 16) { r0 = q[2 * t + 6]; r1 = q[2 * t + 7]; }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // MSG: the message term of a coupled net computed IN the step kernel (no gather / GEMM / bias-activation launches):
 //   1  lstm_comm (agents/utils.py:182-199):  hm = relu([h_j : j in nbr(i)] @ W_msg + b_msg)          -> x[:, KX-64:]
 //   2  lstm_ic3  (agents/utils.py:395-400):  s  = mean_j(h_j) @ W_msg + b_msg + enc                   -> x (KX = 64)
@@ -650,7 +700,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, cons
 // CARRY (HEAD 4, round 6): 0 none; 1 the re-step hands its message term on (carry_out / mm_next); 2 it also STARTS from the one the
 // previous launch handed on (carry_in): no neighbour rows, no product in front of the K loop.  A template parameter, not a launch
 // argument: at 256 registers a run-time choice cost every form of the kernel ~4 us (profiles/r06_ab_msg_carry.txt).
-template <int HEAD, int MSG, int ENC = 0, int CARRY = 0>
+// PREC (opt-in): 0 exact fp32 (v_mfma_f32_16x16x4_f32), 1 bf16x3 for the main K loop and the value re-step's h' @ Wh (see
+// chunk_bf16x3; img is then nmarl_lstm_wimage_bf16x3's image).  The encoder pre-phase, epilogues and heads stay fp32.
+template <int HEAD, int MSG, int ENC = 0, int CARRY = 0, int PREC = 0>
 __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const FusedArgs& a = xa.f;
@@ -710,6 +762,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     // (a static s_setprio 1 for the younger wave group 4..7 of the coupled kernels -- MI355X_MICROARCH.md's lever for 8-wave blocks --
     // was tried in round 6: +0.3 % on the grid's lock-step, same box: not kept)
     static_assert(HEAD != 4 || MSG != 0, "HEAD 4 is the coupled nets' policy + value step");
+    static_assert(PREC == 0 || MSG == 0, "bf16x3: the uncoupled nets' step forms only");
     constexpr bool PV = HEAD == 3 || HEAD == 4;          // policy step + value re-step in this launch
     // HEAD 4: this launch's flag value = generation + 1.  The load is ISSUED here and consumed after the K loop: a
     // readfirstlane right away would park the wave for a memory round trip before it has requested anything else
@@ -811,6 +864,14 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
         const float kf_ = (ch) < nx ? 1.0f : keepA;                                       \
         d0.x *= kf_; d0.y *= kf_; d0.z *= kf_; d0.w *= kf_;                               \
         d1.x *= kf_; d1.y *= kf_; d1.z *= kf_; d1.w *= kf_;                               \
+    }
+    // one chunk of the main product from the chunk buffer at CB (the lane's base applied here): fp32 or bf16x3 (PREC)
+#define NMARL_KCHUNK(CB, A0, A1)                                                          \
+    if constexpr (PREC != 0) {                                                            \
+        chunk_bf16x3(acc, (CB) + (16 * grp + c) * X3_PITCH, A0, A1);                      \
+    } else {                                                                              \
+        const float* buf = (CB) + (4 * grp * 16 + c) * 20;                                \
+        NMARL_CHUNK(buf, A0, A1)                                                          \
     }
     if (MSG == 0 && ENC == 0) { NMARL_A_LOAD(0, a0, a1) }
     // ---- ENC: the input encoders' operands (see the kernel's header), REQUESTED here -- behind the two weight chunks, in front of
@@ -1322,8 +1383,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
 #pragma unroll
                 for (int t = 0; t < 16; ++t) zs[t] = acc[t];
             }
-            const float* buf = lds + bsel * CH_FLOATS + (4 * grp * 16 + c) * 20;
-            NMARL_CHUNK(buf, a0, a1)
+            NMARL_KCHUNK(lds + bsel * CH_FLOATS, a0, a1)
             if (ENC_LDS && ch < nx && e_out != nullptr && row0 + c < a.E) {      // ENC: this chunk of the encoded input, for the update
                 float* so = e_out + (int64_t)n * e_out_sn + (row0 + c) * e_out_row + 4 * grp + ch * CH_K;
                 *reinterpret_cast<float4*>(so) = a0;
@@ -1346,8 +1406,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) zs[t] = acc[t];
         }
-        const float* buf = lds + bsel * CH_FLOATS + (4 * grp * 16 + c) * 20;
-        NMARL_CHUNK(buf, a0, a1)
+        NMARL_KCHUNK(lds + bsel * CH_FLOATS, a0, a1)
     }
     NMARL_STAMP(20)
     if (CP_PARK) {
@@ -1523,12 +1582,11 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
         }
 #pragma unroll
         for (int hc = 0; hc < 2; ++hc) {
-            const float* buf = lds + ((nx + hc) % NBUF) * CH_FLOATS + (4 * grp * 16 + c) * 20;
             const float* ar = a_tile + c * APITCH + hc * CH_K + 4 * grp;
             float4 r0, r1;
             r0.x = ar[0] * keepA; r0.y = ar[1] * keepA; r0.z = ar[2] * keepA; r0.w = ar[3] * keepA;
             r1.x = ar[16] * keepA; r1.y = ar[17] * keepA; r1.z = ar[18] * keepA; r1.w = ar[19] * keepA;
-            NMARL_CHUNK(buf, r0, r1)
+            NMARL_KCHUNK(lds + ((nx + hc) % NBUF) * CH_FLOATS, r0, r1)
         }
         NMARL_STAMP(23)
         __builtin_amdgcn_wave_barrier();                 // every lane has read its A operands: the tile may be overwritten
@@ -1665,6 +1723,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
 #undef NMARL_STAGE_STORE
 #undef NMARL_A_LOAD
 #undef NMARL_A_MASK
+#undef NMARL_KCHUNK
 }
 
 // image[n][ch][kl][c][t] = W[32 ch + kl][64 (t >> 2) + 4 c + (t & 3)] (t < 16; 16..19 = 0), W = [wx (KX rows); wh (64 rows)]:
@@ -1679,6 +1738,35 @@ __global__ void lstm_wimage_kernel(const int N, const int KX, const float* wx, c
     float v = 0.0f;
     const int col = (t >> 2) * H + 4 * cc + (t & 3);
     if (t < 16) v = k < KX ? wx[(int64_t)n * wx_sn + (int64_t)k * G4 + col] : wh[(int64_t)n * wh_sn + (int64_t)(k - KX) * G4 + col];
+    img[(int64_t)n * img_sn + o] = v;
+}
+
+// bf16x3 image: the fp32 image's chunks (same bytes per k row), each in the layout of chunk_bf16x3 -- dword
+// (16 grp + c) X3_PITCH + 8 t + 4 h + jp of chunk ch packs elements j = 2 jp, 2 jp + 1 (low half first) of the hi (h = 0) or
+// lo (h = 1) fragment of W[32 ch + kr(j)][64 (t >> 2) + 4 c + (t & 3)], kr(j) = 4 grp + j (j < 4), 16 + 4 grp + j - 4; the
+// rest of the chunk is 0.  hi = bf16_rne(w), lo = bf16_rne(w - hi) by plain casts (NaN stays NaN).
+__global__ void lstm_wimage_bf16x3_kernel(const int N, const int KX, const float* wx, const int64_t wx_sn, const float* wh,
+                                          const int64_t wh_sn, unsigned* img, const int64_t img_sn) {
+    const int per_agent = (KX + H) * 320;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)N * per_agent) return;
+    const int n = (int)(i / per_agent), o = (int)(i % per_agent);
+    const int ch = o / CH_FLOATS, r = o % CH_FLOATS;
+    const int gc = r / X3_PITCH, q = r % X3_PITCH;
+    unsigned v = 0u;
+    if (gc < 64 && q < 128) {
+        const int grp = gc >> 4, cc = gc & 15, t = q >> 3, hl = (q >> 2) & 1, jp = q & 3;
+        const int col = (t >> 2) * H + 4 * cc + (t & 3);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = 2 * jp + e;
+            const int k = ch * CH_K + (j < 4 ? 4 * grp + j : 16 + 4 * grp + j - 4);
+            const float w = k < KX ? wx[(int64_t)n * wx_sn + (int64_t)k * G4 + col] : wh[(int64_t)n * wh_sn + (int64_t)(k - KX) * G4 + col];
+            const __bf16 hb = (__bf16)w;
+            const __bf16 b = hl ? (__bf16)(w - (float)hb) : hb;
+            v |= (unsigned)__builtin_bit_cast(unsigned short, b) << (16 * e);
+        }
+    }
     img[(int64_t)n * img_sn + o] = v;
 }
 
@@ -1790,6 +1878,17 @@ extern "C" int nmarl_lstm_wimage(int32_t N, int32_t KX, const float* wx, int64_t
     return nmarl_check_launch();
 }
 
+extern "C" int nmarl_lstm_wimage_bf16x3(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
+                                        float* img, int64_t img_sn, void* stream) {
+    if (N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || !wh || !img || (KX > 0 && !wx) || img_sn < (int64_t)(KX + H) * 320 ||
+        (img_sn % 4) || ((uintptr_t)img % 16) || wh_sn < H * G4 || (KX > 0 && wx_sn < (int64_t)KX * G4))
+        return NMARL_EINVAL;
+    const int64_t total = (int64_t)N * (KX + H) * 320;
+    hipLaunchKernelGGL(lstm_wimage_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       N, KX, wx, wx_sn, wh, wh_sn, reinterpret_cast<unsigned*>(img), img_sn);
+    return nmarl_check_launch();
+}
+
 extern "C" int nmarl_lstm_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t w_sn, float* img, int64_t img_sn,
                                      void* stream) {
     if (N <= 0 || K <= 0 || K % CH_K || K > 256 || !w_msg || !img || w_sn < (int64_t)K * 64 || img_sn < (int64_t)K * 64 ||
@@ -1873,8 +1972,9 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
                                  const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
                                  float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
                                  const nmarl_msg_t* msg, void* stream, const nmarl_step_enc_t* enc = nullptr,
-                                 const nmarl_grid_env_t* genv = nullptr) {
+                                 const nmarl_grid_env_t* genv = nullptr, const int prec = 0) {
     const int mk = msg ? msg->kind : 0;
+    if (prec != 0 && (mk != 0 || genv)) return NMARL_EINVAL;     // bf16x3: the MSG = 0 forms only
     const int KM = mk ? H : 0;                   // columns of x the message pre-phase produces
     if (Hh != H || E < 0 || N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || KX2 < 0 || KX2 > KX || KX2 % CH_K || mk < 0 || mk > 3 ||
         (mk && (KX2 != 0 || KX < H)) ||
@@ -1977,6 +2077,8 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
         NMARL_SET_LDS((lstm_step_x_kernel<4, 1>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 2>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 1, 1>))
         NMARL_SET_LDS((lstm_step_x_kernel<4, 1, 0, 1>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 2, 0, 1>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 1, 1, 1>))
         NMARL_SET_LDS((lstm_step_x_kernel<4, 1, 0, 2>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 2, 0, 2>)) NMARL_SET_LDS((lstm_step_x_kernel<4, 1, 1, 2>))
+        NMARL_SET_LDS((lstm_step_x_kernel<0, 0, 0, 0, 1>)) NMARL_SET_LDS((lstm_step_x_kernel<1, 0, 0, 0, 1>))
+        NMARL_SET_LDS((lstm_step_x_kernel<2, 0, 0, 0, 1>)) NMARL_SET_LDS((lstm_step_x_kernel<3, 0, 0, 0, 1>))
 #undef NMARL_SET_LDS
         lds_once.done(lds_bit);
     }
@@ -2032,12 +2134,20 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lb_e) != hipSuccess ||
                     hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lb_e) != hipSuccess ||
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 1, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lb_e) != hipSuccess ||
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 2, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lb_e) != hipSuccess)
                     return NMARL_EHIP;
                 enc_once.done(bit);
             }
-            if (single) hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 2>), grid, dim3(512), lb_e, static_cast<hipStream_t>(stream), xa);
-            else hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 1>), grid, dim3(512), lb_e, static_cast<hipStream_t>(stream), xa);
+            hipStream_t st = static_cast<hipStream_t>(stream);
+            if (prec) {
+                if (single) hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 2, 0, 1>), grid, dim3(512), lb_e, st, xa);
+                else hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 1, 0, 1>), grid, dim3(512), lb_e, st, xa);
+            } else if (single) hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 2>), grid, dim3(512), lb_e, st, xa);
+            else hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 1>), grid, dim3(512), lb_e, st, xa);
             return nmarl_check_launch();
         }
     }
@@ -2099,7 +2209,9 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (mk == 1 && kind == 3) lb_extra += 512 * sizeof(float4);      // HEAD 4 / MSG 1: the parked cell-state slots (CP_PARK)
-#define NMARL_LX(HD, MS) hipLaunchKernelGGL((lstm_step_x_kernel<HD, MS>), grid, dim3(512), lb + lb_extra, st, xa)
+#define NMARL_LX(HD, MS)                                                                                                         \
+    if (prec) hipLaunchKernelGGL((lstm_step_x_kernel<HD, 0, 0, 0, 1>), grid, dim3(512), lb + lb_extra, st, xa);                 \
+    else hipLaunchKernelGGL((lstm_step_x_kernel<HD, MS>), grid, dim3(512), lb + lb_extra, st, xa)
     // the one-launch lock-steps: by what the caller hands on between them (nmarl_msg_t carry_in / carry_out / mean_next)
     const int carry = !msg ? 0 : msg->carry_in ? 2 : (msg->carry_out || msg->mean_next) ? 1 : 0;
 #define NMARL_LC(MS, EN)                                                                                                         \
@@ -2132,6 +2244,18 @@ extern "C" int nmarl_lstm_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, c
     return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, KX2, x2, x2_sn, x2_row, h_in, h_sn, img, img_sn, bias, bias_sn, zadd1, zadd1_sn,
                          zadd2, zadd2_sn, c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr,
                          stream);
+}
+
+extern "C" int nmarl_lstm_step_x_bf16x3(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
+                                        int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
+                                        const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
+                                        int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
+                                        const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
+                                        float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
+                                        void* stream) {
+    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, KX2, x2, x2_sn, x2_row, h_in, h_sn, img, img_sn, bias, bias_sn, zadd1, zadd1_sn,
+                         zadd2, zadd2_sn, c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr,
+                         stream, nullptr, nullptr, 1);
 }
 
 extern "C" int nmarl_lstm_step_x_msg(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
@@ -2185,6 +2309,16 @@ extern "C" int nmarl_lstm_step_x_enc(int64_t E, int32_t N, int32_t Hh, int32_t K
     if (!enc || !head) return NMARL_EINVAL;
     return launch_step_x(E, N, Hh, KX, nullptr, 0, 0, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
                          c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr, stream, enc);
+}
+
+extern "C" int nmarl_lstm_step_x_enc_bf16x3(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* h_in, int64_t h_sn,
+                                            const float* img, int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev,
+                                            int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn, float* c_new,
+                                            int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
+                                            const nmarl_step_enc_t* enc, void* stream) {
+    if (!enc || !head) return NMARL_EINVAL;
+    return launch_step_x(E, N, Hh, KX, nullptr, 0, 0, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
+                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr, stream, enc, nullptr, 1);
 }
 
 #ifdef NMARL_STEP_TIMELINE

@@ -26,6 +26,9 @@ def parse_args(argv=None):
                     help='experiment config path')
     sp.add_argument('--num-envs', type=int, default=None, help='replicas per GPU (overrides ENV_CONFIG num_envs)')
     sp.add_argument('--no-graph', action='store_true', help='do not capture the rollout in a hipGraph')
+    sp.add_argument('--lstm-precision', choices=('fp32', 'bf16x3'), default=None,
+                    help='arithmetic of the rollout\'s LSTM products (overrides MODEL_CONFIG lstm_precision; default fp32). '
+                         'bf16x3: opt-in split-bf16 form, IA2C / IA2C-FP / ConseNet only; the update stays fp32')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -65,10 +68,17 @@ def train(args):
     world, rank, local, group = _dist()
     dirs = init_dir(args.base_dir)
     init_log(dirs['log'], rank)
-    if rank == 0:
-        copy_file(args.config_dir, dirs['data'])
     config = configparser.ConfigParser()
     config.read(args.config_dir)
+    if rank == 0:
+        copy_file(args.config_dir, dirs['data'])
+        if args.lstm_precision is not None:
+            # the override goes into the run's copy of the ini: `evaluate` rebuilds the policy from that file
+            config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
+            with open(os.path.join(dirs['data'], os.path.basename(args.config_dir)), 'w') as f:
+                config.write(f)
+    elif args.lstm_precision is not None:
+        config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
     env_cfg = config['ENV_CONFIG']
     total_step = int(config.getfloat('TRAIN_CONFIG', 'total_step'))
     test_step = int(config.getfloat('TRAIN_CONFIG', 'test_interval'))

@@ -208,20 +208,49 @@ def xside_supported(kx, n_h):
     return n_h == FUSED_H and kx % 32 == 0 and 0 <= kx <= XSIDE_MAX_K
 
 
-def lstm_wimage(wx, wh, out=None):
+# arithmetic of the x-side step's main product (and the value re-step's h' @ Wh): 'fp32' exact (the default everywhere),
+# 'bf16x3' the opt-in split-bf16 form (csrc/lstm_mfma.hip chunk_bf16x3) -- the MSG = 0 step forms of the uncoupled nets only
+PRECISIONS = ('fp32', 'bf16x3')
+
+
+def check_precision(precision, what='precision'):
+    if precision not in PRECISIONS:
+        raise ValueError('%s: %r is not one of %s' % (what, precision, ', '.join(PRECISIONS)))
+    return precision
+
+
+def lstm_wimage(wx, wh, out=None, precision='fp32'):
     """Chunked LDS image of [wx; wh] (wx [N,KX,4H] or None, wh [N,H,4H]) for the x-mode of the fused step; rebuild it
-    whenever the weights change.  -> [N, (KX+64)*320] f32."""
+    whenever the weights change.  -> [N, (KX+64)*320] f32; precision 'bf16x3': the split (hi, lo) image of the same bytes,
+    [N, 2*(KX+64)*320] bf16 (nmarl_lstm_wimage_bf16x3)."""
+    check_precision(precision, 'lstm_wimage')
     N = wh.shape[0]
     KX = 0 if wx is None else wx.shape[1]
     n = lib.nmarl_lstm_wimage_floats(KX)
+    x3 = precision == 'bf16x3'
+    dt, width = (torch.bfloat16, 2 * n) if x3 else (F32, n)
     if out is None:
-        out = torch.empty(N, n, dtype=F32, device=wh.device)
+        out = torch.empty(N, width, dtype=dt, device=wh.device)
+    if out.shape != (N, width) or out.stride(1) != 1 or out.stride(0) % (2 if x3 else 1):
+        raise _lib.NmarlError('lstm_wimage: out must be [%d, %d] %s with rows of whole words' % (N, width, dt))
     if wh.stride(2) != 1 or wh.stride(1) != wh.shape[2] or (wx is not None and (wx.stride(2) != 1 or wx.stride(1) != wx.shape[2])):
         raise _lib.NmarlError('lstm_wimage: weights need contiguous per-agent panels')
-    check(lib.nmarl_lstm_wimage(N, KX, ptr(wx, F32, strided=True), 0 if wx is None else wx.stride(0),
-                                ptr(wh, F32, strided=True), wh.stride(0), ptr(out, F32), out.stride(0), stream()),
-          'nmarl_lstm_wimage')
+    fn, name = (lib.nmarl_lstm_wimage_bf16x3, 'nmarl_lstm_wimage_bf16x3') if x3 else (lib.nmarl_lstm_wimage, 'nmarl_lstm_wimage')
+    check(fn(N, KX, ptr(wx, F32, strided=True), 0 if wx is None else wx.stride(0), ptr(wh, F32, strided=True), wh.stride(0),
+             ptr(out, dt), out.stride(0) // (2 if x3 else 1), stream()), name)
     return out
+
+
+def _img_arg(img, N, KX, precision, what):
+    """(pointer, agent stride in 4-byte words) of a step kernel's weight image, checked against KX and the precision."""
+    n = lib.nmarl_lstm_wimage_floats(KX)
+    if precision == 'bf16x3':
+        if img.dtype != torch.bfloat16 or img.shape != (N, 2 * n) or img.stride(0) % 2:
+            raise _lib.NmarlError('%s: bf16x3 needs the split image lstm_wimage(..., precision="bf16x3") of KX = %d' % (what, KX))
+        return ptr(img, torch.bfloat16), img.stride(0) // 2
+    if img.dtype != F32 or img.shape != (N, n):
+        raise _lib.NmarlError('%s: weight image does not match KX = %d (fp32)' % (what, KX))
+    return ptr(img, F32), img.stride(0)
 
 
 MSG_GATHER_RELU, MSG_MEAN_ADD, MSG_DIAL = 1, 2, 3      # nmarl_msg_t.kind: lstm_comm / lstm_ic3 / lstm_dial
@@ -245,29 +274,31 @@ def lstm_msg_wimage(w_msg, out=None):
     return out
 
 
-def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, what):
+def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, what, precision='fp32'):
     """nmarl_lstm_step_x: xs = (x [N,E,KX1] or None, wx (unused here: it is inside the image), image[, x2 [N,E,KX2][, msg]]):
     the LSTM input is [x | x2] (x2 optional), or [x | message term] with msg = dict(kind, nbr_idx, w_msg, b_msg, img,
     enc=None, out=None): the last 64 columns are computed inside the kernel from the neighbours' h (heads only); kind
-    MSG_DIAL: from msg['src'] [N,E,64], the senders' message vectors, with hm (before `enc` is added) -> msg['out2']."""
+    MSG_DIAL: from msg['src'] [N,E,64], the senders' message vectors, with hm (before `enc` is added) -> msg['out2'].
+    precision 'bf16x3': the split-bf16 main product (image from lstm_wimage(..., precision='bf16x3')); no message term."""
     N, E, H = h.shape
     x, _, img = xs[:3]
     x2 = xs[3] if len(xs) > 3 else None
     msg = xs[4] if len(xs) > 4 else None
+    x3 = check_precision(precision, what) == 'bf16x3'
+    if x3 and msg is not None:
+        raise _lib.NmarlError('%s: bf16x3 exists for the uncoupled nets\' step forms only (no message term); coupled nets are fp32-only' % what)
     if isinstance(x, dict):          # the input encoders run inside the launch (step_enc_spec): x is their description
         if head is None or head.kind != 3 or x2 is not None or msg is not None or zadd1 is not None or zadd2 is not None:
             raise _lib.NmarlError('%s: the in-kernel encoders need the policy + value step of an uncoupled net' % what)
         KX = FC_J if x.get('w_fp') is None else 2 * FC_J          # (one encoder: IA2C / ConseNet; two: IA2C-FP)
-        if img.shape != (N, lib.nmarl_lstm_wimage_floats(KX)):
-            raise _lib.NmarlError('%s: weight image does not match KX = %d' % (what, KX))
-        check(lib.nmarl_lstm_step_x_enc(E, N, H, KX, *_pn(h), ptr(img, F32), img.stride(0), *_bias(bias), *_pn(c_prev), ptr(done, F32),
-                                        *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head), C.byref(_step_enc(x, N, E)), stream()), what)
+        fn = lib.nmarl_lstm_step_x_enc_bf16x3 if x3 else lib.nmarl_lstm_step_x_enc
+        check(fn(E, N, H, KX, *_pn(h), *_img_arg(img, N, KX, precision, what), *_bias(bias), *_pn(c_prev), ptr(done, F32),
+                 *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head), C.byref(_step_enc(x, N, E)), stream()), what)
         return
     xp, x_sn, x_row, K1 = (None, 0, 0, 0) if x is None else (*_rows_view(x, x.shape[2], what + ' x'), x.shape[2])
     x2p, x2_sn, x2_row, K2 = (None, 0, 0, 0) if x2 is None else (*_rows_view(x2, x2.shape[2], what + ' x2'), x2.shape[2])
     KX = K1 + K2 + (H if msg is not None else 0)
-    if img.shape != (N, lib.nmarl_lstm_wimage_floats(KX)):
-        raise _lib.NmarlError('%s: weight image does not match KX = %d' % (what, KX))
+    img_p, img_sn = _img_arg(img, N, KX, precision, what)
     if msg is not None:
         if head is None or x2 is not None or zadd1 is not None or zadd2 is not None:
             raise _lib.NmarlError('%s: the in-kernel message term needs a head and excludes x2 / addends' % what)
@@ -325,7 +356,7 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
             # slot t of the saved LSTM inputs -- receives their output and is read back by the K loop
             if head.kind != 3 or msg['kind'] != MSG_GATHER_RELU or x is None:
                 raise _lib.NmarlError('%s: the in-kernel encoders of a coupled net need lstm_comm\'s policy + value step and its x slot' % what)
-            check(lib.nmarl_lstm_step_x_msg_enc(E, N, H, KX, xp, x_sn, x_row, *_pn(h), ptr(img, F32), img.stride(0), *_bias(bias),
+            check(lib.nmarl_lstm_step_x_msg_enc(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
                                                 *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
                                                 C.byref(m), C.byref(_step_enc(dict(spec, out=None), N, E)), stream()), what)
             return
@@ -345,15 +376,16 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
             if genv['words'].dtype != torch.int64 or genv['words'].numel() < lib.nmarl_lstm_step_grid_words(E):
                 raise _lib.NmarlError('%s: genv["words"] must hold nmarl_lstm_step_grid_words(E) 64-bit words' % what)
             g.words = ptr(genv['words'], torch.int64)
-            check(lib.nmarl_lstm_step_x_msg_grid(E, N, H, KX, xp, x_sn, x_row, *_pn(h), ptr(img, F32), img.stride(0), *_bias(bias),
+            check(lib.nmarl_lstm_step_x_msg_grid(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
                                                  *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
                                                  C.byref(m), C.byref(g), stream()), what)
             return
-        check(lib.nmarl_lstm_step_x_msg(E, N, H, KX, xp, x_sn, x_row, *_pn(h), ptr(img, F32), img.stride(0), *_bias(bias),
+        check(lib.nmarl_lstm_step_x_msg(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
                                         *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
                                         C.byref(m), stream()), what)
         return
-    check(lib.nmarl_lstm_step_x(E, N, H, KX, xp, x_sn, x_row, K2, x2p, x2_sn, x2_row, *_pn(h), ptr(img, F32), img.stride(0),
+    fn = lib.nmarl_lstm_step_x_bf16x3 if x3 else lib.nmarl_lstm_step_x
+    check(fn(E, N, H, KX, xp, x_sn, x_row, K2, x2p, x2_sn, x2_row, *_pn(h), img_p, img_sn,
                                 *_bias(bias), *_pn(zadd1), *_pn(zadd2), *_pn(c_prev), ptr(done, F32), *_pn(gates),
                                 *_pn(c_out), *_pn(h_out), None if head is None else C.byref(head), stream()), what)
 
@@ -492,15 +524,21 @@ def step_handoff_supported(N, E, device, K=128):
     return N * ((E + 127) // 128) <= cap
 
 
-def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=None):
+def _fp32_only(precision, what):
+    if check_precision(precision, what) != 'fp32':
+        raise _lib.NmarlError('%s: bf16x3 needs the x-side mode (xs with the split image); this path is fp32-only' % what)
+
+
+def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=None, precision='fp32'):
     """(gates, c', h') = cell(zadd1 (+ zadd2) + (h*(1-done)) @ wh + bias, c_prev, done) in ONE MFMA kernel
     (H = 64).  All operands [N,E,*] panels (strided slots allowed); h_out / c_out may alias h / c_prev.
     xs = (x, wx, image): the x-side product x @ wx is computed inside as well (K = KX + 64, image from lstm_wimage;
-    zadd1 / zadd2 may then be None)."""
+    zadd1 / zadd2 may then be None).  precision: see _step_x ('bf16x3' with xs only)."""
     N, E, H = h.shape
     if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, None, 'nmarl_lstm_step_x')
+        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, None, 'nmarl_lstm_step_x', precision)
         return h_out, c_out
+    _fp32_only(precision, 'lstm_step_fused')
     if wh.stride(2) != 1 or wh.stride(1) != 4 * H:
         raise _lib.NmarlError('lstm_step_fused: wh must be [N,H,4H] with contiguous [H,4H] panels')
     check(lib.nmarl_lstm_step_fused(E, N, H, *_pn(h), ptr(wh, F32, strided=True), wh.stride(0), *_bias(bias),
@@ -512,11 +550,12 @@ def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out
 HEAD_MAX_A = 8      # widest action set the fused head epilogue supports (csrc/lstm_mfma.hip: MAXA)
 
 
-def _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, head, what, xs=None, gates=None):
+def _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, head, what, xs=None, gates=None, precision='fp32'):
     N, E, H = h.shape
     if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, what)
+        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, what, precision)
         return
+    _fp32_only(precision, what)
     if gates is not None:
         raise _lib.NmarlError('%s: gates output needs the x-side mode' % what)
     if wh.stride(2) != 1 or wh.stride(1) != 4 * H:
@@ -534,7 +573,7 @@ def _head_param(w, what):
 
 
 def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w, pi_b, pi_out, act_out, mode,
-                     u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, gates=None):
+                     u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, gates=None, precision='fp32'):
     """forward('p') of one lock-step in ONE kernel: the fused step (lstm_step_fused), then in its epilogue
     pi = softmax(h' @ pi_w + pi_b) -> pi_out [N,E,A] and the action draw of sample_actions -> act_out [E,N]."""
     N, E, H = h.shape
@@ -546,11 +585,12 @@ def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w
     hd.pi_out, hd.pi_sn = _pn(pi_out)
     hd.act_out, hd.u = ptr(act_out, torch.uint8), ptr(u, F32)
     hd.seed, hd.env_id_base, hd.step, hd.step_dev = seed, env_id_base, int(step), ptr(step_dev, torch.int64)
-    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[p]', xs, gates)
+    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[p]', xs, gates, precision)
     return pi_out, act_out
 
 
-def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, v_b, action, nbr_idx, n_a, v_out, xs=None):
+def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, v_b, action, nbr_idx, n_a, v_out, xs=None,
+                    precision='fp32'):
     """forward('v') of one lock-step in ONE kernel: the fused step, then v = [h', onehot(neighbour actions)] @ v_w
     + v_b -> v_out [N,E]; the one-hot rows are gathered from action [E,N] u8 (no one-hot tensor)."""
     N, E, H = h.shape
@@ -564,13 +604,13 @@ def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, 
     if v_out.dim() != 2 or v_out.stride(1) != 1:
         raise _lib.NmarlError('lstm_step_value: v_out must be [N,E] with unit column stride')
     hd.v_out, hd.v_sn = ptr(v_out, F32, strided=True), v_out.stride(0)
-    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[v]', xs)
+    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[v]', xs, precision=precision)
     return v_out
 
 
 def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_out, act_out, v_w, v_b, nbr_idx, n_a,
                            v_out, mode, u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, h_out=None,
-                           c_out=None, gates=None, defer_action_term=False):
+                           c_out=None, gates=None, defer_action_term=False, precision='fp32'):
     """forward('p') AND forward('v') of one lock-step (quirk Q1) for nets without a cross-agent recurrence: one MFMA
     kernel (policy step + pi + draw, then the value re-step from the new state with the same addend and the critic on
     h'') + the critic's neighbour-action term, which needs all agents' draws, added by one small launch (unless
@@ -594,8 +634,9 @@ def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_ou
     hd.v_out, hd.v_sn = ptr(v_out, F32, strided=True), v_out.stride(0)
     h_out, c_out = (h if h_out is None else h_out), (c if c_out is None else c_out)
     if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c, done, gates, c_out, h_out, xs, hd, 'nmarl_lstm_step_x[pv]')
+        _step_x(h, bias, zadd1, zadd2, c, done, gates, c_out, h_out, xs, hd, 'nmarl_lstm_step_x[pv]', precision)
     else:
+        _fp32_only(precision, 'lstm_step_policy_value')
         if gates is not None:
             raise _lib.NmarlError('lstm_step_policy_value: gates output needs the x-side mode')
         _fused_head(h, wh, bias, zadd1, zadd2, c, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[pv]')

@@ -291,6 +291,9 @@ class BatchedTrainer:
                  use_graph=True, rank=0, world_size=1, save_activations=True, compact_obs=True, fused_encode=True,
                  capture_update=True, rearm_after=200, keep_graphs=False):
         self.env, self.model = env, model
+        if rank == 0:
+            prec = getattr(getattr(model, 'policy', None), 'precision', 'fp32')
+            logging.info('Training: LSTM rollout products in %s%s' % (prec, '' if prec == 'fp32' else ' (opt-in; the update stays fp32)'))
         # keep_graphs: the captured hipGraph_t objects stay inspectable (torch.cuda.CUDAGraph.raw_cuda_graph; tools/graph_nodes.py)
         self.keep_graphs = bool(keep_graphs) or os.environ.get('NMARL_KEEP_GRAPHS', '0') == '1'
         # uncoupled nets: the rollout's policy steps double as the forward pass of the update (models.py)

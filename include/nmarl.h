@@ -387,6 +387,25 @@ int nmarl_lstm_step_x(int64_t E, int32_t N, int32_t H, int32_t KX, const float* 
                       float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
                       void* stream);
 /*
+ * bf16x3 (opt-in reduced precision; the fp32 entry points above are unchanged): the main product [x | h (1-done)] @ [Wx; Wh]
+ * and the value re-step's h' @ Wh as hi_a hi_b + hi_a lo_b + lo_a hi_b on the bf16 matrix cores, with a = hi + lo,
+ * hi = bf16_rne(a), lo = bf16_rne(a - hi), fp32 accumulation (~3 * 2^-18 |a||b| per product).  Everything else -- the
+ * in-kernel encoders, the cell, the heads, the draw, the env step -- is the fp32 twin's arithmetic.
+ * nmarl_lstm_wimage_bf16x3: the split image of [wx; wh], the same nmarl_lstm_wimage_floats(KX) 4-byte words per agent
+ * (img_sn in words), each word two bf16 (see csrc/lstm_mfma.hip for the layout).  nmarl_lstm_step_x_bf16x3 /
+ * nmarl_lstm_step_x_enc_bf16x3: the arguments of nmarl_lstm_step_x / nmarl_lstm_step_x_enc with that image; no message
+ * term (x2, zadd1 / zadd2 and every head kind are accepted as by the twin).
+ */
+int nmarl_lstm_wimage_bf16x3(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
+                             float* img, int64_t img_sn, void* stream);
+int nmarl_lstm_step_x_bf16x3(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
+                             int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
+                             const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
+                             int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
+                             const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
+                             float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
+                             void* stream);
+/*
  * nmarl_lstm_step_x for the policy / value step of a COUPLED net, its message term computed inside the kernel from the
  * neighbours' previous, un-masked h (quirk Q3; h_in of the other agents, agent stride h_sn) instead of by separate
  * gather / GEMM / bias-activation launches:
@@ -496,6 +515,10 @@ int nmarl_lstm_step_x_enc(int64_t E, int32_t N, int32_t H, int32_t KX, const flo
                           int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev, int64_t c_prev_sn,
                           const float* done, float* gates, int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
                           int64_t h_new_sn, const nmarl_head_t* head, const nmarl_step_enc_t* enc, void* stream);
+int nmarl_lstm_step_x_enc_bf16x3(int64_t E, int32_t N, int32_t H, int32_t KX, const float* h_in, int64_t h_sn, const float* img,
+                                 int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev, int64_t c_prev_sn,
+                                 const float* done, float* gates, int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
+                                 int64_t h_new_sn, const nmarl_head_t* head, const nmarl_step_enc_t* enc, void* stream);
 int nmarl_lstm_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t w_sn, float* img, int64_t img_sn, void* stream);
 int nmarl_lstm_step_sync_words(int64_t E, int32_t N);
 int nmarl_lstm_step_x_msg(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
