@@ -30,7 +30,7 @@ if _build.built_hash() != _build.source_hash():
 LIB_PATH = os.environ.get('NMARL_LIB_AB') or LIB_PATH
 lib = C.CDLL(LIB_PATH)
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 class CaccParams(C.Structure):
@@ -179,10 +179,6 @@ SIGNATURES = {
     'nmarl_nbr_mean_bwd_add': [_i64, _i32, _i32, _i32, _p, _p, _p, _p, _p],
     'nmarl_nbr_onehot': [_i64, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
     'nmarl_lstm_cell_fwd': [_i64, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p],
-    'nmarl_lstm_step_fused': [_i64, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p,
-                              _i64, _p, _i64, _p],
-    'nmarl_lstm_step_fused_head': [_i64, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64,
-                                   _p, _i64, _p, _i64, C.POINTER(Head), _p],
     'nmarl_lstm_wimage_floats': [_i32],
     'nmarl_lstm_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_step_x': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,

@@ -632,7 +632,7 @@ class BatchedPolicy:
         head step (policy / value), whose kernel can compute the message term itself (`_msg`)."""
         if self.xside:
             return None, None, (enc, self.params[self.k_wx], self._step_img)
-        return enc, None, None
+        return enc, None, self._wh_xs()
 
     # -- x-side product inside the fused step (uncoupled nets: the LSTM input is the encoders' output itself)
     k_wx = None
@@ -656,14 +656,22 @@ class BatchedPolicy:
         return self.k_wx is not None and ops.xside_supported(self.params[self.k_wx].shape[1], self.n_h)
 
     def refresh_wimage(self):
-        """Rebuild the chunked [Wx; Wh] image the x-side step reads; call after every change of the weights (the
-        batched engine does it at the first lock-step of a batch and before the update's forward pass)."""
+        """Rebuild the chunked [Wx; Wh] image the step kernel reads (H = 64 nets without the x-side mode: the image of Wh
+        alone, KX = 0); call after every change of the weights (the batched engine does it at the first lock-step of a
+        batch and before the update's forward pass)."""
         if self.xside:
             self._img = ops.lstm_wimage(self.params[self.k_wx], self.params[self.k_wh], out=self._img)
             if self.precision == 'bf16x3':
                 self._img_x3 = ops.lstm_wimage(self.params[self.k_wx], self.params[self.k_wh], out=self._img_x3, precision='bf16x3')
             if self.msg_kind and ops.msg_supported(self.msg_kind, self.m_max, self.n_h):
                 self._msg_img = ops.lstm_msg_wimage(self.params['w_msg'], out=self._msg_img)
+        elif self.n_h == ops.FUSED_H:
+            self._img = ops.lstm_wimage(None, self.params[self.k_wh], out=self._img)
+
+    def _wh_xs(self):
+        """xs of the step kernel's KX = 0 form (H = 64 without the x-side mode: the whole x-side part comes as addends),
+        None for other widths (batched GEMM + cell)."""
+        return (None, None, self._img) if self.n_h == ops.FUSED_H else None
 
     msg_kind = 0            # ops.MSG_*: the message term the step kernel can compute itself (coupled nets)
     msg_inplace_ok = False  # the in-kernel message term reads no h of other agents (lstm_dial: the senders' message vectors)
@@ -916,7 +924,7 @@ class NCMultiAgentPolicy(BatchedPolicy):
             self._fc_infer(m, 'w_msg', 'w_msg_b', ops.BIAS_RELU, out=enc[:, :, 2 * H:])
             return None, None, (enc, p['wx_hid'], self._img)
         hm = self._fc_infer(m, 'w_msg', 'w_msg_b', ops.BIAS_RELU)
-        return torch.bmm(hm, p['wx_hid'][:, 2 * H:]), enc, None
+        return torch.bmm(hm, p['wx_hid'][:, 2 * H:]), enc, self._wh_xs()
 
     def _seq_args(self):
         p = self.params
@@ -998,7 +1006,7 @@ class IC3MultiAgentPolicy(BatchedPolicy):
             self._fc_infer(ops.nbr_mean(h, self.nbr_idx), 'w_msg', 'w_msg_b', ops.BIAS_NONE, out=x).add_(enc)
             return None, None, (x, p['wx_hid'], self._img)
         s = self._fc_infer(ops.nbr_mean(h, self.nbr_idx), 'w_msg', 'w_msg_b', ops.BIAS_NONE).add_(enc)
-        return torch.bmm(s, p['wx_hid']), None, None
+        return torch.bmm(s, p['wx_hid']), None, self._wh_xs()
 
     def _seq_args(self):
         p = self.params
@@ -1200,7 +1208,7 @@ class DIALMultiAgentPolicy(BatchedPolicy):
             x = self._x_target(h, second, save)
             torch.add(hm, enc, out=x)
             return None, None, (x, p['wx_hid'], self._img)
-        return torch.bmm(hm.add_(enc), p['wx_hid']), None, None
+        return torch.bmm(hm.add_(enc), p['wx_hid']), None, self._wh_xs()
 
     def _seq_args(self):
         p = self.params

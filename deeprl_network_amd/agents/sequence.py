@@ -44,6 +44,7 @@ class CoupledSequence(torch.autograd.Function):
         S = torch.empty(N, T, E, H, dtype=F32, device=dev) if kind == 'dial' else None    # dial: enc + hm
         masked = set(range(T)) if masked_steps is None else set(masked_steps)
         fused = H == ops.FUSED_H
+        xs = (None, None, ops.lstm_wimage(None, wh)) if fused else None      # (KX = 0: wh alone, the x-side part as addends)
         keep = 1.0 - done
         for t in range(T):
             hp = Hall[:, t].contiguous()
@@ -61,7 +62,7 @@ class CoupledSequence(torch.autograd.Function):
                 torch.add(A1[:, t], enc[:, t], out=S[:, t])
                 z1, z2 = torch.bmm(S[:, t], wx), None
             if fused:
-                ops.lstm_step_fused(Hall[:, t], wh, b, z1, z2, Call[:, t], done[t], G[:, t], Call[:, t + 1], Hall[:, t + 1])
+                ops.lstm_step_fused(Hall[:, t], wh, b, z1, z2, Call[:, t], done[t], G[:, t], Call[:, t + 1], Hall[:, t + 1], xs=xs)
             else:
                 hk = hp * keep[t].view(1, E, 1) if t in masked else hp
                 z = torch.bmm(hk, wh) if z2 is None else torch.baddbmm(z2, hk, wh)

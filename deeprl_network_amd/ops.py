@@ -197,7 +197,7 @@ def cell_fwd(z, bias, c_prev, done, gates, c_new, h_new, z2=None):
                                   *_pn(gates), *_pn(c_new), *_pn(h_new), stream()), 'nmarl_lstm_cell_fwd')
 
 
-FUSED_H = 64      # nmarl_lstm_step_fused is specialised for 64-unit cells (256 gate columns per MFMA strip)
+FUSED_H = 64      # nmarl_lstm_step_x is specialised for 64-unit cells (256 gate columns per MFMA strip)
 
 
 XSIDE_MAX_K = 256      # widest x-side input of nmarl_lstm_step_x (multiples of 32)
@@ -524,45 +524,24 @@ def step_handoff_supported(N, E, device, K=128):
     return N * ((E + 127) // 128) <= cap
 
 
-def _fp32_only(precision, what):
-    if check_precision(precision, what) != 'fp32':
-        raise _lib.NmarlError('%s: bf16x3 needs the x-side mode (xs with the split image); this path is fp32-only' % what)
+def _xs_or_image(xs, wh):
+    """xs as given, or the compatibility form for callers that pass wh alone: KX = 0 (no x-side input, any x-side
+    pre-activation comes as zadd1 / zadd2) with the image of wh built on THIS call -- one extra launch per step.  In-repo
+    paths build the image once per weight change and pass xs = (None, None, image) themselves."""
+    return xs if xs is not None else (None, None, lstm_wimage(None, wh))
 
 
 def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=None, precision='fp32'):
-    """(gates, c', h') = cell(zadd1 (+ zadd2) + (h*(1-done)) @ wh + bias, c_prev, done) in ONE MFMA kernel
+    """(gates, c', h') = cell([x | h*(1-done)] @ [wx; wh] (+ zadd1) (+ zadd2) + bias, c_prev, done) in ONE MFMA kernel
     (H = 64).  All operands [N,E,*] panels (strided slots allowed); h_out / c_out may alias h / c_prev.
-    xs = (x, wx, image): the x-side product x @ wx is computed inside as well (K = KX + 64, image from lstm_wimage;
-    zadd1 / zadd2 may then be None).  precision: see _step_x ('bf16x3' with xs only)."""
-    N, E, H = h.shape
-    if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, None, 'nmarl_lstm_step_x', precision)
-        return h_out, c_out
-    _fp32_only(precision, 'lstm_step_fused')
-    if wh.stride(2) != 1 or wh.stride(1) != 4 * H:
-        raise _lib.NmarlError('lstm_step_fused: wh must be [N,H,4H] with contiguous [H,4H] panels')
-    check(lib.nmarl_lstm_step_fused(E, N, H, *_pn(h), ptr(wh, F32, strided=True), wh.stride(0), *_bias(bias),
-                                    *_pn(zadd1), *_pn(zadd2), *_pn(c_prev), ptr(done, F32), *_pn(gates),
-                                    *_pn(c_out), *_pn(h_out), stream()), 'nmarl_lstm_step_fused')
+    xs = (x, wx, image), image from lstm_wimage: the x-side product x @ wx is computed inside (K = KX + 64); x = None is
+    KX = 0, the recurrent product alone.  xs = None: KX = 0 with the image of wh built per call (see _xs_or_image).
+    precision: see _step_x ('bf16x3' needs its split image)."""
+    _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, _xs_or_image(xs, wh), None, 'nmarl_lstm_step_x', precision)
     return h_out, c_out
 
 
 HEAD_MAX_A = 8      # widest action set the fused head epilogue supports (csrc/lstm_mfma.hip: MAXA)
-
-
-def _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, head, what, xs=None, gates=None, precision='fp32'):
-    N, E, H = h.shape
-    if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, what, precision)
-        return
-    _fp32_only(precision, what)
-    if gates is not None:
-        raise _lib.NmarlError('%s: gates output needs the x-side mode' % what)
-    if wh.stride(2) != 1 or wh.stride(1) != 4 * H:
-        raise _lib.NmarlError('%s: wh must be [N,H,4H] with contiguous [H,4H] panels' % what)
-    check(lib.nmarl_lstm_step_fused_head(E, N, H, *_pn(h), ptr(wh, F32, strided=True), wh.stride(0), *_bias(bias),
-                                         *_pn(zadd1), *_pn(zadd2), *_pn(c_prev), ptr(done, F32), None, 0,
-                                         *_pn(c_out), *_pn(h_out), C.byref(head), stream()), what)
 
 
 def _head_param(w, what):
@@ -576,7 +555,6 @@ def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w
                      u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, gates=None, precision='fp32'):
     """forward('p') of one lock-step in ONE kernel: the fused step (lstm_step_fused), then in its epilogue
     pi = softmax(h' @ pi_w + pi_b) -> pi_out [N,E,A] and the action draw of sample_actions -> act_out [E,N]."""
-    N, E, H = h.shape
     A = pi_w.shape[2]
     hd = _lib.Head()
     hd.kind, hd.A, hd.mode = 1, A, mode
@@ -585,7 +563,7 @@ def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w
     hd.pi_out, hd.pi_sn = _pn(pi_out)
     hd.act_out, hd.u = ptr(act_out, torch.uint8), ptr(u, F32)
     hd.seed, hd.env_id_base, hd.step, hd.step_dev = seed, env_id_base, int(step), ptr(step_dev, torch.int64)
-    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[p]', xs, gates, precision)
+    _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, _xs_or_image(xs, wh), hd, 'nmarl_lstm_step_x[p]', precision)
     return pi_out, act_out
 
 
@@ -604,7 +582,7 @@ def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, 
     if v_out.dim() != 2 or v_out.stride(1) != 1:
         raise _lib.NmarlError('lstm_step_value: v_out must be [N,E] with unit column stride')
     hd.v_out, hd.v_sn = ptr(v_out, F32, strided=True), v_out.stride(0)
-    _fused_head(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[v]', xs, precision=precision)
+    _step_x(h, bias, zadd1, zadd2, c_prev, done, None, c_out, h_out, _xs_or_image(xs, wh), hd, 'nmarl_lstm_step_x[v]', precision)
     return v_out
 
 
@@ -618,7 +596,7 @@ def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_ou
     with msg['sync'], see step_handoff_supported): the re-step's message term comes from the neighbours' NEW h, handed over
     between the blocks inside the launch; h_out must not alias h.  The state (h, c) [N,E,64] is advanced
     by the policy step only -- in place, or into (h_out, c_out) (slots of the update's sequence buffers); `gates`
-    [N,E,4H] receives the policy step's gates (x-side mode only).  v_out [N,E] with unit column stride."""
+    [N,E,4H] receives the policy step's gates.  v_out [N,E] with unit column stride."""
     N, E, H = h.shape
     hd = _lib.Head()
     hd.kind, hd.A, hd.mode = 3, pi_w.shape[2], mode
@@ -633,13 +611,7 @@ def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_ou
         raise _lib.NmarlError('lstm_step_policy_value: v_out must be [N,E] with unit column stride')
     hd.v_out, hd.v_sn = ptr(v_out, F32, strided=True), v_out.stride(0)
     h_out, c_out = (h if h_out is None else h_out), (c if c_out is None else c_out)
-    if xs is not None:
-        _step_x(h, bias, zadd1, zadd2, c, done, gates, c_out, h_out, xs, hd, 'nmarl_lstm_step_x[pv]', precision)
-    else:
-        _fp32_only(precision, 'lstm_step_policy_value')
-        if gates is not None:
-            raise _lib.NmarlError('lstm_step_policy_value: gates output needs the x-side mode')
-        _fused_head(h, wh, bias, zadd1, zadd2, c, done, c_out, h_out, hd, 'nmarl_lstm_step_fused_head[pv]')
+    _step_x(h, bias, zadd1, zadd2, c, done, gates, c_out, h_out, _xs_or_image(xs, wh), hd, 'nmarl_lstm_step_x[pv]', precision)
     if not defer_action_term:
         if not v_out.is_contiguous():
             raise _lib.NmarlError('lstm_step_policy_value: the neighbour-action add needs a contiguous v_out')
@@ -1418,10 +1390,11 @@ class _LstmSequence(torch.autograd.Function):
         keep = (1.0 - done)                                                   # [T,E]
         masked = set(range(T)) if masked_steps is None else set(masked_steps)
         fused = H == FUSED_H and wh.stride(2) == 1 and wh.stride(1) == H4
+        xs = (None, None, lstm_wimage(None, wh)) if fused else None          # (KX = 0: wh alone)
         for t in range(T):
             if fused:     # recurrent GEMM + cell in one MFMA kernel, pre-activation never leaves the CU
                 lstm_step_fused(Hall[:, t], wh, b, pre[:, t], None, Call[:, t], done[t], G[:, t], Call[:, t + 1],
-                                Hall[:, t + 1])
+                                Hall[:, t + 1], xs=xs)
                 continue
             hk = Hall[:, t] * keep[t].view(1, E, 1) if t in masked else Hall[:, t]
             # recurrent product as a plain GEMM; the x-side pre-activation enters the cell kernel as 2nd addend

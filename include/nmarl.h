@@ -308,23 +308,24 @@ int nmarl_lstm_cell_bwd(int64_t E, int32_t N, int32_t H, const float* gates, int
                         int64_t dh2_sn, const float* dc_new, int64_t dc_sn, float* dz, int64_t dz_sn,
                         float* dc_prev, int64_t dc_prev_sn, void* stream);
 /*
- * Fused recurrent GEMM + cell on the gfx950 matrix cores (v_mfma_f32_16x16x4_f32), H = 64 only:
- *   z = zadd1 (+ zadd2) + (h_in * (1-done)) @ wh ;  (gates, c_new, h_new) = cell(z + bias, c_prev, done)
- * Same maths as a batched GEMM followed by nmarl_lstm_cell_fwd, but the [rows,4H] pre-activation never
- * reaches HBM.  h_in [N,E,H], wh [N,H,4H], bias [N,4H], zadd1/zadd2 [N,E,4H] (zadd2 may be NULL: the
- * x-side product s*Wx, and for NeurComm additionally the message term), c_prev/c_new/h_new [N,E,H],
- * gates [N,E,4H] or NULL; agent strides `*_sn` in floats (multiples of 4); h_new may alias h_in and c_new
- * may alias c_prev.  Returns NMARL_EINVAL for H != 64 (callers then use GEMM + nmarl_lstm_cell_fwd).
- */
-int nmarl_lstm_step_fused(int64_t E, int32_t N, int32_t H, const float* h_in, int64_t h_sn,
-                          const float* wh, int64_t wh_sn, const float* bias, int64_t bias_sn,
-                          const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                          const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                          int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
-                          int64_t h_new_sn, void* stream);
-/*
- * The fused step with an actor or critic head in its epilogue (H = 64, A <= 8): what
- * Trainer._get_policy / _get_value (utils.py:129-149) need from one lock-step, with h' still on chip.
+ * The fused LSTM step on the gfx950 matrix cores (v_mfma_f32_16x16x4_f32), H = 64 only: the WHOLE pre-activation of
+ * agents/utils.py:102-113 (lstm), 199-208 (lstm_comm), 401-408 (lstm_ic3),
+ *   z = [x | h_in * (1-done)] @ [wx; wh] + bias (+ zadd1) (+ zadd2),   x [N,E,KX], KX in {0, 32, ..., 256},
+ *   (gates, c_new, h_new) = cell(z, c_prev, done)
+ * Same maths as batched GEMMs followed by nmarl_lstm_cell_fwd, but the [rows,4H] pre-activation never reaches HBM.
+ * x: the LSTM input of one lock-step -- fc output (KX = n_fc), the [fcs | fcp] concatenation of policies.py:176-181
+ * (KX = 2 n_fc), lstm_comm's [hx | hp | hm] (KX = 3 H), lstm_ic3's s (KX = H) -- with agent stride x_sn and row pitch
+ * x_row >= KX (floats, multiples of 4; a column block of a wider buffer is read in place).  KX = 0: no x, the recurrent
+ * product alone; the x-side pre-activation, if any, then arrives as zadd1 / zadd2 [N,E,4H] (either may be NULL).
+ * KX2 > 0: the LAST KX2 columns of x come from a second tensor x2 [N,E,KX2] (x then holds the first KX - KX2): the
+ * value re-step of a coupled net re-uses the observation / fingerprint encodings and swaps in the re-computed message.
+ * h_in / c_prev / c_new / h_new [N,E,H], bias [N,4H], gates [N,E,4H] or NULL; agent strides `*_sn` in floats (multiples
+ * of 4), these pointers and the image 16-byte aligned; h_new may alias h_in and c_new may alias c_prev.
+ * The weights come as the chunked image nmarl_lstm_wimage builds from wx [N,KX,4H] (NULL for KX = 0) and wh [N,H,4H]
+ * (agent strides in floats): per agent nmarl_lstm_wimage_floats(KX) = (KX+64)*320 floats, image[k][c][t] = W[k][16t+c]
+ * for t < 16, 4 floats of padding per (k,c); rebuild it whenever the weights change (once per update).
+ * head (NULL or kind 0: none) puts an actor or critic head in the epilogue (A <= 8): what Trainer._get_policy /
+ * _get_value (utils.py:129-149) need from one lock-step, with h' still on chip.
  *   kind 1 (forward 'p', policies.py:50-57 + utils.py:135-141):
  *       pi = softmax(h' @ w + b), w [N,H,A], b [N,A]  -> pi_out [N,E,A] (the next fingerprint slot),
  *       action = nmarl_sample_actions' draw from pi (same modes / Philox counters) -> act_out [E,Ntot] u8
@@ -333,12 +334,12 @@ int nmarl_lstm_step_fused(int64_t E, int32_t N, int32_t H, const float* h_in, in
  *       of absent neighbours unused), b [N,1]; neighbour actions are read from act_in [E,Ntot] u8 through
  *       nbr_idx [N,m_max] (-1 padded, as in nmarl_nbr_onehot)  -> v_out [N,E]
  *   kind 3 (forward 'p' AND forward 'v' of one lock-step, quirk Q1, for nets whose recurrence has no cross-agent
- *       term): kind 1, then the value re-step from the state just produced -- z = the same addend + (h'(1-done)) @ wh,
- *       cell from c'(1-done) -- and v_h = h'' @ w2[:H] + b2 -> v_out [N,E]; h'' / c'' are not stored (the reference
- *       discards them, policies.py:124-133).  The critic's neighbour-action term needs the other agents' draws of
- *       this lock-step: add it with nmarl_nbr_action_value_fwd(accumulate = 1).
- * Agent strides in floats; `u` as in nmarl_sample_actions (mode 0).  A NULL head or kind 0 is
- * nmarl_lstm_step_fused.  NMARL_EINVAL for A > 8 (callers compose GEMM + softmax + nmarl_sample_actions).
+ *       term): kind 1, then the value re-step from the state just produced -- z = the same x-side part and addends
+ *       + (h'(1-done)) @ wh, cell from c'(1-done) -- and v_h = h'' @ w2[:H] + b2 -> v_out [N,E]; h'' / c'' are not
+ *       stored (the reference discards them, policies.py:124-133).  The critic's neighbour-action term needs the other
+ *       agents' draws of this lock-step: add it with nmarl_nbr_action_value_fwd(accumulate = 1).
+ * Agent strides in floats; `u` as in nmarl_sample_actions (mode 0).  NMARL_EINVAL for A > 8 (callers compose GEMM +
+ * softmax + nmarl_sample_actions).
  */
 typedef struct nmarl_head {
     int32_t kind, A, mode, m_max;
@@ -356,26 +357,6 @@ typedef struct nmarl_head {
     const float* w2; int64_t w2_sn;      /* kind 3: the critic's weights / bias (w, b are the actor's) */
     const float* b2; int64_t b2_sn;
 } nmarl_head_t;
-int nmarl_lstm_step_fused_head(int64_t E, int32_t N, int32_t H, const float* h_in, int64_t h_sn,
-                               const float* wh, int64_t wh_sn, const float* bias, int64_t bias_sn,
-                               const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                               const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                               int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
-                               int64_t h_new_sn, const nmarl_head_t* head, void* stream);
-/*
- * The fused step with the x-side product inside: the WHOLE pre-activation of agents/utils.py:102-113 (lstm),
- * 199-208 (lstm_comm), 401-408 (lstm_ic3) on the matrix cores,
- *   z = [x | h_in * (1-done)] @ [wx; wh] + bias (+ zadd1) (+ zadd2),   x [N,E,KX], KX in {0, 32, ..., 256},
- * then cell + optional head exactly as nmarl_lstm_step_fused_head (head NULL / kind 0: none; gates may be requested).
- * x: the LSTM input of one lock-step -- fc output (KX = n_fc), the [fcs | fcp] concatenation of policies.py:176-181
- * (KX = 2 n_fc), lstm_comm's [hx | hp | hm] (KX = 3 H), lstm_ic3's s (KX = H) -- with agent stride x_sn and row pitch
- * x_row >= KX (floats, multiples of 4; a column block of a wider buffer is read in place).  zadd1 / zadd2 may be NULL.
- * KX2 > 0: the LAST KX2 columns of x come from a second tensor x2 [N,E,KX2] (x then holds the first KX - KX2): the
- * value re-step of a coupled net re-uses the observation / fingerprint encodings and swaps in the re-computed message.
- * The weights come as the chunked image nmarl_lstm_wimage builds from wx [N,KX,4H] and wh [N,H,4H] (agent strides in
- * floats): per agent nmarl_lstm_wimage_floats(KX) = (KX+64)*320 floats, image[k][c][t] = W[k][16t+c] for t < 16, 4
- * floats of padding per (k,c); rebuild it whenever the weights change (once per update).  H = 64 only.
- */
 int nmarl_lstm_wimage_floats(int32_t KX);
 int nmarl_lstm_wimage(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
                       float* img, int64_t img_sn, void* stream);

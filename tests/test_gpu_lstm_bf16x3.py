@@ -178,7 +178,7 @@ def test_bf16x3_refuses_the_message_term_and_fp32_only_paths():
         ops.lstm_step_fused(hg, None, cu(d['b']), None, None, cg, cu(d['done']), None, cg, hg, xs=(cu(d['x']), None, img), precision='bf16x3')
     with pytest.raises(_lib.NmarlError):
         ops.lstm_step_fused(hg, None, cu(d['b']), None, None, cg, cu(d['done']), None, cg, hg, xs=(cu(d['x']), None, img3))
-    with pytest.raises(_lib.NmarlError):           # no x-side image: the h-only kernel is fp32-only
+    with pytest.raises(_lib.NmarlError):           # no image given: the KX = 0 compatibility form builds an fp32 one
         ops.lstm_step_fused(hg, cu(d['wh']), cu(d['b']), cu(torch.zeros(N, E, 4 * H)), None, cg, cu(d['done']), None, cg, hg, precision='bf16x3')
     # HEAD 0 (no heads) under bf16x3 runs and is close to fp32
     h0, c0 = cu(d['h']), cu(d['c'])

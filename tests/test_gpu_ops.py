@@ -132,7 +132,7 @@ def test_bias_act_and_cell_second_addend():
 @pytest.mark.parametrize('two_addends', [False, True])
 def test_lstm_step_fused_mfma(N, E, two_addends):
     """MFMA GEMM + cell in one kernel == (h*(1-done)) @ Wh + addends -> cell, incl. ragged row counts, strided
-    sequence slots, gates output and in-place state update."""
+    sequence slots, gates output and in-place state update (wh without xs: the KX = 0 form of the x-side step)."""
     from deeprl_network_amd import ops
     from oracle import ops_ref
     H = 64
@@ -178,7 +178,7 @@ def test_lstm_step_fused_mfma(N, E, two_addends):
 def test_lstm_step_fused_heads(N, E, A, m_max, two_addends, mode):
     """The actor / critic epilogues of the fused step (forward 'p' + draw, forward 'v') == step, then
     softmax(h' W + b) + sample_actions, resp. [h', onehot(nbr actions)] W + b, incl. ragged rows, in-place
-    state, parameters living in a wider flat row, -1 padded neighbour tables and all draw modes."""
+    state, parameters living in a wider flat row, -1 padded neighbour tables and all draw modes (the KX = 0 form)."""
     from deeprl_network_amd import ops
     from oracle import ops_ref
     H = 64
@@ -636,7 +636,7 @@ def _xside_case(N, E, KX, A, m_max, seed, addends):
 
 
 @pytest.mark.parametrize('N,E', [(8, 4096), (8, 1), (25, 130), (3, 127), (8, 257)])
-@pytest.mark.parametrize('KX,addends', [(128, 0), (64, 0), (192, 1), (0, 1), (32, 2), (256, 0)])
+@pytest.mark.parametrize('KX,addends', [(128, 0), (64, 0), (192, 1), (0, 1), (0, 2), (32, 2), (256, 0)])
 def test_lstm_step_x_whole_preactivation_on_mfma(N, E, KX, addends):
     """nmarl_lstm_step_x: z = [x | h keep] @ [Wx; Wh] + b (+ addends) -> cell, vs the float64 restatement
     (agents/utils.py:102-113): every supported input width, ragged row counts, x as a column block of a wider buffer,
@@ -675,7 +675,7 @@ def test_lstm_step_x_whole_preactivation_on_mfma(N, E, KX, addends):
 
 
 @pytest.mark.parametrize('N,E,A,m_max', [(8, 4096, 4, 2), (25, 130, 5, 4), (3, 127, 8, 2), (8, 1, 4, 2)])
-@pytest.mark.parametrize('KX,addends', [(128, 0), (64, 1), (192, 0)])
+@pytest.mark.parametrize('KX,addends', [(128, 0), (64, 1), (192, 0), (0, 2)])
 @pytest.mark.parametrize('mode', [1, 2])
 def test_lstm_step_x_heads(N, E, A, m_max, KX, addends, mode):
     """The head epilogues on top of the x-side step: forward('p') + draw (kind 1), forward('v') (kind 2) and both in

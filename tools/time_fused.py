@@ -1,5 +1,6 @@
 """Time the fused LSTM step kernels at the bench shape (N = 8, E = 4096, H = 64):
-  * recurrent-only step (nmarl_lstm_step_fused: addend from a separate s @ Wx library GEMM, timed beside it),
+  * the KX = 0 form of the step (nmarl_lstm_step_x on the image of Wh alone: addend from a separate s @ Wx library GEMM,
+    timed beside it),
   * the x-side step (nmarl_lstm_step_x: K = KX + 64 inside), plain / with gates / with the policy+value heads (kind 3).
     python tools/time_fused.py [E] [KX]
 """
@@ -26,6 +27,7 @@ co, ho = torch.empty_like(c), torch.empty_like(h)
 gates = torch.empty(N, E, 4 * H, device='cuda')
 pi, act, v = torch.empty(N, E, A, device='cuda'), torch.zeros(E, N, dtype=torch.uint8, device='cuda'), torch.empty(N, E, device='cuda')
 img = ops.lstm_wimage(wx, wh)
+xs0 = (None, None, ops.lstm_wimage(None, wh))
 zbuf = torch.empty(N, E, 4 * H, device='cuda')
 
 
@@ -57,9 +59,9 @@ def timed(name, f, n=20, reps=10):
 flops_x = 2.0 * N * E * (KX + H) * 4 * H
 print('N=%d E=%d KX=%d: x-side step = %.2f GFLOP -> %.1f us at the 157.3 TFLOP/s fp32 matrix peak' % (N, E, KX, flops_x / 1e9, flops_x / 157.3e6))
 timed('library GEMM s @ Wx', lambda: torch.bmm(x, wx, out=zbuf))
-timed('recurrent-only step (addend given)', lambda: ops.lstm_step_fused(h, wh, b, z1, None, c, done, None, co, ho))
-timed('recurrent-only step + gates', lambda: ops.lstm_step_fused(h, wh, b, z1, None, c, done, gates, co, ho))
-timed('recurrent-only policy+value (kind 3)', lambda: ops.lstm_step_policy_value(h, wh, b, z1, None, c, done, pi_w, pi_b, pi, act, v_w, v_b, nbr, A, v, mode=2))
+timed('KX = 0 step (addend given)', lambda: ops.lstm_step_fused(h, None, b, z1, None, c, done, None, co, ho, xs=xs0))
+timed('KX = 0 step + gates', lambda: ops.lstm_step_fused(h, None, b, z1, None, c, done, gates, co, ho, xs=xs0))
+timed('KX = 0 policy+value (kind 3)', lambda: ops.lstm_step_policy_value(h, None, b, z1, None, c, done, pi_w, pi_b, pi, act, v_w, v_b, nbr, A, v, mode=2, xs=xs0))
 u = timed('x-side step', lambda: ops.lstm_step_fused(h, None, b, None, None, c, done, None, co, ho, xs=(x, None, img)))
 print('    -> %.1f TFLOP/s = %.2f of the fp32 matrix peak' % (flops_x / u / 1e6, flops_x / u / 157.3e6))
 timed('x-side step + gates', lambda: ops.lstm_step_fused(h, None, b, None, None, c, done, gates, co, ho, xs=(x, None, img)))
