@@ -30,7 +30,7 @@ if _build.built_hash() != _build.source_hash():
 LIB_PATH = os.environ.get('NMARL_LIB_AB') or LIB_PATH
 lib = C.CDLL(LIB_PATH)
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 
 class CaccParams(C.Structure):
@@ -151,6 +151,18 @@ class GridEnv(C.Structure):
                  ('episode', C.c_void_p), ('words', C.c_void_p)])
 
 
+class StepX(C.Structure):
+    """nmarl_step_x_t (include/nmarl.h): arguments of nmarl_lstm_step_x, every form of the lock-step."""
+    _fields_ = ([('E', C.c_int64)] + [(k, C.c_int32) for k in ('N', 'H', 'KX', 'KX2', 'precision', 'pad_')] +
+                [('x', C.c_void_p), ('x_sn', C.c_int64), ('x_row', C.c_int64), ('x2', C.c_void_p), ('x2_sn', C.c_int64),
+                 ('x2_row', C.c_int64)] +
+                [('h_in', C.c_void_p), ('h_sn', C.c_int64)] +
+                [f for k in ('img', 'bias', 'zadd1', 'zadd2', 'c_prev') for f in ((k, C.c_void_p), (k + '_sn', C.c_int64))] +
+                [('done', C.c_void_p)] +
+                [f for k in ('gates', 'c_new', 'h_new') for f in ((k, C.c_void_p), (k + '_sn', C.c_int64))] +
+                [('head', C.POINTER(Head)), ('msg', C.POINTER(Msg)), ('enc', C.POINTER(StepEnc)), ('genv', C.POINTER(GridEnv))])
+
+
 _p = C.c_void_p
 _i64 = C.c_int64
 _i32 = C.c_int32
@@ -180,39 +192,21 @@ SIGNATURES = {
     'nmarl_nbr_onehot': [_i64, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
     'nmarl_lstm_cell_fwd': [_i64, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_wimage_floats': [_i32],
-    'nmarl_lstm_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
-    'nmarl_lstm_step_x': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p,
-                          _i64, _p, _i64, _p, _i64, C.POINTER(Head), _p],
-    'nmarl_lstm_wimage_bf16x3': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
-    'nmarl_lstm_step_x_bf16x3': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64,
-                                 _p, _p, _i64, _p, _i64, _p, _i64, C.POINTER(Head), _p],
-    'nmarl_lstm_step_x_enc_bf16x3': [_i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
-                                     C.POINTER(Head), C.POINTER(StepEnc), _p],
+    'nmarl_lstm_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _i32, _p],
+    'nmarl_lstm_step_x': [C.POINTER(StepX), _p],
     'nmarl_lstm_msg_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_step_sync_words': [_i64, _i32],
-    'nmarl_lstm_step_x_msg': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
-                              C.POINTER(Head), C.POINTER(Msg), _p],
-    'nmarl_lstm_step_x_enc': [_i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
-                              C.POINTER(Head), C.POINTER(StepEnc), _p],
-    'nmarl_lstm_step_x_msg_enc': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
-                                  C.POINTER(Head), C.POINTER(Msg), C.POINTER(StepEnc), _p],
     'nmarl_lstm_step_env_words': [_i64],
     'nmarl_lstm_step_grid_words': [_i64],
     'nmarl_lstm_step_grid_env_blocks': [_i64, _i32],
-    'nmarl_lstm_step_x_msg_grid': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64,
-                                   C.POINTER(Head), C.POINTER(Msg), C.POINTER(GridEnv), _p],
     'nmarl_lstm_bptt_wimage_floats': [_i32],
     'nmarl_lstm_bptt_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_bptt_step': [_i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p,
-                             _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _p],
-    'nmarl_lstm_bptt_step_db': [_i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p,
-                                _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p],
+                             _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p],
     'nmarl_lstm_bptt_step_parts': [_i64],
     'nmarl_lstm_bptt_seq_blocks': [_i64],
-    'nmarl_lstm_bptt_seq': [_i32, _i64, _i32, _i32, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i64,
-                            _p, _i64, _p, _i64, _p, _i64, _p],
-    'nmarl_lstm_bptt_seq_dy': [_i32, _i64, _i32, _i32, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _i64, _i64,
-                               _p, _i64, _p, _i64, _p, _i64, _p],
+    'nmarl_lstm_bptt_seq': [_i32, _i64, _i32, _i32, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i32,
+                            _p, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_bptt_msg_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_bptt_coupled_ws_words': [_i64, _i32],
     'nmarl_lstm_bptt_coupled': [C.POINTER(BpttCoupled), _p],

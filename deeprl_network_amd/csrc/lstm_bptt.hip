@@ -1162,13 +1162,13 @@ extern "C" int nmarl_lstm_bptt_wimage(int32_t N, int32_t KM, const float* wxm, i
 
 extern "C" int nmarl_lstm_bptt_step_parts(int64_t E) { return (int)((E + ROWS_B - 1) / ROWS_B * WAVES); }
 
-extern "C" int nmarl_lstm_bptt_step_db(int64_t E, int32_t N, int32_t Hh, int32_t KM, const float* gates, int64_t gates_sn,
-                                       const float* c_prev, int64_t c_prev_sn, const float* c_new, int64_t c_new_sn,
-                                       const float* done, const float* dh, int64_t dh_sn, const float* dh2, int64_t dh2_sn,
-                                       const float* dc_in, int64_t dc_sn, const float* img, int64_t img_sn, float* dz,
-                                       int64_t dz_sn, float* dc_prev, int64_t dc_prev_sn, float* dx, int64_t dx_sn,
-                                       const float* mask, int64_t mask_sn, int64_t mask_row, float* dhd, int64_t dhd_sn,
-                                       int32_t apply_keep, float* db_part, int64_t db_sn, void* stream) {
+extern "C" int nmarl_lstm_bptt_step(int64_t E, int32_t N, int32_t Hh, int32_t KM, const float* gates, int64_t gates_sn,
+                                    const float* c_prev, int64_t c_prev_sn, const float* c_new, int64_t c_new_sn,
+                                    const float* done, const float* dh, int64_t dh_sn, const float* dh2, int64_t dh2_sn,
+                                    const float* dc_in, int64_t dc_sn, const float* img, int64_t img_sn, float* dz,
+                                    int64_t dz_sn, float* dc_prev, int64_t dc_prev_sn, float* dx, int64_t dx_sn,
+                                    const float* mask, int64_t mask_sn, int64_t mask_row, float* dhd, int64_t dhd_sn,
+                                    int32_t apply_keep, float* db_part, int64_t db_sn, void* stream) {
     if (db_part && E > 0 && (db_sn < (E + ROWS_B - 1) / ROWS_B * WAVES * (int64_t)G4 || ((uintptr_t)db_part % 4))) return NMARL_EINVAL;
     if (Hh != H || E < 0 || N <= 0 || (KM != 0 && KM != H) ||
         (E > 0 && (!gates || !c_prev || !c_new || !done || !img || !dz || !dc_prev || !dhd || (KM > 0 && !dx))))
@@ -1204,27 +1204,15 @@ extern "C" int nmarl_lstm_bptt_step_db(int64_t E, int32_t N, int32_t Hh, int32_t
     return nmarl_check_launch();
 }
 
-extern "C" int nmarl_lstm_bptt_step(int64_t E, int32_t N, int32_t Hh, int32_t KM, const float* gates, int64_t gates_sn,
-                                    const float* c_prev, int64_t c_prev_sn, const float* c_new, int64_t c_new_sn,
-                                    const float* done, const float* dh, int64_t dh_sn, const float* dh2, int64_t dh2_sn,
-                                    const float* dc_in, int64_t dc_sn, const float* img, int64_t img_sn, float* dz,
-                                    int64_t dz_sn, float* dc_prev, int64_t dc_prev_sn, float* dx, int64_t dx_sn,
-                                    const float* mask, int64_t mask_sn, int64_t mask_row, float* dhd, int64_t dhd_sn,
-                                    int32_t apply_keep, void* stream) {
-    return nmarl_lstm_bptt_step_db(E, N, Hh, KM, gates, gates_sn, c_prev, c_prev_sn, c_new, c_new_sn, done, dh, dh_sn, dh2, dh2_sn, dc_in,
-                                   dc_sn, img, img_sn, dz, dz_sn, dc_prev, dc_prev_sn, dx, dx_sn, mask, mask_sn, mask_row, dhd, dhd_sn,
-                                   apply_keep, nullptr, 0, stream);
-}
-
 extern "C" int nmarl_lstm_bptt_seq_blocks(int64_t E) { return (int)((E + ROWS_B - 1) / ROWS_B); }
 
-static int launch_bptt_seq(int32_t T, int64_t E, int32_t N, int32_t Hh, const float* gates, int64_t gates_sn,
-                           int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
-                           const float* dh_ext, int64_t dh_sn, int64_t dh_st, const float* dy8, int64_t dy_sn, int64_t dy_st,
-                           const float* hw, int64_t hw_sn, int32_t O, const float* img, int64_t img_sn,
-                           float* dz, int64_t dz_sn, int64_t dz_st, float* db_part, int64_t db_sn, float* dh0,
-                           int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream) {
-    if (Hh != H || E < 0 || N <= 0 || T <= 0 || (E > 0 && (!gates || !c_all || !done || (!dh_ext && !dy8) || (dh_ext && dy8) || !img || !dz)))
+extern "C" int nmarl_lstm_bptt_seq(int32_t T, int64_t E, int32_t N, int32_t Hh, const float* gates, int64_t gates_sn,
+                                   int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
+                                   const float* dh_ext, int64_t dh_sn, int64_t dh_st, const float* dy8, int64_t dy_sn, int64_t dy_st,
+                                   const float* hw, int64_t hw_sn, int32_t O, const float* img, int64_t img_sn,
+                                   float* dz, int64_t dz_sn, int64_t dz_st, float* db_part, int64_t db_sn, float* dh0,
+                                   int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream) {
+    if (!dh_ext == !dy8 || Hh != H || E < 0 || N <= 0 || T <= 0 || (E > 0 && (!gates || !c_all || !done || !img || !dz)))
         return NMARL_EINVAL;
     if (dy8 && (!hw || O <= 0 || O > 8 || hw_sn < (int64_t)H * O || dy_st < E * 8 || (dy_st % 4) || !sn_ok(dy_sn, (T - 1) * dy_st + E * 8) ||
                 ((uintptr_t)dy8 % 16)))
@@ -1262,26 +1250,6 @@ static int launch_bptt_seq(int32_t T, int64_t E, int32_t N, int32_t Hh, const fl
         hipLaunchKernelGGL(lstm_bptt_seq_kernel<false>, dim3((unsigned)(nblk * N)), dim3(512), (size_t)SEQ_IMG * 4,
                            static_cast<hipStream_t>(stream), a);
     return nmarl_check_launch();
-}
-
-extern "C" int nmarl_lstm_bptt_seq(int32_t T, int64_t E, int32_t N, int32_t Hh, const float* gates, int64_t gates_sn,
-                                   int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
-                                   const float* dh_ext, int64_t dh_sn, int64_t dh_st, const float* img, int64_t img_sn,
-                                   float* dz, int64_t dz_sn, int64_t dz_st, float* db_part, int64_t db_sn, float* dh0,
-                                   int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream) {
-    if (!dh_ext) return NMARL_EINVAL;
-    return launch_bptt_seq(T, E, N, Hh, gates, gates_sn, gates_st, c_all, c_sn, c_st, done, dh_ext, dh_sn, dh_st, nullptr, 0, 0, nullptr, 0, 0,
-                           img, img_sn, dz, dz_sn, dz_st, db_part, db_sn, dh0, dh0_sn, dc0, dc0_sn, stream);
-}
-
-extern "C" int nmarl_lstm_bptt_seq_dy(int32_t T, int64_t E, int32_t N, int32_t Hh, const float* gates, int64_t gates_sn,
-                                      int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
-                                      const float* dy8, int64_t dy_sn, int64_t dy_st, const float* hw, int64_t hw_sn, int32_t O,
-                                      const float* img, int64_t img_sn, float* dz, int64_t dz_sn, int64_t dz_st, float* db_part,
-                                      int64_t db_sn, float* dh0, int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream) {
-    if (!dy8) return NMARL_EINVAL;
-    return launch_bptt_seq(T, E, N, Hh, gates, gates_sn, gates_st, c_all, c_sn, c_st, done, nullptr, 0, 0, dy8, dy_sn, dy_st, hw, hw_sn, O,
-                           img, img_sn, dz, dz_sn, dz_st, db_part, db_sn, dh0, dh0_sn, dc0, dc0_sn, stream);
 }
 
 extern "C" int nmarl_lstm_bptt_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t w_sn, float* img, int64_t img_sn,

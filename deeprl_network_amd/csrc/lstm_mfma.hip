@@ -368,7 +368,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, cons
 // the dropped lo_a lo_b and the two roundings leave ~3 * 2^-18 |a||b| per product).  A chunk's 32 k rows are ONE k-block:
 // lane (c, grp) holds A[row c][k = 8 grp + j] and B[k = 8 grp + j][col c], and MFMA k index 8 grp + j is chunk row 4 grp + j
 // (j < 4), 16 + 4 grp + j - 4 (j >= 4) -- exactly the rows the lane's fp32 A registers A0 / A1 already hold, so the A fragment
-// is those registers split in place; the image (nmarl_lstm_wimage_bf16x3) stores B in the same k order.
+// is those registers split in place; the image (nmarl_lstm_wimage, precision 1) stores B in the same k order.
 // Chunk image (same 40 KB as the fp32 one, so the staging ring is unchanged): lane (c, grp) owns X3_PITCH dwords at
 // (16 grp + c) X3_PITCH; tile t's hi fragment is dwords 8 t .. 8 t + 3, its lo fragment 8 t + 4 .. 8 t + 7 -- one ds_read_b128
 // each; X3_PITCH = 4 x odd keeps the 16 lanes of a group on disjoint banks.
@@ -439,7 +439,7 @@ __device__ __forceinline__ void chunk_bf16x3(f32x4 (&acc)[16], const float* buf,
 // previous launch handed on (carry_in): no neighbour rows, no product in front of the K loop.  A template parameter, not a launch
 // argument: at 256 registers a run-time choice cost every form of the kernel ~4 us (profiles/r06_ab_msg_carry.txt).
 // PREC (opt-in): 0 exact fp32 (v_mfma_f32_16x16x4_f32), 1 bf16x3 for the main K loop and the value re-step's h' @ Wh (see
-// chunk_bf16x3; img is then nmarl_lstm_wimage_bf16x3's image).  The encoder pre-phase, epilogues and heads stay fp32.
+// chunk_bf16x3; img is then nmarl_lstm_wimage's precision-1 image).  The encoder pre-phase, epilogues and heads stay fp32.
 template <int HEAD, int MSG, int ENC = 0, int CARRY = 0, int PREC = 0>
 __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1531,24 +1531,17 @@ extern "C" int nmarl_lstm_step_sync_words(int64_t E, int32_t N) {
 }
 
 extern "C" int nmarl_lstm_wimage(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
-                                 float* img, int64_t img_sn, void* stream) {
+                                 float* img, int64_t img_sn, int32_t precision, void* stream) {
     if (N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || !wh || !img || (KX > 0 && !wx) || img_sn < (int64_t)(KX + H) * 320 ||
-        (img_sn % 4) || ((uintptr_t)img % 16) || wh_sn < H * G4 || (KX > 0 && wx_sn < (int64_t)KX * G4))
+        (img_sn % 4) || ((uintptr_t)img % 16) || wh_sn < H * G4 || (KX > 0 && wx_sn < (int64_t)KX * G4) || precision < 0 || precision > 1)
         return NMARL_EINVAL;
     const int64_t total = (int64_t)N * (KX + H) * 320;
-    hipLaunchKernelGGL(lstm_wimage_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       N, KX, wx, wx_sn, wh, wh_sn, img, img_sn);
-    return nmarl_check_launch();
-}
-
-extern "C" int nmarl_lstm_wimage_bf16x3(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
-                                        float* img, int64_t img_sn, void* stream) {
-    if (N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || !wh || !img || (KX > 0 && !wx) || img_sn < (int64_t)(KX + H) * 320 ||
-        (img_sn % 4) || ((uintptr_t)img % 16) || wh_sn < H * G4 || (KX > 0 && wx_sn < (int64_t)KX * G4))
-        return NMARL_EINVAL;
-    const int64_t total = (int64_t)N * (KX + H) * 320;
-    hipLaunchKernelGGL(lstm_wimage_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       N, KX, wx, wx_sn, wh, wh_sn, reinterpret_cast<unsigned*>(img), img_sn);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (precision)
+        hipLaunchKernelGGL(lstm_wimage_bf16x3_kernel, grid, dim3(256), 0, st, N, KX, wx, wx_sn, wh, wh_sn, reinterpret_cast<unsigned*>(img), img_sn);
+    else
+        hipLaunchKernelGGL(lstm_wimage_kernel, grid, dim3(256), 0, st, N, KX, wx, wx_sn, wh, wh_sn, img, img_sn);
     return nmarl_check_launch();
 }
 
@@ -1628,18 +1621,30 @@ extern "C" int nmarl_handoff_capacity(int32_t which, int32_t K) {
 
 extern "C" int nmarl_lstm_step_grid_env_blocks(int64_t E, int32_t N);
 
-static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                         int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
-                                 const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                 int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                                 const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
-                                 float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                                 const nmarl_msg_t* msg, void* stream, const nmarl_step_enc_t* enc = nullptr,
-                                 const nmarl_grid_env_t* genv = nullptr, const int prec = 0) {
+extern "C" int nmarl_lstm_step_x(const nmarl_step_x_t* s, void* stream) {
+    if (!s) return NMARL_EINVAL;
+    const int64_t E = s->E;
+    const int32_t N = s->N, KX = s->KX, KX2 = s->KX2, prec = s->precision;
+    const float *x = s->x, *x2 = s->x2, *h_in = s->h_in, *img = s->img, *bias = s->bias, *zadd1 = s->zadd1, *zadd2 = s->zadd2,
+                *c_prev = s->c_prev, *done = s->done;
+    float *gates = s->gates, *c_new = s->c_new, *h_new = s->h_new;
+    const int64_t x_sn = s->x_sn, x_row = s->x_row, x2_sn = s->x2_sn, x2_row = s->x2_row, h_sn = s->h_sn, img_sn = s->img_sn,
+                  bias_sn = s->bias_sn, zadd1_sn = s->zadd1_sn, zadd2_sn = s->zadd2_sn, c_prev_sn = s->c_prev_sn, gates_sn = s->gates_sn,
+                  c_new_sn = s->c_new_sn, h_new_sn = s->h_new_sn;
+    const nmarl_head_t* head = s->head;
+    const nmarl_msg_t* msg = s->msg;
+    const nmarl_step_enc_t* enc = s->enc;
+    const nmarl_grid_env_t* genv = s->genv;
     const int mk = msg ? msg->kind : 0;
-    if (prec != 0 && (mk != 0 || genv)) return NMARL_EINVAL;     // bf16x3: the MSG = 0 forms only
+    const int kind = head ? head->kind : 0;
+    // which optional parts go together: a message term needs a head and takes no addends; the in-launch encoders and the grid env
+    // role need head kind 3; the encoders write x with message kind 1 and read no x without a message term; the grid role needs
+    // message kind 2; bf16x3: the MSG = 0 forms
+    if ((msg && (mk == 0 || kind == 0 || zadd1 || zadd2)) || ((enc || genv) && kind != 3) || (enc && (mk > 1 || (mk == 1) != !!x)) ||
+        (genv && mk != 2) || prec < 0 || prec > 1 || (prec && (msg || genv)))
+        return NMARL_EINVAL;
     const int KM = mk ? H : 0;                   // columns of x the message pre-phase produces
-    if (Hh != H || E < 0 || N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || KX2 < 0 || KX2 > KX || KX2 % CH_K || mk < 0 || mk > 3 ||
+    if (s->H != H || E < 0 || N <= 0 || KX < 0 || KX > MAX_KX || KX % CH_K || KX2 < 0 || KX2 > KX || KX2 % CH_K || mk < 0 || mk > 3 ||
         (mk && (KX2 != 0 || KX < H)) ||
         (E > 0 && (!h_in || !img || !bias || !c_prev || !done || !c_new || !h_new || (KX - KX2 - KM > 0 && !x && (!enc || mk)) || (KX2 > 0 && !x2))))
         return NMARL_EINVAL;
@@ -1656,7 +1661,6 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
                                         (msg->out2_row % 4) || (msg->out2_sn % 4))))))
             return NMARL_EINVAL;
     }
-    const int kind = head ? head->kind : 0;
     if (kind < 0 || kind > 3 || (mk == 3 && kind == 3)) return NMARL_EINVAL;     // lstm_dial: the two-launch lock-step only
     if (kind != 0 && E > 0) {
         if (head->A <= 0 || head->A > MAXA || !head->w || !head->b || head->b_sn < (kind == 2 ? 1 : head->A)) return NMARL_EINVAL;
@@ -1704,8 +1708,7 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
             xa.mm_out = msg->mean_out; xa.mm_sn = msg->mean_out_sn; xa.mm_row = msg->mean_out_row;
         }
         if (msg->carry_in || msg->carry_out || msg->mean_next) {
-            const int kd = head ? head->kind : 0;
-            if (kd != 3 || mk == 3 || (msg->carry_in && (msg->carry_in_sn < E * (int64_t)H || (msg->carry_in_sn % 4) || ((uintptr_t)msg->carry_in % 16))) ||
+            if (kind != 3 || mk == 3 || (msg->carry_in && (msg->carry_in_sn < E * (int64_t)H || (msg->carry_in_sn % 4) || ((uintptr_t)msg->carry_in % 16))) ||
                 (msg->carry_out && (msg->carry_out_sn < E * (int64_t)H || (msg->carry_out_sn % 4) || ((uintptr_t)msg->carry_out % 16))) ||
                 (msg->mean_next && (mk != 2 || msg->mean_next_row < H || msg->mean_next_sn < E * msg->mean_next_row || ((uintptr_t)msg->mean_next % 16) ||
                                     (msg->mean_next_row % 4) || (msg->mean_next_sn % 4))))
@@ -1716,8 +1719,7 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
         if (mk == 3) {
             xa.src = msg->src; xa.src_sn = msg->src_sn; xa.xm2_out = msg->out2; xa.xm2_sn = msg->out2_sn; xa.xm2_row = msg->out2_row;
             if (msg->next_out) {
-                const int kd = head ? head->kind : 0;
-                if (kd != 1 || !msg->next_img || !msg->next_b || msg->next_img_sn < H * 64 || (msg->next_img_sn % 4) ||
+                if (kind != 1 || !msg->next_img || !msg->next_b || msg->next_img_sn < H * 64 || (msg->next_img_sn % 4) ||
                     ((uintptr_t)msg->next_img % 16) || msg->next_b_sn < H || (msg->next_b_sn % 4) || ((uintptr_t)msg->next_b % 16) ||
                     msg->next_out_sn < E * (int64_t)H || (msg->next_out_sn % 4) || ((uintptr_t)msg->next_out % 16))
                     return NMARL_EINVAL;
@@ -1745,7 +1747,6 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
 #undef NMARL_SET_LDS
         lds_once.done(lds_bit);
     }
-    if (mk && kind == 0) return NMARL_EINVAL;                   // the message pre-phase exists for the policy / value steps
     dim3 grid(a.blocks_per_agent * N);
     if (enc) {
         // the input encoders inside the launch (ENC 1) on the CACC input layout: the uncoupled nets' policy + value step (<3,0,1>), or
@@ -1753,7 +1754,7 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
         const bool coupled = mk == 1 && kind == 3;
         const bool single = !enc->w_fp;                        // ENC 2: the observation encoder alone (IA2C; ConseNet with m_max = 0)
         const int ob_rows = 5 * (1 + enc->m_max);
-        if ((mk != 0 && !coupled) || kind != 3 || KX != (coupled ? 3 * H : single ? H : 2 * H) || KX2 != 0 || zadd1 || zadd2 || N > 32 || enc->F != 5 ||
+        if ((mk != 0 && !coupled) || KX != (coupled ? 3 * H : single ? H : 2 * H) || KX2 != 0 || zadd1 || zadd2 || N > 32 || enc->F != 5 ||
             (coupled && single) || (single ? (enc->m_max != 0 && enc->m_max != 2) : (enc->A != 4 || enc->m_max != 2)) ||
             !enc->ob || !enc->w_ob || !enc->b_ob || enc->ob_row < (int64_t)N * 5 || enc->w_ob_sn < (int64_t)ob_rows * H || enc->b_ob_sn < H ||
             (enc->b_ob_sn % 4) || ((uintptr_t)enc->b_ob % 16) ||
@@ -1814,7 +1815,6 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
             return nmarl_check_launch();
         }
     }
-    if (genv && !(mk == 2 && kind == 3)) return NMARL_EINVAL;
     if (mk && kind == 3) {
         // policy step + value re-step of a coupled net in ONE launch: the re-step's message term needs the neighbours' new h, handed
         // over between blocks inside the launch -- every block must be resident (one block per CU: 512 threads, > 80 KB LDS)
@@ -1897,50 +1897,6 @@ static int launch_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const flo
     return nmarl_check_launch();
 }
 
-extern "C" int nmarl_lstm_step_x(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                                 int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
-                                 const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                 int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                                 const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
-                                 float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                                 void* stream) {
-    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, KX2, x2, x2_sn, x2_row, h_in, h_sn, img, img_sn, bias, bias_sn, zadd1, zadd1_sn,
-                         zadd2, zadd2_sn, c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr,
-                         stream);
-}
-
-extern "C" int nmarl_lstm_step_x_bf16x3(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                                        int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
-                                        const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                        int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                                        const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
-                                        float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                                        void* stream) {
-    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, KX2, x2, x2_sn, x2_row, h_in, h_sn, img, img_sn, bias, bias_sn, zadd1, zadd1_sn,
-                         zadd2, zadd2_sn, c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr,
-                         stream, nullptr, nullptr, 1);
-}
-
-extern "C" int nmarl_lstm_step_x_msg(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                                     const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                     int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                                     int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                                     const nmarl_head_t* head, const nmarl_msg_t* msg, void* stream) {
-    if (!msg || msg->kind == 0 || !head) return NMARL_EINVAL;
-    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
-                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, msg, stream);
-}
-
-extern "C" int nmarl_lstm_step_x_msg_enc(int64_t E, int32_t N, int32_t Hh, int32_t KX, float* x, int64_t x_sn, int64_t x_row,
-                                         const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                         int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                                         int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                                         const nmarl_head_t* head, const nmarl_msg_t* msg, const nmarl_step_enc_t* enc, void* stream) {
-    if (!msg || msg->kind != 1 || !head || head->kind != 3 || !enc || !x) return NMARL_EINVAL;
-    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
-                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, msg, stream, enc);
-}
-
 // env-role blocks a grid launch gets: the compute units the LSTM blocks leave idle, at most one per group of 16 replicas
 extern "C" int nmarl_lstm_step_grid_env_blocks(int64_t E, int32_t N) {
     if (E <= 0 || N <= 0) return 0;
@@ -1953,36 +1909,7 @@ extern "C" int nmarl_lstm_step_grid_env_blocks(int64_t E, int32_t N) {
 
 extern "C" int nmarl_lstm_step_grid_words(int64_t E) { return E <= 0 ? 0 : (int)(2 * E); }
 
-extern "C" int nmarl_lstm_step_x_msg_grid(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                                          const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                                          int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                                          int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                                          const nmarl_head_t* head, const nmarl_msg_t* msg, const nmarl_grid_env_t* genv, void* stream) {
-    if (!msg || msg->kind != 2 || !head || head->kind != 3 || !genv) return NMARL_EINVAL;
-    return launch_step_x(E, N, Hh, KX, x, x_sn, x_row, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
-                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, msg, stream, nullptr, genv);
-}
-
 extern "C" int nmarl_lstm_step_env_words(int64_t E) { return E <= 0 ? 0 : (int)((E + 63) / 64 * 64); }
-
-extern "C" int nmarl_lstm_step_x_enc(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* h_in, int64_t h_sn, const float* img,
-                                     int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev, int64_t c_prev_sn,
-                                     const float* done, float* gates, int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
-                                     int64_t h_new_sn, const nmarl_head_t* head, const nmarl_step_enc_t* enc, void* stream) {
-    if (!enc || !head) return NMARL_EINVAL;
-    return launch_step_x(E, N, Hh, KX, nullptr, 0, 0, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
-                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr, stream, enc);
-}
-
-extern "C" int nmarl_lstm_step_x_enc_bf16x3(int64_t E, int32_t N, int32_t Hh, int32_t KX, const float* h_in, int64_t h_sn,
-                                            const float* img, int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev,
-                                            int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn, float* c_new,
-                                            int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                                            const nmarl_step_enc_t* enc, void* stream) {
-    if (!enc || !head) return NMARL_EINVAL;
-    return launch_step_x(E, N, Hh, KX, nullptr, 0, 0, 0, nullptr, 0, 0, h_in, h_sn, img, img_sn, bias, bias_sn, nullptr, 0, nullptr, 0,
-                         c_prev, c_prev_sn, done, gates, gates_sn, c_new, c_new_sn, h_new, h_new_sn, head, nullptr, stream, enc, nullptr, 1);
-}
 
 #ifdef NMARL_STEP_TIMELINE
 extern "C" int nmarl_timeline_set(unsigned long long* p, void* stream) {

@@ -169,7 +169,7 @@ class LargeGridBatchEnv:
 
     def inkernel_step(self, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
         """Arguments of `step` for the policy's lock-step launch to run the env step itself, on the actions it draws
-        (ops._step_x msg['genv'], nmarl_lstm_step_x_msg_grid): same state tensors, same outputs."""
+        (ops._step_x msg['genv'], nmarl_lstm_step_x with genv): same state tensors, same outputs."""
         if not self.compact_obs or self.params.objective:
             raise _lib.NmarlError('the in-launch grid env step writes the compact observation and knows the queue objective')
         if self._words is None:          # hand-off words of the launch ([E][2] u64): zeroed once, every launch leaves them zero

@@ -222,7 +222,7 @@ def check_precision(precision, what='precision'):
 def lstm_wimage(wx, wh, out=None, precision='fp32'):
     """Chunked LDS image of [wx; wh] (wx [N,KX,4H] or None, wh [N,H,4H]) for the x-mode of the fused step; rebuild it
     whenever the weights change.  -> [N, (KX+64)*320] f32; precision 'bf16x3': the split (hi, lo) image of the same bytes,
-    [N, 2*(KX+64)*320] bf16 (nmarl_lstm_wimage_bf16x3)."""
+    [N, 2*(KX+64)*320] bf16 (nmarl_lstm_wimage with precision 1)."""
     check_precision(precision, 'lstm_wimage')
     N = wh.shape[0]
     KX = 0 if wx is None else wx.shape[1]
@@ -235,9 +235,9 @@ def lstm_wimage(wx, wh, out=None, precision='fp32'):
         raise _lib.NmarlError('lstm_wimage: out must be [%d, %d] %s with rows of whole words' % (N, width, dt))
     if wh.stride(2) != 1 or wh.stride(1) != wh.shape[2] or (wx is not None and (wx.stride(2) != 1 or wx.stride(1) != wx.shape[2])):
         raise _lib.NmarlError('lstm_wimage: weights need contiguous per-agent panels')
-    fn, name = (lib.nmarl_lstm_wimage_bf16x3, 'nmarl_lstm_wimage_bf16x3') if x3 else (lib.nmarl_lstm_wimage, 'nmarl_lstm_wimage')
-    check(fn(N, KX, ptr(wx, F32, strided=True), 0 if wx is None else wx.stride(0), ptr(wh, F32, strided=True), wh.stride(0),
-             ptr(out, dt), out.stride(0) // (2 if x3 else 1), stream()), name)
+    check(lib.nmarl_lstm_wimage(N, KX, ptr(wx, F32, strided=True), 0 if wx is None else wx.stride(0), ptr(wh, F32, strided=True),
+                                wh.stride(0), ptr(out, dt), out.stride(0) // (2 if x3 else 1), 1 if x3 else 0, stream()),
+          'nmarl_lstm_wimage')
     return out
 
 
@@ -287,18 +287,31 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
     x3 = check_precision(precision, what) == 'bf16x3'
     if x3 and msg is not None:
         raise _lib.NmarlError('%s: bf16x3 exists for the uncoupled nets\' step forms only (no message term); coupled nets are fp32-only' % what)
+    a = _lib.StepX(E=E, N=N, H=H, precision=1 if x3 else 0)
+    a.h_in, a.h_sn = _pn(h)
+    a.bias, a.bias_sn = _bias(bias)
+    a.zadd1, a.zadd1_sn = _pn(zadd1)
+    a.zadd2, a.zadd2_sn = _pn(zadd2)
+    a.c_prev, a.c_prev_sn = _pn(c_prev)
+    a.done = ptr(done, F32)
+    a.gates, a.gates_sn = _pn(gates)
+    a.c_new, a.c_new_sn = _pn(c_out)
+    a.h_new, a.h_new_sn = _pn(h_out)
+    if head is not None:
+        a.head = C.pointer(head)
     if isinstance(x, dict):          # the input encoders run inside the launch (step_enc_spec): x is their description
         if head is None or head.kind != 3 or x2 is not None or msg is not None or zadd1 is not None or zadd2 is not None:
             raise _lib.NmarlError('%s: the in-kernel encoders need the policy + value step of an uncoupled net' % what)
-        KX = FC_J if x.get('w_fp') is None else 2 * FC_J          # (one encoder: IA2C / ConseNet; two: IA2C-FP)
-        fn = lib.nmarl_lstm_step_x_enc_bf16x3 if x3 else lib.nmarl_lstm_step_x_enc
-        check(fn(E, N, H, KX, *_pn(h), *_img_arg(img, N, KX, precision, what), *_bias(bias), *_pn(c_prev), ptr(done, F32),
-                 *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head), C.byref(_step_enc(x, N, E)), stream()), what)
-        return
-    xp, x_sn, x_row, K1 = (None, 0, 0, 0) if x is None else (*_rows_view(x, x.shape[2], what + ' x'), x.shape[2])
-    x2p, x2_sn, x2_row, K2 = (None, 0, 0, 0) if x2 is None else (*_rows_view(x2, x2.shape[2], what + ' x2'), x2.shape[2])
-    KX = K1 + K2 + (H if msg is not None else 0)
-    img_p, img_sn = _img_arg(img, N, KX, precision, what)
+        a.KX = FC_J if x.get('w_fp') is None else 2 * FC_J          # (one encoder: IA2C / ConseNet; two: IA2C-FP)
+        a.enc = C.pointer(_step_enc(x, N, E))
+    else:
+        K1, K2 = (0 if t is None else t.shape[2] for t in (x, x2))
+        if x is not None:
+            a.x, a.x_sn, a.x_row = _rows_view(x, K1, what + ' x')
+        if x2 is not None:
+            a.x2, a.x2_sn, a.x2_row = _rows_view(x2, K2, what + ' x2')
+        a.KX, a.KX2 = K1 + K2 + (H if msg is not None else 0), K2
+    a.img, a.img_sn = _img_arg(img, N, a.KX, precision, what)
     if msg is not None:
         if head is None or x2 is not None or zadd1 is not None or zadd2 is not None:
             raise _lib.NmarlError('%s: the in-kernel message term needs a head and excludes x2 / addends' % what)
@@ -356,10 +369,7 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
             # slot t of the saved LSTM inputs -- receives their output and is read back by the K loop
             if head.kind != 3 or msg['kind'] != MSG_GATHER_RELU or x is None:
                 raise _lib.NmarlError('%s: the in-kernel encoders of a coupled net need lstm_comm\'s policy + value step and its x slot' % what)
-            check(lib.nmarl_lstm_step_x_msg_enc(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
-                                                *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
-                                                C.byref(m), C.byref(_step_enc(dict(spec, out=None), N, E)), stream()), what)
-            return
+            a.enc = C.pointer(_step_enc(dict(spec, out=None), N, E))
         genv = msg.get('genv')
         if genv is not None:
             # lstm_ic3 on the synthetic grid: the env step as a role of this launch (LargeGridBatchEnv.inkernel_step), on the compute
@@ -376,18 +386,9 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
             if genv['words'].dtype != torch.int64 or genv['words'].numel() < lib.nmarl_lstm_step_grid_words(E):
                 raise _lib.NmarlError('%s: genv["words"] must hold nmarl_lstm_step_grid_words(E) 64-bit words' % what)
             g.words = ptr(genv['words'], torch.int64)
-            check(lib.nmarl_lstm_step_x_msg_grid(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
-                                                 *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
-                                                 C.byref(m), C.byref(g), stream()), what)
-            return
-        check(lib.nmarl_lstm_step_x_msg(E, N, H, KX, xp, x_sn, x_row, *_pn(h), img_p, img_sn, *_bias(bias),
-                                        *_pn(c_prev), ptr(done, F32), *_pn(gates), *_pn(c_out), *_pn(h_out), C.byref(head),
-                                        C.byref(m), stream()), what)
-        return
-    fn = lib.nmarl_lstm_step_x_bf16x3 if x3 else lib.nmarl_lstm_step_x
-    check(fn(E, N, H, KX, xp, x_sn, x_row, K2, x2p, x2_sn, x2_row, *_pn(h), img_p, img_sn,
-                                *_bias(bias), *_pn(zadd1), *_pn(zadd2), *_pn(c_prev), ptr(done, F32), *_pn(gates),
-                                *_pn(c_out), *_pn(h_out), None if head is None else C.byref(head), stream()), what)
+            a.genv = C.pointer(g)
+        a.msg = C.pointer(m)
+    check(lib.nmarl_lstm_step_x(C.byref(a), stream()), what)
 
 
 def step_enc1_supported(n_feat, m_max, n_fc, n_h, N):
@@ -1070,10 +1071,10 @@ def bptt_step(gates, c_prev, c_new, done, dh, dh2, dc, ws, dz, dc_prev, dhd, app
     wxm, _, img = ws
     KM = 0 if wxm is None else wxm.shape[1]
     mp, m_sn, m_row = (None, 0, 0) if mask is None else _rows_view(mask, mask.shape[2], 'bptt_step mask')
-    check(lib.nmarl_lstm_bptt_step_db(E, N, H4 // 4, KM, *_pn(gates), *_pn(c_prev), *_pn(c_new), ptr(done, F32), *_pn(dh), *_pn(dh2),
-                                      *_pn(dc), ptr(img, F32), img.stride(0), *_pn(dz), *_pn(dc_prev), *_pn(dx), mp, m_sn, m_row,
-                                      *_pn(dhd), 1 if apply_keep else 0, ptr(db_part, F32), 0 if db_part is None else db_part.stride(0),
-                                      stream()), 'nmarl_lstm_bptt_step_db')
+    check(lib.nmarl_lstm_bptt_step(E, N, H4 // 4, KM, *_pn(gates), *_pn(c_prev), *_pn(c_new), ptr(done, F32), *_pn(dh), *_pn(dh2),
+                                   *_pn(dc), ptr(img, F32), img.stride(0), *_pn(dz), *_pn(dc_prev), *_pn(dx), mp, m_sn, m_row,
+                                   *_pn(dhd), 1 if apply_keep else 0, ptr(db_part, F32), 0 if db_part is None else db_part.stride(0),
+                                   stream()), 'nmarl_lstm_bptt_step')
 
 
 BPTT_SEQ_MAX_E = 1 << 21     # nmarl_lstm_bptt_seq addresses one (agent, step) panel with 32-bit byte offsets
@@ -1110,7 +1111,7 @@ def bptt_seq(G, Call, done, dHs, img, dZ, want_db=True, want_state_grad=False, h
     """The whole reverse recurrence in one launch (nmarl_lstm_bptt_seq): G / dZ [N,T,E,4H], Call [N,T+1,E,H], done [T,E],
     dHs [N,T,E,H] (the heads' dL/dh_t), img = lstm_bptt_wimage(None, wh).  -> (db [N,4H] or None, dh0, dc0 or None):
     every step masks the carried state by done_t (the reference's lstm does, agents/utils.py:104-105).
-    head_dy = (dy8 [N,T*E,8], hw [N,64,O]) instead of dHs: the kernel forms the heads' dL/dh itself (nmarl_lstm_bptt_seq_dy)."""
+    head_dy = (dy8 [N,T*E,8], hw [N,64,O]) instead of dHs: the kernel forms the heads' dL/dh itself (nmarl_lstm_bptt_seq's dy8 form)."""
     N, T, E, H4 = G.shape
     H = H4 // 4
     for x, w, what in ((G, H4, 'gates'), (dZ, H4, 'dz'), (Call, H, 'c_all')) + (((dHs, H, 'dh_ext'),) if head_dy is None else ()):
@@ -1120,21 +1121,17 @@ def bptt_seq(G, Call, done, dHs, img, dZ, want_db=True, want_state_grad=False, h
     part = torch.empty(N, nblk, H4, dtype=F32, device=G.device) if want_db else None
     dh0 = torch.empty(N, E, H, dtype=F32, device=G.device) if want_state_grad else None
     dc0 = torch.empty(N, E, H, dtype=F32, device=G.device) if want_state_grad else None
-    if head_dy is not None:
+    if head_dy is None:          # exactly one of the two forms of the heads' dL/dh: (dh_ext, its strides) or (dy8, its strides, hw, O)
+        dh, dy = (ptr(dHs, F32, strided=True), dHs.stride(0), dHs.stride(1)), (None, 0, 0, None, 0, 0)
+    else:
         dy8, hw = head_dy
         if dy8.shape != (N, T * E, 8) or not dy8.is_contiguous() or hw.shape[:2] != (N, H) or not hw.is_contiguous():
             raise ValueError('bptt_seq: head_dy = (dy8 [N,T*E,8], hw [N,64,O]) contiguous')
-        check(lib.nmarl_lstm_bptt_seq_dy(T, E, N, H, ptr(G, F32, strided=True), G.stride(0), G.stride(1), ptr(Call, F32, strided=True),
-                                         Call.stride(0), Call.stride(1), ptr(done, F32), ptr(dy8, F32), dy8.stride(0), E * 8,
-                                         ptr(hw, F32), hw.stride(0), hw.shape[2], ptr(img, F32), img.stride(0),
-                                         ptr(dZ, F32, strided=True), dZ.stride(0), dZ.stride(1), ptr(part),
-                                         0 if part is None else part.stride(0), *_pn(dh0), *_pn(dc0), stream()), 'nmarl_lstm_bptt_seq_dy')
-        return (part.sum(dim=1) if want_db else None), dh0, dc0
+        dh, dy = (None, 0, 0), (ptr(dy8, F32), dy8.stride(0), E * 8, ptr(hw, F32), hw.stride(0), hw.shape[2])
     check(lib.nmarl_lstm_bptt_seq(T, E, N, H, ptr(G, F32, strided=True), G.stride(0), G.stride(1), ptr(Call, F32, strided=True),
-                                  Call.stride(0), Call.stride(1), ptr(done, F32), ptr(dHs, F32, strided=True), dHs.stride(0),
-                                  dHs.stride(1), ptr(img, F32), img.stride(0), ptr(dZ, F32, strided=True), dZ.stride(0),
-                                  dZ.stride(1), ptr(part), 0 if part is None else part.stride(0), *_pn(dh0), *_pn(dc0),
-                                  stream()), 'nmarl_lstm_bptt_seq')
+                                  Call.stride(0), Call.stride(1), ptr(done, F32), *dh, *dy, ptr(img, F32), img.stride(0),
+                                  ptr(dZ, F32, strided=True), dZ.stride(0), dZ.stride(1), ptr(part), 0 if part is None else part.stride(0),
+                                  *_pn(dh0), *_pn(dc0), stream()), 'nmarl_lstm_bptt_seq')
     return (part.sum(dim=1) if want_db else None), dh0, dc0
 
 

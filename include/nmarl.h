@@ -313,6 +313,8 @@ int nmarl_lstm_cell_bwd(int64_t E, int32_t N, int32_t H, const float* gates, int
  *   z = [x | h_in * (1-done)] @ [wx; wh] + bias (+ zadd1) (+ zadd2),   x [N,E,KX], KX in {0, 32, ..., 256},
  *   (gates, c_new, h_new) = cell(z, c_prev, done)
  * Same maths as batched GEMMs followed by nmarl_lstm_cell_fwd, but the [rows,4H] pre-activation never reaches HBM.
+ * ONE entry point for every form of the lock-step, nmarl_lstm_step_x(const nmarl_step_x_t*, stream): the struct below holds
+ * the arguments, and the optional parts present -- head, msg, enc, genv (NULL: absent) and precision -- choose the form.
  * x: the LSTM input of one lock-step -- fc output (KX = n_fc), the [fcs | fcp] concatenation of policies.py:176-181
  * (KX = 2 n_fc), lstm_comm's [hx | hp | hm] (KX = 3 H), lstm_ic3's s (KX = H) -- with agent stride x_sn and row pitch
  * x_row >= KX (floats, multiples of 4; a column block of a wider buffer is read in place).  KX = 0: no x, the recurrent
@@ -324,6 +326,11 @@ int nmarl_lstm_cell_bwd(int64_t E, int32_t N, int32_t H, const float* gates, int
  * The weights come as the chunked image nmarl_lstm_wimage builds from wx [N,KX,4H] (NULL for KX = 0) and wh [N,H,4H]
  * (agent strides in floats): per agent nmarl_lstm_wimage_floats(KX) = (KX+64)*320 floats, image[k][c][t] = W[k][16t+c]
  * for t < 16, 4 floats of padding per (k,c); rebuild it whenever the weights change (once per update).
+ * The optional parts go together as described under each of them; NMARL_EINVAL for any other combination: msg with
+ * msg->kind = 0, msg without a head (or with head kind 0), msg with zadd1 / zadd2, enc or genv without head kind 3,
+ * genv without message kind 2, enc with message kind 2 / 3, enc with message kind 1 but no x, enc without msg but with x,
+ * precision other than 0 / 1, precision 1 with msg or genv.
+ *
  * head (NULL or kind 0: none) puts an actor or critic head in the epilogue (A <= 8): what Trainer._get_policy /
  * _get_value (utils.py:129-149) need from one lock-step, with h' still on chip.
  *   kind 1 (forward 'p', policies.py:50-57 + utils.py:135-141):
@@ -357,39 +364,10 @@ typedef struct nmarl_head {
     const float* w2; int64_t w2_sn;      /* kind 3: the critic's weights / bias (w, b are the actor's) */
     const float* b2; int64_t b2_sn;
 } nmarl_head_t;
-int nmarl_lstm_wimage_floats(int32_t KX);
-int nmarl_lstm_wimage(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
-                      float* img, int64_t img_sn, void* stream);
-int nmarl_lstm_step_x(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                      int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
-                      const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                      int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                      const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
-                      float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                      void* stream);
 /*
- * bf16x3 (opt-in reduced precision; the fp32 entry points above are unchanged): the main product [x | h (1-done)] @ [Wx; Wh]
- * and the value re-step's h' @ Wh as hi_a hi_b + hi_a lo_b + lo_a hi_b on the bf16 matrix cores, with a = hi + lo,
- * hi = bf16_rne(a), lo = bf16_rne(a - hi), fp32 accumulation (~3 * 2^-18 |a||b| per product).  Everything else -- the
- * in-kernel encoders, the cell, the heads, the draw, the env step -- is the fp32 twin's arithmetic.
- * nmarl_lstm_wimage_bf16x3: the split image of [wx; wh], the same nmarl_lstm_wimage_floats(KX) 4-byte words per agent
- * (img_sn in words), each word two bf16 (see csrc/lstm_mfma.hip for the layout).  nmarl_lstm_step_x_bf16x3 /
- * nmarl_lstm_step_x_enc_bf16x3: the arguments of nmarl_lstm_step_x / nmarl_lstm_step_x_enc with that image; no message
- * term (x2, zadd1 / zadd2 and every head kind are accepted as by the twin).
- */
-int nmarl_lstm_wimage_bf16x3(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
-                             float* img, int64_t img_sn, void* stream);
-int nmarl_lstm_step_x_bf16x3(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                             int32_t KX2, const float* x2, int64_t x2_sn, int64_t x2_row,
-                             const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                             int64_t bias_sn, const float* zadd1, int64_t zadd1_sn, const float* zadd2, int64_t zadd2_sn,
-                             const float* c_prev, int64_t c_prev_sn, const float* done, float* gates, int64_t gates_sn,
-                             float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn, const nmarl_head_t* head,
-                             void* stream);
-/*
- * nmarl_lstm_step_x for the policy / value step of a COUPLED net, its message term computed inside the kernel from the
- * neighbours' previous, un-masked h (quirk Q3; h_in of the other agents, agent stride h_sn) instead of by separate
- * gather / GEMM / bias-activation launches:
+ * msg (NULL: none; needs a head, no x2 / zadd1 / zadd2): the policy / value step of a COUPLED net, its message term computed
+ * inside the kernel from the neighbours' previous, un-masked h (quirk Q3; h_in of the other agents, agent stride h_sn) instead
+ * of by separate gather / GEMM / bias-activation launches:
  *   kind 1  lstm_comm (agents/utils.py:182-199): hm = relu([h_j : j in nbr(i)] @ w_msg + b_msg), K = 64*m_max <= 128;
  *           the LSTM input is [x (KX-64 columns: [hx | hp]) | hm]
  *   kind 2  lstm_ic3 (agents/utils.py:395-400): s = mean_j(h_j) @ w_msg + b_msg + enc, K = 64; the LSTM input is s (KX = 64)
@@ -412,9 +390,9 @@ int nmarl_lstm_step_x_bf16x3(int64_t E, int32_t N, int32_t H, int32_t KX, const 
  * nmarl_lstm_step_sync_words(E, N) 32-bit words the caller zeroes once and then leaves alone (word 2 becomes non-zero
  * if a block ever waited in vain, i.e. the launch shared the device with other work); every block must be resident, so
  * N * ceil(E / 128) may not exceed nmarl_handoff_capacity(1, K) (NMARL_EINVAL otherwise: use the two launches).  v_out
- * receives the critic's h part only (as nmarl_lstm_step_x with kind 3); gates / c_new / h_new / out are the POLICY step's.
- * msg->status (may be NULL): the hand-off status words (see nmarl_handoff_capacity below) -- word 0 is set, and stays
- * set, when a wave gives up waiting; nmarl_rmsprop_tf_clip_guarded then applies nothing (fail closed).
+ * receives the critic's h part only (as without a message term, head kind 3); gates / c_new / h_new / out are the POLICY
+ * step's.  msg->status (may be NULL): the hand-off status words (see nmarl_handoff_capacity below) -- word 0 is set, and
+ * stays set, when a wave gives up waiting; nmarl_rmsprop_tf_clip_guarded then applies nothing (fail closed).
  */
 typedef struct nmarl_msg {
     int32_t kind, m_max, K, pad_;
@@ -453,18 +431,25 @@ typedef struct nmarl_msg {
     float* mean_next; int64_t mean_next_sn, mean_next_row;
 } nmarl_msg_t;
 /*
- * The input encoders of a lock-step INSIDE the policy + value launch (head kind 3, no message term; round 5): IA2C-FP on
- * CACC, policies.py:176-181 -- s = [relu([x_i | x_nbr] W_ob + b_ob) | relu([pi_nbr] W_fp + b_fp)] (KX = 128) is formed by a
- * register-only matrix-core pre-phase from the env's COMPACT observation and the previous-step policies, written once to
- * `out` (the update's saved LSTM input; may be NULL: bootstrap step) and consumed as the K loop's first four chunks -- no
- * encoder launch, no re-read of s.  Replaces nmarl_fc_fwd_multi / the encoder half of nmarl_cacc_step_encode in front of
- * nmarl_lstm_step_x; same function up to fp32 summation order (the matrix cores add four products at a time).
+ * enc (NULL: none; needs head kind 3, no x2 / zadd1 / zadd2): the input encoders of a lock-step INSIDE the policy + value
+ * launch (round 5): IA2C-FP on CACC, policies.py:176-181 -- s = [relu([x_i | x_nbr] W_ob + b_ob) | relu([pi_nbr] W_fp + b_fp)]
+ * (KX = 128) is formed by a register-only matrix-core pre-phase from the env's COMPACT observation and the previous-step
+ * policies, written once to `out` (the update's saved LSTM input; may be NULL: bootstrap step) and consumed as the K loop's
+ * first four chunks -- no encoder launch, no re-read of s; x = NULL.  Replaces nmarl_fc_fwd_multi / the encoder half of
+ * nmarl_cacc_step_encode in front of the step; same function up to fp32 summation order (the matrix cores add four products
+ * at a time).
  *   ob [E][N][F = 5] (row pitch ob_row floats), fp [N][E][A = 4] (agent stride fp_sn); w_ob [N][15][64], b_ob [N][64],
  *   w_fp [N][8][64], b_fp [N][64]: the parameter tensors as they are (agent strides *_sn); out [N][E][128] view (agent
  *   stride out_sn, row pitch out_row); nbr: HOST copy of the neighbour table [N][m_max = 2], ascending, -1 padded (N <= 32).
  * Round 6 -- the observation encoder ALONE (w_fp = NULL; KX = 64, out [N][E][64]): IA2C (policies.py:145, `fc(ob, 'fc', n_fc)`:
  *   m_max = 2, w_ob [N][15][64]) and ConseNet (policies.py:381-390, the agent's own five features only: m_max = 0, w_ob [N][5][64],
  *   nbr ignored); fp / b_fp / relu_bits unused (NULL).
+ * enc WITH msg -- NeurComm's WHOLE lock-step in one launch (round 6; agents/utils.py:118-217 `lstm_comm`, utils.py:163-197,
+ * envs/cacc_env.py:191-242): head kind 3 and message kind 1 -- the two input encoders [relu(x~ W_ob + b) | relu(p~ W_fp + b)]
+ * run in the launch's pre-phase and, with enc->env, the CACC env step behind the action draw.  x (KX = 192: [N][E] rows of
+ * pitch x_row, agent stride x_sn) is the S slot of the saved activations: its first 128 columns are WRITTEN here by the encoders
+ * (every lane then reads back, as its K-loop operands, exactly the 16-byte pieces it wrote), the last 64 by the message pre-phase
+ * (msg->out).  enc->out must be NULL or x.  Replaces nmarl_cacc_step_encode + the step with the message term alone.
  */
 typedef struct nmarl_step_enc {
     const float* ob; int64_t ob_row;
@@ -491,33 +476,17 @@ typedef struct nmarl_step_enc {
      * per row instead of re-reading the 512-byte row of `out`. */
     uint32_t* relu_bits; int64_t relu_bits_sn;
 } nmarl_step_enc_t;
-int nmarl_lstm_step_env_words(int64_t E);
-int nmarl_lstm_step_x_enc(int64_t E, int32_t N, int32_t H, int32_t KX, const float* h_in, int64_t h_sn, const float* img,
-                          int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev, int64_t c_prev_sn,
-                          const float* done, float* gates, int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
-                          int64_t h_new_sn, const nmarl_head_t* head, const nmarl_step_enc_t* enc, void* stream);
-int nmarl_lstm_step_x_enc_bf16x3(int64_t E, int32_t N, int32_t H, int32_t KX, const float* h_in, int64_t h_sn, const float* img,
-                                 int64_t img_sn, const float* bias, int64_t bias_sn, const float* c_prev, int64_t c_prev_sn,
-                                 const float* done, float* gates, int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new,
-                                 int64_t h_new_sn, const nmarl_head_t* head, const nmarl_step_enc_t* enc, void* stream);
-int nmarl_lstm_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t w_sn, float* img, int64_t img_sn, void* stream);
-int nmarl_lstm_step_sync_words(int64_t E, int32_t N);
-int nmarl_lstm_step_x_msg(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                          const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                          int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                          int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                          const nmarl_head_t* head, const nmarl_msg_t* msg, void* stream);
 /*
- * CommNet's lock-step on the synthetic 5x5 grid with the ENV STEP as a role of the same launch (round 6; utils.py:163-197,
- * envs/atsc_env.py:181-207, agents/utils.py:344-417): nmarl_lstm_step_x_msg (head kind 3, message kind 2, msg->ob = the compact
- * observation encoder inside) launched with nmarl_lstm_step_grid_env_blocks(E, N) blocks MORE than the N x ceil(E / 128) LSTM
- * blocks -- the compute units those leave idle (56 of 256 at 25 x 1024).  Every LSTM wave adds its drawn actions into its replicas'
- * hand-off words (words [E][2] u64: 3 bits per agent, an arrival count above bit 59; nmarl_lstm_step_grid_words(E) words zeroed
- * ONCE, left zero by every launch); an env block waits (bounded) for the 25 arrivals of its groups of 16 replicas and then runs
- * nmarl_grid_step's own device code on them (bit-identical; arguments as for nmarl_grid_step with compact_obs = 1, objective =
- * queue), writing state, reward, done and the observation of lock-step t + 1 while the LSTM blocks are in their value re-steps.
- * A time-out raises msg->status word 0 (fail closed, like the hand-off of the new h).  env_blocks = 0: not available (no idle
- * compute unit) -- use nmarl_lstm_step_x_msg + nmarl_grid_step.
+ * genv (NULL: none; needs head kind 3 and message kind 2) -- CommNet's lock-step on the synthetic 5x5 grid with the ENV STEP as a
+ * role of the same launch (round 6; utils.py:163-197, envs/atsc_env.py:181-207, agents/utils.py:344-417): the step with head
+ * kind 3, message kind 2 and msg->ob (the compact observation encoder inside) launched with nmarl_lstm_step_grid_env_blocks(E, N)
+ * blocks MORE than the N x ceil(E / 128) LSTM blocks -- the compute units those leave idle (56 of 256 at 25 x 1024).  Every LSTM
+ * wave adds its drawn actions into its replicas' hand-off words (words [E][2] u64: 3 bits per agent, an arrival count above bit
+ * 59; nmarl_lstm_step_grid_words(E) words zeroed ONCE, left zero by every launch); an env block waits (bounded) for the 25
+ * arrivals of its groups of 16 replicas and then runs nmarl_grid_step's own device code on them (bit-identical; arguments as for
+ * nmarl_grid_step with compact_obs = 1, objective = queue), writing state, reward, done and the observation of lock-step t + 1
+ * while the LSTM blocks are in their value re-steps.  A time-out raises msg->status word 0 (fail closed, like the hand-off of the
+ * new h).  env_blocks = 0: not available (no idle compute unit) -- use the step without genv + nmarl_grid_step.
  */
 typedef struct nmarl_grid_env {
     const nmarl_grid_params_t* params;
@@ -526,26 +495,44 @@ typedef struct nmarl_grid_env {
     int32_t auto_reset, pad_; uint64_t seed; int64_t env_id_base; int32_t* episode;
     uint64_t* words;
 } nmarl_grid_env_t;
+/*
+ * precision 1 = bf16x3 (opt-in reduced precision; 0 = exact fp32, the default): the main product [x | h (1-done)] @ [Wx; Wh]
+ * and the value re-step's h' @ Wh as hi_a hi_b + hi_a lo_b + lo_a hi_b on the bf16 matrix cores, with a = hi + lo,
+ * hi = bf16_rne(a), lo = bf16_rne(a - hi), fp32 accumulation (~3 * 2^-18 |a||b| per product).  Everything else -- the
+ * in-kernel encoders, the cell, the heads, the draw, the env step -- is the fp32 form's arithmetic.
+ * nmarl_lstm_wimage with precision 1: the split image of [wx; wh], the same nmarl_lstm_wimage_floats(KX) 4-byte words per
+ * agent (img_sn in words), each word two bf16 (see csrc/lstm_mfma.hip for the layout).  The step with precision 1 takes that
+ * image; no message term and no grid role (x2, zadd1 / zadd2, enc and every head kind are accepted as with precision 0).
+ */
+typedef struct nmarl_step_x {
+    int64_t E;
+    int32_t N, H, KX, KX2, precision, pad_;
+    const float* x; int64_t x_sn, x_row;        /* written by the encoders with enc + msg (see nmarl_step_enc_t) */
+    const float* x2; int64_t x2_sn, x2_row;
+    const float* h_in; int64_t h_sn;
+    const float* img; int64_t img_sn;
+    const float* bias; int64_t bias_sn;
+    const float* zadd1; int64_t zadd1_sn;
+    const float* zadd2; int64_t zadd2_sn;
+    const float* c_prev; int64_t c_prev_sn;
+    const float* done;
+    float* gates; int64_t gates_sn;
+    float* c_new; int64_t c_new_sn;
+    float* h_new; int64_t h_new_sn;
+    const nmarl_head_t* head;
+    const nmarl_msg_t* msg;
+    const nmarl_step_enc_t* enc;
+    const nmarl_grid_env_t* genv;
+} nmarl_step_x_t;
+int nmarl_lstm_wimage_floats(int32_t KX);
+int nmarl_lstm_wimage(int32_t N, int32_t KX, const float* wx, int64_t wx_sn, const float* wh, int64_t wh_sn,
+                      float* img, int64_t img_sn, int32_t precision, void* stream);
+int nmarl_lstm_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t w_sn, float* img, int64_t img_sn, void* stream);
+int nmarl_lstm_step_sync_words(int64_t E, int32_t N);
+int nmarl_lstm_step_env_words(int64_t E);
 int nmarl_lstm_step_grid_words(int64_t E);
 int nmarl_lstm_step_grid_env_blocks(int64_t E, int32_t N);
-int nmarl_lstm_step_x_msg_grid(int64_t E, int32_t N, int32_t H, int32_t KX, const float* x, int64_t x_sn, int64_t x_row,
-                               const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                               int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                               int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                               const nmarl_head_t* head, const nmarl_msg_t* msg, const nmarl_grid_env_t* genv, void* stream);
-/*
- * NeurComm's WHOLE lock-step in one launch (round 6; agents/utils.py:118-217 `lstm_comm`, utils.py:163-197, envs/cacc_env.py:191-242):
- * nmarl_lstm_step_x_msg with head kind 3 and message kind 1, plus `enc` as in nmarl_lstm_step_x_enc -- the two input encoders
- * [relu(x~ W_ob + b) | relu(p~ W_fp + b)] run in the launch's pre-phase and, with enc->env, the CACC env step behind the action
- * draw.  x (KX = 192: [N][E] rows of pitch x_row, agent stride x_sn) is the S slot of the saved activations: its first 128 columns
- * are WRITTEN here by the encoders (every lane then reads back, as its K-loop operands, exactly the 16-byte pieces it wrote), the
- * last 64 by the message pre-phase (msg->out).  enc->out must be NULL or x.  Replaces nmarl_cacc_step_encode + nmarl_lstm_step_x_msg.
- */
-int nmarl_lstm_step_x_msg_enc(int64_t E, int32_t N, int32_t H, int32_t KX, float* x, int64_t x_sn, int64_t x_row,
-                              const float* h_in, int64_t h_sn, const float* img, int64_t img_sn, const float* bias,
-                              int64_t bias_sn, const float* c_prev, int64_t c_prev_sn, const float* done, float* gates,
-                              int64_t gates_sn, float* c_new, int64_t c_new_sn, float* h_new, int64_t h_new_sn,
-                              const nmarl_head_t* head, const nmarl_msg_t* msg, const nmarl_step_enc_t* enc, void* stream);
+int nmarl_lstm_step_x(const nmarl_step_x_t* a, void* stream);
 /*
  * One reverse step of the unrolled LSTM training graph (agents/utils.py:102-113, 199-208, 401-408, 585-593), the cell
  * backward and the dgrad product fused on the matrix cores (H = 64):
@@ -561,31 +548,28 @@ int nmarl_lstm_step_x_msg_enc(int64_t E, int32_t N, int32_t H, int32_t KX, float
 int nmarl_lstm_bptt_wimage_floats(int32_t KM);
 int nmarl_lstm_bptt_wimage(int32_t N, int32_t KM, const float* wxm, int64_t wxm_sn, const float* wh, int64_t wh_sn,
                            float* img, int64_t img_sn, void* stream);
+/* db_part (may be NULL): the step also ADDS the column sums of dz (the LSTM bias gradient of this step) to db_part
+ * [N][nmarl_lstm_bptt_step_parts(E)][256] (agent stride db_sn): the caller zeroes it before the first reverse step, orders
+ * the steps of one recurrence on one stream and sums over the parts at the end -- no pass over dZ. */
+int nmarl_lstm_bptt_step_parts(int64_t E);
 int nmarl_lstm_bptt_step(int64_t E, int32_t N, int32_t H, int32_t KM, const float* gates, int64_t gates_sn,
                          const float* c_prev, int64_t c_prev_sn, const float* c_new, int64_t c_new_sn,
                          const float* done, const float* dh, int64_t dh_sn, const float* dh2, int64_t dh2_sn,
                          const float* dc_in, int64_t dc_sn, const float* img, int64_t img_sn, float* dz,
                          int64_t dz_sn, float* dc_prev, int64_t dc_prev_sn, float* dx, int64_t dx_sn,
                          const float* mask, int64_t mask_sn, int64_t mask_row, float* dhd, int64_t dhd_sn,
-                         int32_t apply_keep, void* stream);
-/* The same step, also ADDING the column sums of dz (the LSTM bias gradient of this step) to db_part
- * [N][nmarl_lstm_bptt_step_parts(E)][256] (agent stride db_sn; may be NULL): the caller zeroes it before the first reverse
- * step, orders the steps of one recurrence on one stream and sums over the parts at the end -- no pass over dZ. */
-int nmarl_lstm_bptt_step_parts(int64_t E);
-int nmarl_lstm_bptt_step_db(int64_t E, int32_t N, int32_t H, int32_t KM, const float* gates, int64_t gates_sn,
-                            const float* c_prev, int64_t c_prev_sn, const float* c_new, int64_t c_new_sn,
-                            const float* done, const float* dh, int64_t dh_sn, const float* dh2, int64_t dh2_sn,
-                            const float* dc_in, int64_t dc_sn, const float* img, int64_t img_sn, float* dz,
-                            int64_t dz_sn, float* dc_prev, int64_t dc_prev_sn, float* dx, int64_t dx_sn,
-                            const float* mask, int64_t mask_sn, int64_t mask_row, float* dhd, int64_t dhd_sn,
-                            int32_t apply_keep, float* db_part, int64_t db_sn, void* stream);
+                         int32_t apply_keep, float* db_part, int64_t db_sn, void* stream);
 /*
  * The whole reverse recurrence of one update in ONE launch, for nets whose recurrence has no cross-agent term (lstm,
  * agents/utils.py:102-113 unrolled by policies.py:99-100): T reverse steps of nmarl_lstm_bptt_step(KM = 0,
  * apply_keep = 1) with dL/dc, the recurrent dL/dh, c_{t-1} and the weight image kept on chip between steps.
  *   gates [N][T][E][4H], dz likewise (agent stride *_sn, step stride *_st, floats);  c_all [N][T+1][E][H] (c_all[t] =
- *   the cell state step t started from);  done [T][E];  dh_ext [N][T][E][H] = dL/dh_t from the heads;
- *   img = nmarl_lstm_bptt_wimage(KM = 0) of the current wh.
+ *   the cell state step t started from);  done [T][E];  img = nmarl_lstm_bptt_wimage(KM = 0) of the current wh.
+ * The heads' dL/dh_t arrives in exactly one of two forms (the other pointer NULL; NMARL_EINVAL otherwise):
+ *   dh_ext [N][T][E][H] = dL/dh_t as a tensor (agent stride dh_sn, step stride dh_st), or
+ *   dy8 [N][T][E][8] = [d logits | d v | 0] of nmarl_heads_loss (agent stride dy_sn, step stride dy_st) with the heads' weights
+ *   hw [N][64][O] = [pi_w | v_w[:64]] (O = A + 1 <= 8): the kernel forms dL/dh_t(heads) = dy_t hw^T itself (round 6), two more
+ *   k-steps of the step's transposed product -- 32 bytes per row-step read instead of 256.
  * c_t (for tanh(c_t)) is RECOMPUTED as gf * (c_all[t] * (1 - done_t)) + gi * gu, operation for operation what the forward
  * kernels store (c_all[T] is never read; this and nmarl_lstm_bptt_coupled): gates / c_all must be the trace of a forward pass.
  * Outputs: dz (every step: the weight-gradient GEMMs need it);  db_part [N][nmarl_lstm_bptt_seq_blocks(E)][4H] or
@@ -595,17 +579,10 @@ int nmarl_lstm_bptt_step_db(int64_t E, int32_t N, int32_t H, int32_t KM, const f
 int nmarl_lstm_bptt_seq_blocks(int64_t E);
 int nmarl_lstm_bptt_seq(int32_t T, int64_t E, int32_t N, int32_t H, const float* gates, int64_t gates_sn,
                         int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
-                        const float* dh_ext, int64_t dh_sn, int64_t dh_st, const float* img, int64_t img_sn,
+                        const float* dh_ext, int64_t dh_sn, int64_t dh_st, const float* dy8, int64_t dy_sn, int64_t dy_st,
+                        const float* hw, int64_t hw_sn, int32_t O, const float* img, int64_t img_sn,
                         float* dz, int64_t dz_sn, int64_t dz_st, float* db_part, int64_t db_sn, float* dh0,
                         int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream);
-/* nmarl_lstm_bptt_seq with the heads' dL/dh formed inside the kernel (round 6): dy8 [N][T][E][8] = [d logits | d v | 0] of
- * nmarl_heads_loss (agent stride dy_sn, step stride dy_st), hw [N][64][O] = [pi_w | v_w[:64]] (O = A + 1 <= 8):
- * dL/dh_t(heads) = dy_t hw^T is two more k-steps of the step's transposed product -- 32 bytes per row-step read instead of 256. */
-int nmarl_lstm_bptt_seq_dy(int32_t T, int64_t E, int32_t N, int32_t H, const float* gates, int64_t gates_sn,
-                           int64_t gates_st, const float* c_all, int64_t c_sn, int64_t c_st, const float* done,
-                           const float* dy8, int64_t dy_sn, int64_t dy_st, const float* hw, int64_t hw_sn, int32_t O,
-                           const float* img, int64_t img_sn, float* dz, int64_t dz_sn, int64_t dz_st, float* db_part,
-                           int64_t db_sn, float* dh0, int64_t dh0_sn, float* dc0, int64_t dc0_sn, void* stream);
 
 /*
  * The reverse recurrence of a COUPLED net's update -- NeurComm (lstm_comm, agents/utils.py:182-208; unrolled training graph
@@ -644,7 +621,7 @@ typedef struct nmarl_bptt_coupled {
     int64_t gates_sn, gates_st, c_sn, c_st, dh_sn, dh_st, img_sn, imgm_sn, mask_sn, mask_st, mask_row, dz_sn, dz_st, d1_sn, d1_st,
         ring_sn, ring_slot, db_sn, dbm_sn, io_sn;
     /* round 6: EITHER dh_ext (the heads' dL/dh as a tensor) OR dy8 [N][T][E][8] = [d logits | d v | 0] of nmarl_heads_loss + the
-     * heads' weights hw [N][64][O] (O <= 8): the kernel then forms dL/dh_t(heads) = dy_t hw^T itself (as nmarl_lstm_bptt_seq_dy) */
+     * heads' weights hw [N][64][O] (O <= 8): the kernel then forms dL/dh_t(heads) = dy_t hw^T itself (as nmarl_lstm_bptt_seq with dy8) */
     const float *dy8, *hw;
     int64_t dy_sn, dy_st, hw_sn;
     int32_t O, pad2_;
@@ -759,7 +736,7 @@ int nmarl_thin_linear_bwd(int64_t rows, int32_t N, int32_t H, int32_t O, const f
  * 50-77): logits = h w[:, :A] + b[:A], v = h w[:, A] + b[A] + va (w [N,64,A+1] = [pi_w | v_w[:64]], b [N,A+1], va [N,rows] the
  * critic's neighbour-action term of nmarl_nbr_action_value_fwd); the loss terms of nmarl_a2c_loss_fwd -> loss_out [N,3]; d logits,
  * d v of nmarl_a2c_loss_bwd with g_up = 1 -> dy8 [N,rows,8] = [d logits | d v | 0 ..] and dv [N,rows]; dw [N,64,A+1] / db [N,A+1]
- * as nmarl_thin_linear_bwd; dh [N,rows,64] (may be NULL: the one-launch BPTT kernels expand dy8 themselves, nmarl_lstm_bptt_seq_dy).
+ * as nmarl_thin_linear_bwd; dh [N,rows,64] (may be NULL: the one-launch BPTT kernels expand dy8 themselves, nmarl_lstm_bptt_seq).
  * Replaces a skinny GEMM, two loss passes and nmarl_thin_linear_bwd: h is read once.  A + 1 <= 8.  Deterministic (partial
  * [N, nmarl_fc_bwd_chunks(rows,N), 65 (A+1) + 3], fixed-order sums).
  */
@@ -831,7 +808,7 @@ int nmarl_nstep_return(int64_t E, int32_t N, int32_t T, const float* r, const fl
  *   ms += (g*g - ms)*(1-rho);  w -= lr * g / sqrt(ms + eps)
  */
 /*
- * In-launch hand-off (nmarl_lstm_step_x_msg head kind 3, nmarl_lstm_bptt_coupled one-launch form): blocks wait for flags
+ * In-launch hand-off (nmarl_lstm_step_x with msg and head kind 3, nmarl_lstm_bptt_coupled one-launch form): blocks wait for flags
  * other blocks of the SAME launch publish, so every block must be co-resident.
  *   nmarl_handoff_capacity(which, K): the number of blocks of that kernel the device holds at once =
  *     hipOccupancyMaxActiveBlocksPerMultiprocessor(kernel, 512 threads, its dynamic LDS) x compute units   (which 1: the

@@ -32,7 +32,7 @@ def _emul(A, W):
 
 
 def _image_ref(w):
-    """Expected split image [N, 2 (K*320)] int16 of w = [wx; wh] [N,K,4H] (layout of nmarl_lstm_wimage_bf16x3)."""
+    """Expected split image [N, 2 (K*320)] int16 of w = [wx; wh] [N,K,4H] (layout of nmarl_lstm_wimage with precision 1)."""
     N, K, _ = w.shape
     hi = w.to(torch.bfloat16)
     lo = (w - hi.float()).to(torch.bfloat16)
@@ -96,7 +96,7 @@ def _check(G, C, Hn, z, c, keep, bound, what):
 @pytest.mark.parametrize('E', [77, 1000, 4096])
 @pytest.mark.parametrize('entry', ['step_x', 'step_x_enc'])
 def test_bf16x3_step_is_the_split_product(E, entry):
-    """nmarl_lstm_step_x_bf16x3 (policy + value, kind 3) and nmarl_lstm_step_x_enc_bf16x3 (<3,0,1>: encoders inside): the policy
+    """nmarl_lstm_step_x with precision 1 (policy + value, kind 3), without and with enc (<3,0,1>: encoders inside): the policy
     step's gates, c', h' vs the float64 split emulation (fp32 accumulation bound 2^-20 sum|a||b|) and vs exact float64 (split
     bound); the fp32 kernel is >= 10x farther from the emulation than the bf16x3 one; the draw follows the kernel's pi; the value
     re-step is the split product too."""

@@ -46,7 +46,7 @@ def test_batched_update_matches_reference_replicas_on_gpu(path, saved):
 def test_batched_update_on_compact_observations_matches_reference_replicas_on_gpu(agent, monkeypatch):
     """BatchedTrainer's exact configuration on CACC -- compact observations + saved activations, the policy + value launch
     running the input encoders itself (IA2C-FP: both, lstm_step_x_kernel<3,0,1>; round 6: IA2C and ConseNet their one, <3,0,2>;
-    nmarl_lstm_step_x_enc: no encoder launch exists) -- against the K = 4 reference-replica golden, and the in-kernel encoders
+    nmarl_lstm_step_x with enc: no encoder launch exists) -- against the K = 4 reference-replica golden, and the in-kernel encoders
     against the separate ones."""
     from helpers import build_product_batched, compare_batched, drive_batched
     z = load_npz(os.path.join(GOLDEN, 'nnb_%s_line.npz' % agent))

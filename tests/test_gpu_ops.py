@@ -725,6 +725,76 @@ def test_lstm_step_x_heads(N, E, A, m_max, KX, addends, mode):
     torch.testing.assert_close(v2, vg, rtol=1e-5, atol=1e-6)
 
 
+def test_lstm_step_x_refuses_combinations_no_form_has():
+    """nmarl_lstm_step_x chooses the form of the lock-step by the optional parts present (head / msg / enc / genv / precision):
+    every combination no form has is refused with NMARL_EINVAL before anything is launched, while the plain policy + value step
+    and the in-launch encoder step built from the same tensors run."""
+    import ctypes as C
+    from deeprl_network_amd import _lib, ops
+    EINVAL = -1
+    N, E, H, KX, A = 2, 32, 64, 64, 4
+    g = torch.Generator().manual_seed(3)
+    r = lambda *s: torch.randn(*s, generator=g).cuda()                                  # noqa: E731
+    h, c, x, bias, zadd = r(N, E, H), r(N, E, H), r(N, E, KX), r(N, 4 * H), r(N, E, 4 * H)
+    img = ops.lstm_wimage(r(N, KX, 4 * H) * 0.1, r(N, H, 4 * H) * 0.1)
+    done = torch.zeros(E, device='cuda')
+    h_new, c_new = torch.full((N, E, H), 7.0, device='cuda'), torch.full((N, E, H), 7.0, device='cuda')
+    pi_w, pi_b, v_w, v_b = r(N, H, A), r(N, A), r(N, H, 1), r(N, 1)
+    pi, v, act = torch.zeros(N, E, A, device='cuda'), torch.zeros(N, E, device='cuda'), torch.zeros(E, N, dtype=torch.uint8, device='cuda')
+    nbr = torch.tensor([[1], [0]], dtype=torch.int32, device='cuda')
+    m_img, m_b, m_enc = ops.lstm_msg_wimage(r(N, H, H) * 0.1), r(N, H), r(N, E, H)
+    enc = ops._step_enc(dict(ob=r(E, N, 5), fp=None, w_ob=r(N, 5, H), b_ob=r(N, H), w_fp=None, b_fp=None, nbrs=[[1], [0]]), N, E)
+    genv = _lib.GridEnv()           # (never read: the combinations below are refused before the grid role's own checks)
+
+    def msg(kind):                  # lstm_comm's (kind 1) / lstm_ic3's (kind 2) message term, one neighbour each
+        return _lib.Msg(kind=kind, m_max=1, K=H, nbr_idx=nbr.data_ptr(), img=m_img.data_ptr(), img_sn=H * H, b=m_b.data_ptr(),
+                        b_sn=H, enc=m_enc.data_ptr(), enc_sn=E * H, enc_row=H)
+
+    def step(head=3, x=x, msg=None, enc=None, genv=None, zadd1=None, zadd2=None, precision=0):
+        a = _lib.StepX(E=E, N=N, H=H, KX=KX, precision=precision, x_sn=E * KX, x_row=KX, h_in=h.data_ptr(), h_sn=E * H,
+                       img=img.data_ptr(), img_sn=img.stride(0), bias=bias.data_ptr(), bias_sn=4 * H, c_prev=c.data_ptr(),
+                       c_prev_sn=E * H, done=done.data_ptr(), c_new=c_new.data_ptr(), c_new_sn=E * H, h_new=h_new.data_ptr(),
+                       h_new_sn=E * H)
+        a.x = None if x is None else x.data_ptr()
+        for name, t in (('zadd1', zadd1), ('zadd2', zadd2)):
+            if t is not None:
+                setattr(a, name, t.data_ptr())
+                setattr(a, name + '_sn', E * 4 * H)
+        if head is not None:
+            a.head = C.pointer(_lib.Head(kind=head, A=A, mode=1, w=pi_w.data_ptr(), w_sn=H * A, b=pi_b.data_ptr(), b_sn=A,
+                                         pi_out=pi.data_ptr(), pi_sn=E * A, act_out=act.data_ptr(), v_out=v.data_ptr(), v_sn=E,
+                                         w2=v_w.data_ptr(), w2_sn=H, b2=v_b.data_ptr(), b2_sn=1))
+        for name, s in (('msg', msg), ('enc', enc), ('genv', genv)):
+            if s is not None:
+                setattr(a, name, C.pointer(s))
+        return _lib.lib.nmarl_lstm_step_x(C.byref(a), _lib.stream())
+
+    refused = {
+        'msg of kind 0': dict(head=1, msg=msg(0)),
+        'msg without a head': dict(head=None, msg=msg(1)),
+        'msg with head kind 0': dict(head=0, msg=msg(1)),
+        'msg with zadd1': dict(head=1, msg=msg(1), zadd1=zadd),
+        'msg with zadd2': dict(head=1, msg=msg(1), zadd2=zadd),
+        'enc without a head': dict(head=None, x=None, enc=enc),
+        'enc with head kind 1': dict(head=1, x=None, enc=enc),
+        'genv with head kind 1': dict(head=1, msg=msg(2), genv=genv),
+        'genv with message kind 1': dict(msg=msg(1), genv=genv),
+        'uncoupled enc with x': dict(enc=enc),
+        'enc with message kind 2': dict(msg=msg(2), x=None, enc=enc),
+        'enc with message kind 1 but no x': dict(msg=msg(1), x=None, enc=enc),
+        'bf16x3 with msg': dict(head=1, msg=msg(1), precision=1),
+        'bf16x3 with genv': dict(msg=msg(2), genv=genv, precision=1),
+        'precision 2': dict(precision=2),
+    }
+    for what, kw in refused.items():
+        assert step(**kw) == EINVAL, what
+    torch.cuda.synchronize()
+    assert torch.all(h_new == 7) and torch.all(c_new == 7)          # nothing was launched
+    assert step() == 0 and step(x=None, enc=enc) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(h_new).all() and not torch.all(h_new == 7)
+
+
 def test_lstm_sequence_x_fwd_bwd():
     """The update's recurrence with the x-side product inside the step (ops.lstm_sequence_x) vs plain autograd over the
     restatement: outputs and all gradients (s, wx, wh, b, h0, c0)."""
@@ -864,7 +934,7 @@ def test_lstm_bptt_seq_one_launch(N, T, E):
 
 @pytest.mark.parametrize('N,T,E,O', [(8, 12, 4096, 5), (3, 5, 127, 6), (25, 4, 130, 6), (2, 1, 1, 5), (4, 7, 33, 3), (2, 3, 70, 8)])
 def test_lstm_bptt_seq_expands_the_heads_gradient_itself(N, T, E, O):
-    """nmarl_lstm_bptt_seq_dy (round 6): the heads' dL/dh handed over as dy8 [N,T*E,8] = [d logits | d v | 0] + the heads' weights
+    """nmarl_lstm_bptt_seq with dy8 (round 6): the heads' dL/dh handed over as dy8 [N,T*E,8] = [d logits | d v | 0] + the heads' weights
     hw [N,64,O] and formed inside the launch (two more k-steps of every step's transposed product) against nmarl_lstm_bptt_seq on
     the tensor dL/dh = dy hw^T (float64 product, rounded once): dz, the bias gradient and the initial state's gradient at fp32
     summation-order tolerance (the fp32 matrix-core accumulation of 5-8 terms against a rounded float64 sum); dones inside the
@@ -949,7 +1019,7 @@ def test_heads_loss_one_pass_vs_torch(N, rows, A, m_max, want_dh):
 @pytest.mark.parametrize('N,E,A,m_max', [(8, 4096, 4, 2), (25, 130, 5, 4), (5, 127, 4, 2), (25, 1024, 5, 4)])
 @pytest.mark.parametrize('kind', [1, 2])
 def test_lstm_step_x_in_kernel_message_term(N, E, A, m_max, kind):
-    """The message term of a coupled net computed by the step kernel's pre-phase (nmarl_lstm_step_x_msg) vs the float64
+    """The message term of a coupled net computed by the step kernel's pre-phase (nmarl_lstm_step_x with msg) vs the float64
     restatement: lstm_comm hm = relu(gather(h) W_msg + b) (kind 1, K = 64 m_max <= 128) / lstm_ic3 s = mean(h) W_msg + b +
     enc (kind 2), ragged -1 padded neighbour tables, message output stored into a column block, policy and value heads."""
     from deeprl_network_amd import ops
@@ -1084,7 +1154,7 @@ def test_lstm_step_x_in_kernel_message_term(N, E, A, m_max, kind):
 
 @pytest.mark.parametrize('N,E,A,m_max', [(8, 4096, 4, 2), (5, 127, 4, 2), (6, 300, 5, 1)])
 def test_lstm_step_x_dial_message_term(N, E, A, m_max):
-    """lstm_dial's receiver side inside the step kernel (nmarl_lstm_step_x_msg kind 3, agents/utils.py:560-580) vs the float64
+    """lstm_dial's receiver side inside the step kernel (nmarl_lstm_step_x with msg kind 3, agents/utils.py:560-580) vs the float64
     restatement: hm = relu(gather(msg) W_msg + b) from the SENDERS' message vectors, s = hm + enc the LSTM input; hm and s
     stored (the update's relu mask / saved input); policy step (also IN PLACE: the pre-phase reads no h) and value step."""
     from deeprl_network_amd import ops
@@ -1441,7 +1511,7 @@ def test_batch_epilogue_matches_host_code(N, E, H, A, F, T):
 @pytest.mark.parametrize('N,E', [(8, 4096), (8, 1000), (8, 77), (5, 1), (3, 129)])
 @pytest.mark.parametrize('mode', [1, 2])
 def test_lstm_step_x_input_encoders_inside_the_launch(N, E, mode):
-    """nmarl_lstm_step_x_enc (lstm_step_x_kernel<3,0,1>): FPPolicy's two input encoders (policies.py:176-181) as the
+    """nmarl_lstm_step_x with enc (lstm_step_x_kernel<3,0,1>): FPPolicy's two input encoders (policies.py:176-181) as the
     register-only pre-phase of the policy + value launch, from the compact observation [E,N,5] and the previous-step policies
     [N,E,4] through the neighbour table (ascending, left packed, absent slots zero).  Against the float64 restatement
     (encoder output, new state, gates, policy, draw, value) and against the separate encoder launch (nmarl_fc_fwd_multi)

@@ -3,7 +3,7 @@
 #   NMARL_GRID_ENV_IN_KERNEL  the grid env step as a role of CommNet's lock-step launch (csrc/lstm_mfma.hip GENV)  vs  nmarl_grid_step
 #   NMARL_MSG_CARRY           the re-step's message term handed to the next lock-step (CARRY 1 | 2)               vs  recomputed
 #   NMARL_FUSED_HEADS_LOSS    heads + loss + heads' backward in one pass (nmarl_heads_loss)                       vs  GEMM + loss fwd / bwd + thin_bwd
-#   NMARL_BPTT_HEAD_DY        the one-launch BPTT expands dy8 itself (nmarl_lstm_bptt_seq_dy)                      vs  dL/dh as a tensor
+#   NMARL_BPTT_HEAD_DY        the one-launch BPTT expands dy8 itself (nmarl_lstm_bptt_seq with dy8)                vs  dL/dh as a tensor
 #   NMARL_BPTT_HEAD_DY_COUPLED  the same for the coupled BPTT kernels (nmarl_bptt_coupled_t.dy8)                    vs  dL/dh as a tensor
 cd "$(dirname "$0")/.."
 run() { env "${@:3}" python bench.py --full --no-cpu-baseline --no-other-configs --steps 20 --warmup 4 --config config/config_$1.ini 2>/dev/null | python -c "

@@ -32,10 +32,8 @@ for name, args in _lib.SIGNATURES.items():
     if hasattr(dbg, name):
         getattr(dbg, name).argtypes = args
         getattr(dbg, name).restype = C.c_int
-_lib.lib.nmarl_lstm_step_x = dbg.nmarl_lstm_step_x            # route the product wrappers through the instrumented build
+_lib.lib.nmarl_lstm_step_x = dbg.nmarl_lstm_step_x            # route every form of the lock-step through the instrumented build
 _lib.lib.nmarl_lstm_wimage = dbg.nmarl_lstm_wimage
-_lib.lib.nmarl_lstm_step_x_msg = dbg.nmarl_lstm_step_x_msg
-_lib.lib.nmarl_lstm_step_x_enc = dbg.nmarl_lstm_step_x_enc
 N, E, H, A, KX = 8, 4096, 64, 4, 128
 head = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 3
 ENC = 'enc' in sys.argv                       # head 3 with the input encoders inside the launch (round 5)
