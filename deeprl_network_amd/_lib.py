@@ -136,6 +136,19 @@ class BpttCoupled(C.Structure):
                  ('O', C.c_int32), ('pad2_', C.c_int32)])
 
 
+class BpttDial(C.Structure):
+    """nmarl_bptt_dial_t (include/nmarl.h): arguments of nmarl_lstm_bptt_dial."""
+    _fields_ = ([(k, C.c_int32) for k in ('N', 'T', 'H', 'm_max', 'r_max', 'r_row', 'symmetric', 'mode', 'ring_slots', 'O')] +
+                [('E', C.c_int64)] +
+                [(k, C.c_void_p) for k in ('gates', 'c_all', 'done', 'dh_ext', 'dy8', 'hw', 'img', 'img_m', 'img_f', 'hm', 'msg', 'dz',
+                                           'ds', 'd1', 'd2', 'ring', 'db_part', 'dbm_part', 'dbf_part', 'dhr_io', 'dc_io', 'ws',
+                                           'status', 'rev_agent', 'rev_col', 'rev_w')] +
+                [(k, C.c_int64) for k in ('gates_sn', 'gates_st', 'c_sn', 'c_st', 'dh_sn', 'dh_st', 'dy_sn', 'dy_st', 'hw_sn', 'img_sn',
+                                          'imgm_sn', 'imgf_sn', 'hm_sn', 'hm_st', 'hm_row', 'msg_sn', 'msg_st', 'dz_sn', 'dz_st',
+                                          'ds_sn', 'ds_st', 'd1_sn', 'd1_st', 'd2_sn', 'd2_st', 'ring_sn', 'ring_slot', 'db_sn',
+                                          'dbm_sn', 'dbf_sn', 'io_sn')])
+
+
 class GridParams(C.Structure):
     """nmarl_grid_params_t (include/nmarl.h)."""
     _fields_ = [('norm_wave', C.c_float), ('clip_wave', C.c_float), ('peak1', C.c_float), ('peak2', C.c_float),
@@ -210,6 +223,7 @@ SIGNATURES = {
     'nmarl_lstm_bptt_msg_wimage': [_i32, _i32, _p, _i64, _p, _i64, _p],
     'nmarl_lstm_bptt_coupled_ws_words': [_i64, _i32],
     'nmarl_lstm_bptt_coupled': [C.POINTER(BpttCoupled), _p],
+    'nmarl_lstm_bptt_dial': [C.POINTER(BpttDial), _p],
     'nmarl_fc_fwd': [_i64, _i32, _i32, _i32, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _i64, _i64, _p],
     'nmarl_fc_fwd_multi': [_i64, _i32, _i32, C.POINTER(FcPart), _i32, _p, _i64, _i64, _p],
     'nmarl_dial_msg_adjoint': [_i64, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i32,

@@ -506,8 +506,8 @@ class BatchedPolicy:
     @property
     def bptt_takes_head_dy(self):
         """The backward of `unroll_saved` understands ops.head_dy_placeholder (the heads' dL/dh as dy8, expanded inside the
-        BPTT kernel): the uncoupled nets' recurrence (ops._lstm_seq_x_backward) and the coupled one (agents/sequence.py; DIAL's
-        step-wise recurrence turns it into the tensor first)."""
+        BPTT kernel): the uncoupled nets' recurrence (ops._lstm_seq_x_backward) and the coupled ones (agents/sequence.py; DIAL overrides
+        this: dy8 only where its one-launch kernel applies, else the step-wise pair, which takes the tensor)."""
         if self.coupled and os.environ.get('NMARL_BPTT_HEAD_DY_COUPLED', '1') == '0':      # (A/B switch for the coupled kernels alone)
             return False
         return self.xside
@@ -1081,7 +1081,13 @@ class DIALMultiAgentPolicy(BatchedPolicy):
     """DIAL (policies.py:479-525 + lstm_dial agents/utils.py:515-599):
     s_i = relu(x~_i W_ob) + relu([mfc_j(h_j) for j in nbr(i)] W_msg) + onehot_H(argmax pi_i(t-1)) -> LSTM(H);
     the message encoder mfc_j = relu(h_j W + b) acts on the sender's un-masked previous h."""
-    bptt_takes_head_dy = False      # (its reverse recurrence is step-wise launches taking dL/dh as a tensor: the fused pass writes it)
+    @property
+    def bptt_takes_head_dy(self):
+        """dy8 where the reverse recurrence is nmarl_lstm_bptt_dial (it expands the heads' gradient itself, in both of its forms);
+        the step-wise pair takes dL/dh as a tensor, which the fused heads pass then writes.  Answered from the neighbour table alone:
+        the engine (agents/sequence.py) also asks ops.bptt_dial_operands_ok for the operands' layout, and where that says no although
+        this said yes it rebuilds the tensor from dy8 (ops.head_dy_to_dh) in front of the step-wise pair -- slower, not wrong."""
+        return BatchedPolicy.bptt_takes_head_dy.fget(self) and ops.dial_bptt_table(self.nbr_idx, self.n_h) is not None
 
     name = 'dial'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'

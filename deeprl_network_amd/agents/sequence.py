@@ -233,9 +233,21 @@ class CoupledSequenceSaved(torch.autograd.Function):
             rev = _reverse_table(nbr_idx, ckind)
             if rev is not None and not ops.bptt_coupled_supported(ckind, nbr_idx.shape[1], H, rev=rev):
                 rev = None                    # e.g. lstm_comm with more than 2 sources per agent: the step-wise loop below
-        if head_dy is not None and rev is None:       # (recurrences without a dy8 form take the tensor it stands for)
+        rev_dial = dbmfc = None
+        if fused and kind == 'dial' and ops.bptt_dial_operands_ok(G, Call, done, dHs if head_dy is None else None, wxm, wh, w_msg, mfc_w,
+                                                                  hm, A2):
+            rev_dial = ops.dial_bptt_table(nbr_idx, H)       # None: m_max > 2, more than 2 sources per agent, no GPU -- the step-wise pair below
+        if head_dy is not None and rev is None and rev_dial is None:       # (recurrences without a dy8 form take the tensor it stands for)
             dHs, head_dy = ops.head_dy_to_dh(*head_dy, (N, T, E, H)), None
-        if rev is not None:
+        if rev_dial is not None:
+            # lstm_dial: the WHOLE reverse recurrence in one launch -- cell backward, [ds | dh] = dz @ [wx; wh]^T, both relu masks, the
+            # message adjoint handed between the agents' blocks, the sender layer's product, the three bias gradients on the way
+            rev = rev_dial
+            ws = (wxm, wh, ops.lstm_bptt_wimage(wxm, wh))
+            wm = (w_msg, ops.lstm_bptt_msg_wimage(w_msg))
+            db, dbmsg, dbmfc, _, _ = ops.bptt_dial(rev, nbr_idx.shape[1], G, Call, done, dHs if head_dy is None else None, ws, wm,
+                                                   ops.lstm_bptt_msg_wimage(mfc_w), hm, A2, dZ, DS, D1, D2, head_dy=head_dy)
+        elif rev is not None:
             # the WHOLE reverse recurrence in one launch: cell backward, [dx | dh] = dz @ [wxm; wh]^T, relu mask, the message
             # adjoint D1 @ w_msg^T handed between the agents' blocks inside the kernel, both bias gradients on the way
             ws = (wxm, wh, ops.lstm_bptt_wimage(wxm, wh))
@@ -246,7 +258,7 @@ class CoupledSequenceSaved(torch.autograd.Function):
             ws = (wxm, wh, ops.lstm_bptt_wimage(wxm, wh))
             dhd_buf = torch.empty(N, E, H, dtype=F32, device=dev)
         adj = None
-        if fused and kind == 'dial' and w_msg.stride(2) == 1 and w_msg.stride(1) == H:
+        if fused and kind == 'dial' and rev_dial is None and w_msg.stride(2) == 1 and w_msg.stride(1) == H:
             # lstm_dial: the whole message adjoint of a step (both relu masks, gather adjoint, both products) in ONE more launch
             rev_d = _reverse_table(nbr_idx, ops.COUPLED_NC)
             if ops.dial_adjoint_supported(nbr_idx.shape[1], H, rev_d):
@@ -304,7 +316,7 @@ class CoupledSequenceSaved(torch.autograd.Function):
                 D2x = D2e.view(N, Rx, H)
                 dwmsg = _dwmsg_by_runs(A2.view(N, Rx, H), D1x, nbr_idx, H)
                 dmfc_w = ops.wgrad(Hx, D2x)
-                dmfc_b = D2x.sum(dim=1) if adj is None else adj[3][1].sum(dim=1)
+                dmfc_b = dbmfc if dbmfc is not None else (D2x.sum(dim=1) if adj is None else adj[3][1].sum(dim=1))
             elif A1.numel() and tuple(A1.shape) == (N, T + 1, E, H) and A1.is_contiguous():
                 dwmsg = ops.wgrad(A1.view(N, Rx, H), D1x)       # ic3: the rollout kept mean_nbr(h_{t-1}) (A1 = the (T + 1)-slab MM buffer)
             else:
@@ -360,7 +372,7 @@ class CoupledSequenceSaved(torch.autograd.Function):
             else:
                 dwmsg = ops.wgrad(ops.nbr_gather(A2[:, :T].reshape(N, R, H), nbr_idx), D1f)
             dmfc_w = ops.wgrad(Hp, D2f)
-            dmfc_b = D2f.sum(dim=1) if adj is None else adj[3][1].sum(dim=1)
+            dmfc_b = dbmfc if dbmfc is not None else (D2f.sum(dim=1) if adj is None else adj[3][1].sum(dim=1))
             denc = DS
         return (None, None, None, denc, None, dwx, dwh, db, dwmsg, dbmsg, dmfc_w, dmfc_b, None, None, None, None, None, None, None)
 

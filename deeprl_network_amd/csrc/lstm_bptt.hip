@@ -616,6 +616,10 @@ struct CoupledArgs {
     const float *dy8, *hw;
     int64_t dy_sn, dy_st, hw_sn;
     int32_t O;
+    // DIAL (lstm_dial, see the note at the kernel): the senders' layer between the gathered adjoint and dL/dh
+    const float *msg, *img_f;               // msg [N][..][E][H] post-relu sender vectors (slab t = msg_t); img_f: W_mfc image, read from global memory
+    float *ds, *d2, *dbf_part;              // ds [N][T][E][H] un-masked dx; d2 [N][..][E][H]; dbf_part [N][tiles][H] column sums of d2
+    int64_t msg_sn, msg_st, imgf_sn, ds_sn, ds_st, d2_sn, d2_st, dbf_sn;
 };
 
 typedef __attribute__((address_space(1))) unsigned gu32;
@@ -632,7 +636,19 @@ __device__ __forceinline__ void bstore4_wt(const __amdgpu_buffer_rsrc_t r, const
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), r, off, 0, SC1);      // write-through (sc1)
 }
 
-template <int NTM, int RMAX, bool MASK, bool DY = false>     // NTM: 16-column tiles of a message row (64 m_max / 16 or 4); RMAX: max sources; DY: see CoupledArgs
+//
+// DIAL = true: lstm_dial (agents/utils.py:561-593, policies.py:479-525).  The receiver side is lstm_comm's (MASK: D1 = dx * (hm > 0),
+// M = D1 W_msg^T through the ring; the un-masked dx is stored as well: ds = d enc), but what a sender j collects is not yet dL/dh: it
+// is dmsg_j, the gradient at its message vector msg = relu(h W_mfc + b_mfc), so the consumer side of the hand-off goes on with
+//     d2_j = dmsg_j * (msg_{t+1}[j] > 0)  (stored: operand of W_mfc's gradient; column sums = b_mfc's gradient),   dL/dh_t[j] += d2_j W_mfc^T
+// -- a third transposed product (16 k-steps x 4 tiles) whose B operand is d2 in the lane's own units and whose result lands in the
+// lane's own units of gh, like the heads' part.  LDS: [Wx; Wh]^T (128 KB) + W_msg (32 KB at m_max = 2) fill the CU's 160 KB, so the
+// 16 KB W_mfc image is NOT staged: its 16 float4 A operands per lane are requested from global memory (L2-resident: every wave of
+// every block of the agent reads the same 16 KB every step) as the FIRST thing of a step, in front of the poll -- they are in
+// flight while the wave waits for its neighbours and need no block barrier; their 64 registers are the product's accumulators later
+// in the step.  The adjoint of step 0's messages is consumed by a tail pass t = -1 (poll, d2_0, dL/dh_{-1}) of the same loop: t_lo = -1
+// in the one-launch form, one more launch (t_hi = t_lo = -1) step-wise; it leaves the complete dL/dh_{-1}, dL/dc_{-1} in dhr_io / dc_io.
+template <int NTM, int RMAX, bool MASK, bool DY = false, bool DIAL = false>     // NTM: 16-column tiles of a message row (64 m_max / 16 or 4); RMAX: max sources; DY: see CoupledArgs
 __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const CoupledArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int IMG8 = G4 * 16 * 8;                // [Wxm; Wh]^T image (NT = 8)
@@ -731,7 +747,7 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
         gh[0] = gh[1] = gh[2] = gh[3] = float4{0.f, 0.f, 0.f, 0.f};                        \
     } else {                                                                               \
         const int64_t ts_ = __builtin_amdgcn_readfirstlane(t_);                            \
-        const __amdgpu_buffer_rsrc_t re_ = make_rsrc(eA + ts_ * a.dh_st, nb1);             \
+        const __amdgpu_buffer_rsrc_t re_ = make_rsrc(eA + ts_ * a.dh_st, nbh);             \
         gh[0] = bload4i(re_, lo1, 0);                                                      \
         gh[1] = bload4i(re_, lo1, 64);                                                     \
         gh[2] = bload4i(re_, lo1, 128);                                                    \
@@ -756,9 +772,13 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
     GateGroup sA, sB;
     float4 gh[4], dc[4];
     float dya = 0.0f, dyb = 0.0f;
-    NMARL_CP_LOADG(sA, t_hi, 0)
-    NMARL_CP_LOADG(sB, t_hi, 1)
-    NMARL_CP_LOADH(t_hi)
+    const int t_hi0 = DIAL && t_hi < 0 ? 0 : t_hi;   // DIAL's tail launch: loads stay inside the tensors, their values are not used
+    NMARL_CP_LOADG(sA, t_hi0, 0)
+    NMARL_CP_LOADG(sB, t_hi0, 1)
+    {
+        const uint32_t nbh = DIAL && t_hi < 0 ? 0u : nb1;        // no heads' gradient at h_{-1}: a zero-record resource reads 0
+        NMARL_CP_LOADH(t_hi0)
+    }
     {
         // state the range starts from: zero at the end of the sequence, else what the previous launch left.  The recurrent
         // dL/dh lives INSIDE the prefetched inputs: it is added to the heads' dL/dh (gh) of the step it belongs to
@@ -773,17 +793,17 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
         gh[2].x += h2.x; gh[2].y += h2.y; gh[2].z += h2.z; gh[2].w += h2.w;
         gh[3].x += h3.x; gh[3].y += h3.y; gh[3].z += h3.z; gh[3].w += h3.w;
     }
-    if (DY) {                                        // + the heads' dL/dh of step t_hi
+    if (DY && !(DIAL && t_hi < 0)) {                 // + the heads' dL/dh of step t_hi
         NMARL_CP_HEADS()
     }
     // bias-gradient partial sums, fully reduced over the wave's 16 rows every step: lane (c, q) keeps, per unit group j,
     // the column of gate 2 (c & 1) + ((c >> 1) & 1), unit 16 j + 4 q + 2 ((c >> 2) & 1) + ((c >> 3) & 1)  (4 registers), and of
     // the message layer's bias the unit 16 jm + 4 q + 2 ((c >> 1) & 1) + (c & 1), jm = 2 ((c >> 2) & 1) + ((c >> 3) & 1)  (1)
-    float dbacc[4], dbm = 0.0f;
+    float dbacc[4], dbm = 0.0f, dbf = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) dbacc[i] = 0.0f;
     const bool b2 = (c & 4) != 0, b3 = (c & 8) != 0;
-    float keepA = 1.0f - (a.done + (int64_t)t_hi * a.E)[lor];
+    float keepA = 1.0f - (a.done + (int64_t)t_hi0 * a.E)[lor];
     __syncthreads();                                 // images visible
 
     // one k-step = the image row (s, q) of all 8 output tiles (two ds_read_b128) x the lane's dz value: 8 MFMAs.  The reads of
@@ -890,9 +910,26 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
     NMARL_BSTAMP(1)
     for (int t = t_hi; t >= t_lo; --t) {
         NMARL_BSTAMP_T(2)
-        const int tp = t > t_lo ? t - 1 : t_lo;      // clamped: the last prefetch re-reads the range's last step
-        const int64_t tu = __builtin_amdgcn_readfirstlane(t);
+        int tp = t > t_lo ? t - 1 : t_lo;            // clamped: the last prefetch re-reads the range's last step
+        if (DIAL && tp < 0) tp = 0;                  // (the tail pass t = -1 prefetches nothing it uses)
+        const int64_t tu = __builtin_amdgcn_readfirstlane(DIAL && t < 0 ? 0 : t);
         const __amdgpu_buffer_rsrc_t rz = make_rsrc(zA + tu * a.dz_st, nb4);
+        // DIAL: the sender layer's operands of step t + 1, requested in front of the poll (see the note above the kernel)
+        const uint32_t nbh = DIAL && t == 0 ? 0u : nb1;          // DIAL: the step behind t = 0 is the tail pass, see the prologue
+        float4 wf[DIAL ? 16 : 1], mg[DIAL ? 4 : 1];
+        unsigned fbits = 0u;
+        if (DIAL) {
+            uint32_t fo = (uint32_t)(q * 16 + c) * 16u, mo = lo1;      // opaque: the image reads are loop invariants (see lstm_bptt_seq_kernel)
+            asm volatile("" : "+v"(fo), "+v"(mo));
+            const int64_t t1 = __builtin_amdgcn_readfirstlane(t + 1);
+            const __amdgpu_buffer_rsrc_t rf = make_rsrc(a.img_f + (int64_t)n * a.imgf_sn, (uint32_t)(H * H) * 4u);
+            const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.msg + (int64_t)n * a.msg_sn + t1 * a.msg_st, t == T - 1 ? 0u : nb1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mg[j] = bload4i(rg, mo, 64 * j);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) wf[s] = bload4i(rf, fo, 1024 * s);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         const __amdgpu_buffer_rsrc_t rd1 = make_rsrc(d1A + tu * a.d1_st, nb1);
         // ---- the neighbours' message adjoints of step t + 1: FIRST thing of the step (it is the hand-off's critical path):
         // one poll, then every source's four loads in flight together.  Nothing else is outstanding at this point (the step
@@ -918,6 +955,17 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
             }
             asm volatile("" ::: "memory");               // payload loads stay below the poll
             NMARL_BSTAMP_T(3)
+            // msg > 0 as 16 bits (bit 4 j + i: unit 16 j + 4 q + i).  DY: formed HERE, in front of the payload loads (the poll's value came
+            // back behind the msg loads: they have landed) -- with the heads' operands resident the 16 msg registers next to the payload
+            // were spilled; the tensor form has the room and spills when they are packed early (241 VGPRs, 36 B of scratch): there at use
+#define NMARL_CP_FBITS()                                                                   \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                  \
+                fbits |= (mg[j].x > 0.0f ? 1u : 0u) << (4 * j) | (mg[j].y > 0.0f ? 2u : 0u) << (4 * j) | \
+                         (mg[j].z > 0.0f ? 4u : 0u) << (4 * j) | (mg[j].w > 0.0f ? 8u : 0u) << (4 * j);
+            if (DIAL && DY) {
+                NMARL_CP_FBITS()
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int s = 0; s < RMAX; ++s) {
                 // nothing to read at the end of the sequence (nothing was handed over yet) and from an absent source (weight 0:
@@ -944,13 +992,64 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
             mk3 = bload4i(rm, lom, 192);
         }
         __builtin_amdgcn_sched_barrier(0);
+        if (!DIAL) {
 #pragma unroll
-        for (int s = 0; s < RMAX; ++s) {                 // summed in source order (the restatement's order)
-            const float w_ = src_w[s];
+            for (int s = 0; s < RMAX; ++s) {             // summed in source order (the restatement's order)
+                const float w_ = src_w[s];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    gh[j].x += w_ * mm[s][j].x; gh[j].y += w_ * mm[s][j].y; gh[j].z += w_ * mm[s][j].z; gh[j].w += w_ * mm[s][j].w;
+                }
+            }
+        } else {
+            // dmsg_{t+1} (source order) -> d2 = dmsg * (msg_{t+1} > 0): stored, summed for b_mfc's gradient, then gh += d2 W_mfc^T
+            f32x4 d2v[4];
+            if (!DY) { NMARL_CP_FBITS() }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                gh[j].x += w_ * mm[s][j].x; gh[j].y += w_ * mm[s][j].y; gh[j].z += w_ * mm[s][j].z; gh[j].w += w_ * mm[s][j].w;
+                float4 dm = float4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < RMAX; ++s) {
+                    const float w_ = src_w[s];
+                    dm.x += w_ * mm[s][j].x; dm.y += w_ * mm[s][j].y; dm.z += w_ * mm[s][j].z; dm.w += w_ * mm[s][j].w;
+                }
+                d2v[j] = f32x4{(fbits >> (4 * j)) & 1u ? dm.x : 0.0f, (fbits >> (4 * j + 1)) & 1u ? dm.y : 0.0f,
+                               (fbits >> (4 * j + 2)) & 1u ? dm.z : 0.0f, (fbits >> (4 * j + 3)) & 1u ? dm.w : 0.0f};
             }
+            {
+                uint32_t so2 = lo1;                      // (stores: lane offset + constant in a VGPR, see below)
+                asm volatile("" : "+v"(so2));
+                const int64_t t1 = __builtin_amdgcn_readfirstlane(t + 1);
+                const __amdgpu_buffer_rsrc_t rd2 = make_rsrc(a.d2 + (int64_t)n * a.d2_sn + t1 * a.d2_st, t == T - 1 ? 0u : nb1);
+                float qm[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    bstore4(rd2, so2 + 64 * j, float4{d2v[j][0], d2v[j][1], d2v[j][2], d2v[j][3]});
+                    const float a0 = odd ? d2v[j][1] : d2v[j][0], g0 = odd ? d2v[j][0] : d2v[j][1];
+                    const float a1 = odd ? d2v[j][3] : d2v[j][2], g1 = odd ? d2v[j][2] : d2v[j][3];
+                    const float r0 = a0 + dpp_xor1(g0), r1 = a1 + dpp_xor1(g1);
+                    const float k2 = hi ? r1 : r0, g2 = hi ? r0 : r1;
+                    qm[j] = k2 + dpp_xor2(g2);
+                }
+                const float k0_ = b2 ? qm[2] : qm[0], g0_ = b2 ? qm[0] : qm[2];
+                const float k1_ = b2 ? qm[3] : qm[1], g1_ = b2 ? qm[1] : qm[3];
+                const float r0_ = k0_ + __shfl_xor(g0_, 4, 64), r1_ = k1_ + __shfl_xor(g1_, 4, 64);
+                const float k3_ = b3 ? r1_ : r0_, g3_ = b3 ? r0_ : r1_;
+                dbf += k3_ + __shfl_xor(g3_, 8, 64);
+            }
+            f32x4 g0_ = f32x4{gh[0].x, gh[0].y, gh[0].z, gh[0].w}, g1_ = f32x4{gh[1].x, gh[1].y, gh[1].z, gh[1].w};
+            f32x4 g2_ = f32x4{gh[2].x, gh[2].y, gh[2].z, gh[2].w}, g3_ = f32x4{gh[3].x, gh[3].y, gh[3].z, gh[3].w};
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {               // k-step s = 4 j + i: d2 unit 16 j + 4 q + i of the lane's row
+                const float bv = d2v[s >> 2][s & 3];
+                g0_ = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].x, bv, g0_, 0, 0, 0);
+                g1_ = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].y, bv, g1_, 0, 0, 0);
+                g2_ = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].z, bv, g2_, 0, 0, 0);
+                g3_ = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s].w, bv, g3_, 0, 0, 0);
+            }
+            gh[0] = float4{g0_[0], g0_[1], g0_[2], g0_[3]}; gh[1] = float4{g1_[0], g1_[1], g1_[2], g1_[3]};
+            gh[2] = float4{g2_[0], g2_[1], g2_[2], g2_[3]}; gh[3] = float4{g3_[0], g3_[1], g3_[2], g3_[3]};
+            if (t < 0) break;                            // the tail pass ends here: gh = dL/dh_{-1}
         }
         __builtin_amdgcn_sched_barrier(0);
         unsigned mbits = 0xFFFFu;                     // bit 4 j + i: hm > 0 for unit 16 j + 4 q + i of the lane's row
@@ -1011,6 +1110,11 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
         NMARL_BSTAMP_T(12)
         // ---- D1 = dx (relu-masked) in the lane's own units; bias gradient of the message layer
         f32x4 d1v[4];
+        if (DIAL) {                                  // ds = the un-masked dx (dL/d enc)
+            const __amdgpu_buffer_rsrc_t rds = make_rsrc(a.ds + (int64_t)n * a.ds_sn + tu * a.ds_st, nb1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bstore4(rds, so1 + 64 * j, float4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]});
+        }
         {
             float qm[4];
 #pragma unroll
@@ -1078,7 +1182,7 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
         gh[1].x += acc[5][0] * keepA; gh[1].y += acc[5][1] * keepA; gh[1].z += acc[5][2] * keepA; gh[1].w += acc[5][3] * keepA;
         gh[2].x += acc[6][0] * keepA; gh[2].y += acc[6][1] * keepA; gh[2].z += acc[6][2] * keepA; gh[2].w += acc[6][3] * keepA;
         gh[3].x += acc[7][0] * keepA; gh[3].y += acc[7][1] * keepA; gh[3].z += acc[7][2] * keepA; gh[3].w += acc[7][3] * keepA;
-        if (DY) {                                    // + the heads' dL/dh of step t - 1 (its dy8 was requested mid-step)
+        if (DY && !(DIAL && t == 0)) {               // + the heads' dL/dh of step t - 1 (its dy8 was requested mid-step)
             NMARL_CP_HEADS()
         }
         keepA = keep_next;
@@ -1098,7 +1202,15 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
 #undef NMARL_CP_MBL
 #undef NMARL_CP_MMF
 #undef NMARL_CP_MKS
+#undef NMARL_CP_FBITS
 
+    if (DIAL && t_lo < 0 && arow_ok) {               // after the tail pass: the complete gradient of the state the sequence started from
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            *reinterpret_cast<float4*>(a.dhr_io + (int64_t)n * a.io_sn + arow_raw * H + 4 * q + 16 * j) = gh[j];
+            *reinterpret_cast<float4*>(a.dc_io + (int64_t)n * a.io_sn + arow_raw * H + 4 * q + 16 * j) = dc[j];
+        }
+    }
     // ---- bias gradients: every lane holds 4 + 1 finished column sums of its wave; sum over the 8 waves, a step-wise run
     // accumulates over its launches
     __syncthreads();                                 // every wave is done with the images: reuse their LDS
@@ -1107,6 +1219,7 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
 #pragma unroll
         for (int j = 0; j < 4; ++j) lds[wave * G4 + 64 * g + 16 * j + 4 * q + iu] = dbacc[j];
         lds[WAVES * G4 + wave * H + 16 * iu + 4 * q + 2 * ((c >> 1) & 1) + (c & 1)] = dbm;
+        if (DIAL) lds[WAVES * (G4 + H) + wave * H + 16 * iu + 4 * q + 2 * ((c >> 1) & 1) + (c & 1)] = dbf;
     }
     __syncthreads();
     const bool accum = t_hi != T - 1;
@@ -1122,6 +1235,13 @@ __global__ __launch_bounds__(512, 1) void lstm_bptt_coupled_kernel(const Coupled
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) v += lds[WAVES * G4 + w * H + u];
         float* o = a.dbm_part + (int64_t)n * a.dbm_sn + (int64_t)blk * H + u;
+        *o = accum ? *o + v : v;
+    } else if (DIAL && threadIdx.x < G4 + 2 * H) {
+        const int u = threadIdx.x - G4 - H;
+        float v = 0.0f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) v += lds[WAVES * (G4 + H) + w * H + u];
+        float* o = a.dbf_part + (int64_t)n * a.dbf_sn + (int64_t)blk * H + u;
         *o = accum ? *o + v : v;
     }
 }
@@ -1325,6 +1445,24 @@ __global__ __launch_bounds__(256) void zero_words_kernel(unsigned* __restrict__ 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) w[i] = 0u;
 }
+
+// the fields nmarl_bptt_coupled_t and nmarl_bptt_dial_t share under the same names -> the kernel's arguments (the relu mask's
+// operand is named differently in the two, and only lstm_dial has the sender layer's: those stay with the entry points)
+template <class P>
+void fill_coupled_common(CoupledArgs& a, const P* p, int64_t tiles) {
+    a.gates = p->gates; a.c_all = p->c_all; a.done = p->done; a.dh_ext = p->dh_ext; a.img = p->img; a.img_m = p->img_m;
+    a.dz = p->dz; a.d1 = p->d1; a.ring = p->ring; a.db_part = p->db_part; a.dbm_part = p->dbm_part; a.dhr_io = p->dhr_io;
+    a.dc_io = p->dc_io;
+    a.flags = reinterpret_cast<unsigned*>(p->ws);
+    a.err = a.flags + (int64_t)p->N * tiles * WAVES;
+    a.rev_agent = p->rev_agent; a.rev_col = p->rev_col; a.rev_w = p->rev_w;
+    a.gates_sn = p->gates_sn; a.gates_st = p->gates_st; a.c_sn = p->c_sn; a.c_st = p->c_st; a.dh_sn = p->dh_sn; a.dh_st = p->dh_st;
+    a.img_sn = p->img_sn; a.imgm_sn = p->imgm_sn; a.dz_sn = p->dz_sn;
+    a.dz_st = p->dz_st; a.d1_sn = p->d1_sn; a.d1_st = p->d1_st; a.ring_sn = p->ring_sn; a.ring_slot = p->ring_slot;
+    a.db_sn = p->db_sn; a.dbm_sn = p->dbm_sn; a.io_sn = p->io_sn;
+    a.E = p->E; a.N = p->N; a.T = p->T; a.tiles = (int32_t)tiles;
+    a.dy8 = p->dy8; a.hw = p->hw; a.dy_sn = p->dy_sn; a.dy_st = p->dy_st; a.hw_sn = p->hw_sn; a.O = p->O;
+}
 }  // namespace
 
 extern "C" int nmarl_lstm_bptt_coupled(const nmarl_bptt_coupled_t* p, void* stream) {
@@ -1357,19 +1495,9 @@ extern "C" int nmarl_lstm_bptt_coupled(const nmarl_bptt_coupled_t* p, void* stre
         ((uintptr_t)p->dhr_io % 16) || ((uintptr_t)p->dc_io % 16) || ((uintptr_t)p->ws % 4))
         return NMARL_EINVAL;
     CoupledArgs a{};
-    a.gates = p->gates; a.c_all = p->c_all; a.done = p->done; a.dh_ext = p->dh_ext; a.img = p->img; a.img_m = p->img_m;
+    fill_coupled_common(a, p, tiles);
     a.mask = p->kind == 1 ? p->mask : nullptr;
-    a.dz = p->dz; a.d1 = p->d1; a.ring = p->ring; a.db_part = p->db_part; a.dbm_part = p->dbm_part; a.dhr_io = p->dhr_io;
-    a.dc_io = p->dc_io;
-    a.flags = reinterpret_cast<unsigned*>(p->ws);
-    a.err = a.flags + (int64_t)N * tiles * WAVES;
-    a.rev_agent = p->rev_agent; a.rev_col = p->rev_col; a.rev_w = p->rev_w;
-    a.gates_sn = p->gates_sn; a.gates_st = p->gates_st; a.c_sn = p->c_sn; a.c_st = p->c_st; a.dh_sn = p->dh_sn; a.dh_st = p->dh_st;
-    a.img_sn = p->img_sn; a.imgm_sn = p->imgm_sn; a.mask_sn = p->mask_sn; a.mask_st = p->mask_st; a.dz_sn = p->dz_sn;
-    a.dz_st = p->dz_st; a.d1_sn = p->d1_sn; a.d1_st = p->d1_st; a.ring_sn = p->ring_sn; a.ring_slot = p->ring_slot;
-    a.db_sn = p->db_sn; a.dbm_sn = p->dbm_sn; a.io_sn = p->io_sn;
-    a.E = E; a.N = N; a.T = T; a.mask_row = (int32_t)p->mask_row; a.tiles = (int32_t)tiles;
-    a.dy8 = p->dy8; a.hw = p->hw; a.dy_sn = p->dy_sn; a.dy_st = p->dy_st; a.hw_sn = p->hw_sn; a.O = p->O;
+    a.mask_sn = p->mask_sn; a.mask_st = p->mask_st; a.mask_row = (int32_t)p->mask_row;
     if (p->ring_slots < 2) return NMARL_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // every polled word starts at zero for every call (flags count the steps done WITHIN the call); the error word behind
@@ -1405,6 +1533,114 @@ extern "C" int nmarl_lstm_bptt_coupled(const nmarl_bptt_coupled_t* p, void* stre
         else if (p->kind == 2 && rmax == 2) rc = launch_coupled<4, 2, false>(a, (unsigned)grid, lds_bytes, st);
         else if (p->kind == 2 && rmax == 4) rc = launch_coupled<4, 4, false>(a, (unsigned)grid, lds_bytes, st);
         else rc = NMARL_EINVAL;
+    }
+    return rc;
+}
+
+// ---- lstm_dial: the DIAL instantiations of lstm_bptt_coupled_kernel (see the note above it)
+namespace {
+template <int NTM>
+int launch_dial(const CoupledArgs& a, unsigned grid, size_t lds_bytes, hipStream_t st) {
+    static NmarlPerDeviceOnce once;
+    if (const unsigned long long bit = once.pending(); bit != ~0ull) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bptt_coupled_kernel<NTM, 2, true, false, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bptt_coupled_kernel<NTM, 2, true, true, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+            return NMARL_EHIP;
+        once.done(bit);
+    }
+    if (a.dy8) hipLaunchKernelGGL((lstm_bptt_coupled_kernel<NTM, 2, true, true, true>), dim3(grid), dim3(512), lds_bytes, st, a);
+    else hipLaunchKernelGGL((lstm_bptt_coupled_kernel<NTM, 2, true, false, true>), dim3(grid), dim3(512), lds_bytes, st, a);
+    return nmarl_check_launch();
+}
+}  // namespace
+
+// blocks per CU of the DIAL instantiations (message rows of K floats): nmarl_handoff_capacity(3, K)
+NMARL_INTERNAL int nmarl_bptt_dial_occupancy(int K) {
+    if (K != 64 && K != 128) return -1;
+    const size_t lds_bytes = ((size_t)G4 * 16 * 8 + (size_t)K * H) * 4;
+    static std::atomic<int> cache[64][2];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    const int kd = K == 128 ? 1 : 0;
+    if (dev >= 0 && dev < 64) {
+        const int hit = cache[dev][kd].load();
+        if (hit > 0) return hit - 1;
+    }
+    int best = -1;
+    auto ask = [&](auto kernel) {
+        int per_cu = 0;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 512, lds_bytes) != hipSuccess)
+            return false;
+        best = best < 0 || per_cu < best ? per_cu : best;
+        return true;
+    };
+    const bool ok = K == 128 ? (ask(lstm_bptt_coupled_kernel<8, 2, true, false, true>) && ask(lstm_bptt_coupled_kernel<8, 2, true, true, true>))
+                             : (ask(lstm_bptt_coupled_kernel<4, 2, true, false, true>) && ask(lstm_bptt_coupled_kernel<4, 2, true, true, true>));
+    if (!ok) return -1;
+    if (dev >= 0 && dev < 64) cache[dev][kd].store(best + 1);
+    return best;
+}
+
+extern "C" int nmarl_lstm_bptt_dial(const nmarl_bptt_dial_t* p, void* stream) {
+    if (!p || p->H != H || p->E < 0 || p->N <= 0 || p->T <= 0 || p->m_max <= 0 || p->m_max > 2 || p->r_max <= 0 || p->r_max > 2 || p->r_row != 2)
+        return NMARL_EINVAL;
+    const int64_t E = p->E;
+    const int N = p->N, T = p->T;
+    const int K = H * p->m_max;                                          // floats per message row
+    if (E == 0) return NMARL_OK;
+    if (E > (1 << 21) || ((uintptr_t)p->status % 4)) return NMARL_EINVAL;
+    if ((!p->dh_ext) == (!p->dy8)) return NMARL_EINVAL;            // the heads' dL/dh: as a tensor, or as dy8 + the heads' weights
+    if (p->dy8 && (!p->hw || p->O <= 0 || p->O > 8 || p->hw_sn < (int64_t)H * p->O || p->dy_st < E * 8 || (p->dy_st % 4) ||
+                   !sn_ok(p->dy_sn, (T - 1) * p->dy_st + E * 8) || ((uintptr_t)p->dy8 % 16)))
+        return NMARL_EINVAL;
+    if (!p->gates || !p->c_all || !p->done || !p->img || !p->img_m || !p->img_f || !p->hm || !p->msg || !p->dz || !p->ds || !p->d1 ||
+        !p->d2 || !p->ring || !p->db_part || !p->dbm_part || !p->dbf_part || !p->dhr_io || !p->dc_io || !p->ws || !p->rev_agent ||
+        !p->rev_col || !p->rev_w)
+        return NMARL_EINVAL;
+    const int64_t tiles = (E + ROWS_B - 1) / ROWS_B;
+    auto seq_ok = [&](const void* q, int64_t sn, int64_t st, int64_t W) {      // [N][T][E][W] with contiguous rows
+        return st >= E * W && (st % 4) == 0 && sn_ok(sn, (T - 1) * st + E * W) && ((uintptr_t)q % 16) == 0;
+    };
+    if (!seq_ok(p->gates, p->gates_sn, p->gates_st, G4) || !seq_ok(p->dz, p->dz_sn, p->dz_st, G4) || p->c_st < E * H || (p->c_st % 4) ||
+        !sn_ok(p->c_sn, T * p->c_st + E * H) || ((uintptr_t)p->c_all % 16) || (p->dh_ext && !seq_ok(p->dh_ext, p->dh_sn, p->dh_st, H)) ||
+        !seq_ok(p->ds, p->ds_sn, p->ds_st, H) || !seq_ok(p->d1, p->d1_sn, p->d1_st, H) || !seq_ok(p->d2, p->d2_sn, p->d2_st, H) ||
+        !seq_ok(p->msg, p->msg_sn, p->msg_st, H) || p->img_sn < (int64_t)G4 * 2 * H || (p->img_sn % 4) || p->imgm_sn < (int64_t)K * H ||
+        (p->imgm_sn % 4) || p->imgf_sn < (int64_t)H * H || (p->imgf_sn % 4) || !sn_ok(p->ring_sn, E * K) ||
+        !sn_ok(p->ring_slot, (N - 1) * p->ring_sn + E * K) || p->db_sn < tiles * G4 || p->dbm_sn < tiles * H || p->dbf_sn < tiles * H ||
+        !sn_ok(p->io_sn, E * H) || p->hm_row < H || (p->hm_row % 4) || p->hm_st < (E - 1) * p->hm_row + H || (p->hm_st % 4) ||
+        !sn_ok(p->hm_sn, (T - 1) * p->hm_st + (E - 1) * p->hm_row + H) || ((uintptr_t)p->hm % 16) || ((uintptr_t)p->img % 16) ||
+        ((uintptr_t)p->img_m % 16) || ((uintptr_t)p->img_f % 16) || ((uintptr_t)p->ring % 16) || ((uintptr_t)p->dhr_io % 16) ||
+        ((uintptr_t)p->dc_io % 16) || ((uintptr_t)p->ws % 4) || p->ring_slots < 2)
+        return NMARL_EINVAL;
+    CoupledArgs a{};
+    fill_coupled_common(a, p, tiles);
+    a.mask = p->hm; a.mask_sn = p->hm_sn; a.mask_st = p->hm_st; a.mask_row = (int32_t)p->hm_row;
+    a.msg = p->msg; a.img_f = p->img_f; a.ds = p->ds; a.d2 = p->d2; a.dbf_part = p->dbf_part;
+    a.msg_sn = p->msg_sn; a.msg_st = p->msg_st; a.imgf_sn = p->imgf_sn; a.ds_sn = p->ds_sn; a.ds_st = p->ds_st; a.d2_sn = p->d2_sn;
+    a.d2_st = p->d2_st; a.dbf_sn = p->dbf_sn;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t grid = tiles * N;
+    const int cap = nmarl_handoff_capacity(3, K);
+    if (cap < 0) return NMARL_EHIP;                  // (nothing launched yet)
+    {       // every polled word starts at zero for every call (a kernel, not a memset node: see nmarl_lstm_bptt_coupled)
+        const int64_t nw = (int64_t)N * tiles * WAVES;
+        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(p->ws), nw);
+    }
+    // one launch (T steps + the tail pass) under the conditions of nmarl_lstm_bptt_coupled, else T + 1 launches of one pass each
+    const bool one_launch = p->mode != 2 && p->ring_slots >= T && (p->mode == 1 || (p->symmetric && grid <= cap));
+    a.slots = one_launch ? T : 2;
+    a.status = p->status;
+    a.fault = one_launch && nmarl_handoff_take_fault() ? 1 : 0;
+    a.max_spins = a.fault ? NMARL_HANDOFF_FAULT_SPINS : NMARL_HANDOFF_MAX_SPINS;
+    const size_t lds_bytes = ((size_t)G4 * 16 * 8 + (size_t)K * H) * 4;
+    int rc = NMARL_OK;
+    for (int t_hi = T - 1; t_hi >= -1 && rc == NMARL_OK; t_hi = one_launch ? -2 : t_hi - 1) {
+        a.t_hi = t_hi;
+        a.t_lo = one_launch ? -1 : t_hi;
+        rc = K == 128 ? launch_dial<8>(a, (unsigned)grid, lds_bytes, st) : launch_dial<4>(a, (unsigned)grid, lds_bytes, st);
     }
     return rc;
 }

@@ -1581,6 +1581,7 @@ bool nmarl_handoff_take_fault() {
 }
 
 NMARL_INTERNAL int nmarl_bptt_coupled_occupancy(int K);      // lstm_bptt.hip: blocks per CU of the coupled BPTT kernel
+NMARL_INTERNAL int nmarl_bptt_dial_occupancy(int K);         // lstm_bptt.hip: ... of its lstm_dial instantiations
 
 extern "C" int nmarl_handoff_capacity(int32_t which, int32_t K) {
     const int cus = nmarl_handoff_cus();
@@ -1612,6 +1613,9 @@ extern "C" int nmarl_handoff_capacity(int32_t which, int32_t K) {
         }
     } else if (which == 2) {
         per_cu = nmarl_bptt_coupled_occupancy(K);
+        if (per_cu < 0) return -1;
+    } else if (which == 3) {
+        per_cu = nmarl_bptt_dial_occupancy(K);
         if (per_cu < 0) return -1;
     } else {
         return -1;

@@ -1136,6 +1136,7 @@ def bptt_seq(G, Call, done, dHs, img, dZ, want_db=True, want_state_grad=False, h
 
 
 COUPLED_NC, COUPLED_IC3 = 1, 2           # nmarl_bptt_coupled_t.kind: lstm_comm / lstm_ic3
+COUPLED_DIAL = 3                         # lstm_dial: nmarl_lstm_bptt_dial (its own argument struct)
 
 
 def dial_adjoint_supported(m_max, H, rev):
@@ -1243,11 +1244,11 @@ COUPLED_RING_MAX_BYTES = 4 << 30     # one slot per step (one-launch form) up to
 COUPLED_WS_KEEP = 2                  # workspaces (ring + flags + hand-over buffers) kept per process, least recently used dropped
 
 
-def _coupled_workspace(dev, N, E, K, T):
+def _coupled_workspace(dev, N, E, K, T, dial=False):
     """Message buffer ([slots][N][E][K], zeroed ONCE: the kernel only needs finite contents; slots = T so that the
     one-launch form never re-reads an address, 2 if that would not fit COUPLED_RING_MAX_BYTES), flag words and the state
     hand-off buffers of nmarl_lstm_bptt_coupled -- allocated once per shape and kept (the update calls it every batch)."""
-    key = (dev, N, E, K, T)
+    key = (dev, N, E, K, T, dial)
     w = _coupled_ws.pop(key, None)
     if w is not None:
         _coupled_ws[key] = w                  # most recently used last
@@ -1261,6 +1262,8 @@ def _coupled_workspace(dev, N, E, K, T):
                  dhr=torch.zeros(N, E, FUSED_H, dtype=F32, device=dev), dc=torch.zeros(N, E, FUSED_H, dtype=F32, device=dev),
                  db=torch.zeros(N, tiles, 4 * FUSED_H, dtype=F32, device=dev), dbm=torch.zeros(N, tiles, FUSED_H, dtype=F32, device=dev),
                  tiles=tiles)
+        if dial:                              # lstm_dial: the sender layer's bias gradient
+            w['dbf'] = torch.zeros(N, tiles, FUSED_H, dtype=F32, device=dev)
         _coupled_ws[key] = w
     if _keepalive[0] is not None:
         _keepalive[0].append(w)
@@ -1316,6 +1319,112 @@ def bptt_coupled(kind, rev, m_max, G, Call, done, dHs, ws, wm, mask, dZ, D1, mod
     a.rev_agent, a.rev_col, a.rev_w = ptr(rev['rev_agent'], torch.int32), ptr(rev['rev_col'], torch.int32), ptr(rev['rev_w'], F32)
     check(lib.nmarl_lstm_bptt_coupled(C.byref(a), stream()), 'nmarl_lstm_bptt_coupled')
     return w['db'].sum(dim=1), w['dbm'].sum(dim=1)
+
+
+def bptt_dial_supported(m_max, H, rev=None, device=None):
+    """nmarl_lstm_bptt_dial handles this lstm_dial recurrence: a GPU, 64-unit cells, at most 2 neighbour slots (message rows of 64 or
+    128 floats: with the [wx; wh] image they fill a CU's LDS) and, with the reverse table at hand, at most 2 sources per agent --
+    lstm_comm's envelope (bptt_coupled_supported).  Everything else stays on bptt_step + dial_msg_adjoint."""
+    if device is not None and torch.device(device).type != 'cuda':
+        return False
+    if device is None and rev is not None and rev['rev_w'].device.type != 'cuda':
+        return False
+    if H != FUSED_H or not 1 <= m_max <= 2:
+        return False
+    return rev is None or rev['r_max'] <= 2
+
+
+def bptt_dial_operands_ok(G, Call, done, dHs, wxm, wh, w_msg, mfc_w, hm, msg):
+    """The layout nmarl_lstm_bptt_dial reads in place: contiguous rows in every sequence operand (hm: a view with unit column stride),
+    contiguous per-agent weight panels.  dHs None: the heads' gradient comes as dy8.  False: the caller stays on the step-wise pair."""
+    H = wh.shape[1]
+
+    def rows(x, W):
+        return x.dim() == 4 and x.stride(3) == 1 and x.stride(2) == W
+
+    def panel(w_):
+        return w_.dim() == 3 and w_.stride(2) == 1 and w_.stride(1) == w_.shape[2]
+    return (rows(G, 4 * H) and rows(Call, H) and rows(msg, H) and (dHs is None or rows(dHs, H)) and hm.dim() == 4 and hm.stride(3) == 1 and
+            hm.shape[3] == H and done.is_contiguous() and wxm.shape[1] == H and panel(wxm) and panel(wh) and panel(w_msg) and panel(mfc_w))
+
+
+def dial_bptt_table(nbr_idx, H):
+    """The reverse neighbour table nmarl_lstm_bptt_dial works from, or None where bptt_dial_supported says no -- the ONE place the
+    engine (agents/sequence.py) and the policy (bptt_takes_head_dy) ask.  Built once per neighbour table."""
+    m_max = nbr_idx.shape[1]
+    if not bptt_dial_supported(m_max, H, device=nbr_idx.device):
+        return None
+    key = (nbr_idx.data_ptr(), nbr_idx.device, tuple(nbr_idx.shape))
+    ent = _dial_tables.pop(key, None)
+    if ent is None:
+        while len(_dial_tables) >= DIAL_TABLES_KEEP:           # least recently used first (a run has one table; a test session many)
+            _dial_tables.pop(next(iter(_dial_tables)))
+        ent = (nbr_idx, reverse_neighbor_table(nbr_idx, COUPLED_NC))                      # keeps nbr_idx alive: the key stays unique
+    _dial_tables[key] = ent                                    # most recently used last
+    rev = ent[1]
+    return rev if rev is not None and bptt_dial_supported(m_max, H, rev=rev, device=nbr_idx.device) else None
+
+
+_dial_tables = {}
+DIAL_TABLES_KEEP = 8                 # reverse tables kept per process (a dropped one is rebuilt on its next use)
+
+
+def bptt_dial(rev, m_max, G, Call, done, dHs, ws, wm, img_f, hm, msg, dZ, DS, D1, D2, mode=0, head_dy=None, want_state_grad=False):
+    """The whole reverse recurrence of lstm_dial's update in one launch (nmarl_lstm_bptt_dial; T + 1 step-wise launches of the same
+    kernel when the grid is not resident at once or the in-launch hand-off is switched off): G / dZ [N,T,E,4H], Call [N,T+1,E,H],
+    done [T,E], dHs [N,T,E,H] or head_dy = (dy8, hw) as in bptt_coupled; hm [N,T,E,H] view (unit column stride) / msg [N,>=T,E,H]
+    the saved post-relu receiver / sender vectors; ws = (wx, wh, lstm_bptt_wimage(wx, wh)), wm = (w_msg, lstm_bptt_msg_wimage(w_msg)),
+    img_f = lstm_bptt_msg_wimage(mfc_w); rev = reverse_neighbor_table(nbr_idx, COUPLED_NC).  Writes dZ, DS (= d enc), D1, D2
+    ([N,T,E,H] views; slabs past T are not touched) -> (db [N,4H], dbmsg [N,H], dbmfc [N,H], dh0, dc0 [N,E,H] or None).
+    mode 0 / 1 / 2: as in bptt_coupled."""
+    N, T, E, H4 = G.shape
+    H = H4 // 4
+    K = H * m_max
+    if mode == 0 and not handoff_enabled():
+        mode = 2
+    for x, w_, what in ((G, H4, 'gates'), (dZ, H4, 'dz'), (Call, H, 'c_all'), (DS, H, 'ds'), (D1, H, 'd1'), (D2, H, 'd2'), (msg, H, 'msg')) + \
+            (((dHs, H, 'dh_ext'),) if head_dy is None else ()):
+        if x.stride(3) != 1 or x.stride(2) != w_:
+            raise ValueError('bptt_dial: %s must have contiguous rows' % what)
+    if hm.dim() != 4 or hm.stride(3) != 1 or hm.shape[3] != H or msg.shape[1] < T:
+        raise ValueError('bptt_dial: hm must be an [N,T,E,H] view with unit column stride, msg [N,>=T,E,H]')
+    w = _coupled_workspace(G.device, N, E, K, T, dial=True)
+    if _keepalive[0] is not None:
+        _keepalive[0].append(rev)             # dial_bptt_table keeps a bounded number of tables: a captured launch holds this one's addresses
+    a = _lib.BpttDial()
+    a.N, a.T, a.H, a.m_max, a.r_max, a.r_row, a.symmetric, a.mode = N, T, H, m_max, rev['r_max'], rev['r_row'], int(rev['symmetric']), int(mode)
+    a.E = E
+    a.gates, a.gates_sn, a.gates_st = ptr(G, F32, strided=True), G.stride(0), G.stride(1)
+    a.c_all, a.c_sn, a.c_st = ptr(Call, F32, strided=True), Call.stride(0), Call.stride(1)
+    a.done = ptr(done, F32)
+    if head_dy is None:
+        a.dh_ext, a.dh_sn, a.dh_st = ptr(dHs, F32, strided=True), dHs.stride(0), dHs.stride(1)
+    else:
+        dy8, hw = head_dy
+        if dy8.shape != (N, T * E, 8) or not dy8.is_contiguous() or hw.shape[:2] != (N, H) or not hw.is_contiguous():
+            raise ValueError('bptt_dial: head_dy = (dy8 [N,T*E,8], hw [N,64,O]) contiguous')
+        a.dy8, a.dy_sn, a.dy_st = ptr(dy8, F32), dy8.stride(0), E * 8
+        a.hw, a.hw_sn, a.O = ptr(hw, F32), hw.stride(0), hw.shape[2]
+    a.img, a.img_sn = ptr(ws[2], F32), ws[2].stride(0)
+    a.img_m, a.imgm_sn = ptr(wm[1], F32), wm[1].stride(0)
+    a.img_f, a.imgf_sn = ptr(img_f, F32), img_f.stride(0)
+    a.hm, a.hm_sn, a.hm_st, a.hm_row = ptr(hm, F32, strided=True), hm.stride(0), hm.stride(1), hm.stride(2)
+    a.msg, a.msg_sn, a.msg_st = ptr(msg, F32, strided=True), msg.stride(0), msg.stride(1)
+    a.dz, a.dz_sn, a.dz_st = ptr(dZ, F32, strided=True), dZ.stride(0), dZ.stride(1)
+    a.ds, a.ds_sn, a.ds_st = ptr(DS, F32, strided=True), DS.stride(0), DS.stride(1)
+    a.d1, a.d1_sn, a.d1_st = ptr(D1, F32, strided=True), D1.stride(0), D1.stride(1)
+    a.d2, a.d2_sn, a.d2_st = ptr(D2, F32, strided=True), D2.stride(0), D2.stride(1)
+    a.ring, a.ring_sn, a.ring_slot, a.ring_slots = ptr(w['ring'], F32), w['ring'].stride(1), w['ring'].stride(0), w['ring'].shape[0]
+    a.db_part, a.db_sn = ptr(w['db'], F32), w['db'].stride(0)
+    a.dbm_part, a.dbm_sn = ptr(w['dbm'], F32), w['dbm'].stride(0)
+    a.dbf_part, a.dbf_sn = ptr(w['dbf'], F32), w['dbf'].stride(0)
+    a.dhr_io, a.dc_io, a.io_sn = ptr(w['dhr'], F32), ptr(w['dc'], F32), w['dhr'].stride(0)
+    a.ws = ptr(w['ws'], torch.int32)
+    a.status = ptr(handoff_status(G.device), torch.int32)
+    a.rev_agent, a.rev_col, a.rev_w = ptr(rev['rev_agent'], torch.int32), ptr(rev['rev_col'], torch.int32), ptr(rev['rev_w'], F32)
+    check(lib.nmarl_lstm_bptt_dial(C.byref(a), stream()), 'nmarl_lstm_bptt_dial')
+    dh0, dc0 = (w['dhr'].clone(), w['dc'].clone()) if want_state_grad else (None, None)
+    return w['db'].sum(dim=1), w['dbm'].sum(dim=1), w['dbf'].sum(dim=1), dh0, dc0
 
 
 def check_coupled_status(device=None):

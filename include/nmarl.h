@@ -630,6 +630,37 @@ int nmarl_lstm_bptt_msg_wimage(int32_t N, int32_t K, const float* w_msg, int64_t
 int nmarl_lstm_bptt_coupled_ws_words(int64_t E, int32_t N);
 int nmarl_lstm_bptt_coupled(const nmarl_bptt_coupled_t* p, void* stream);
 /*
+ * The reverse recurrence of lstm_dial's update (agents/utils.py:561-593, policies.py:479-525) in ONE launch: per reverse step the
+ * work of nmarl_lstm_bptt_step (KM = 64) + nmarl_dial_msg_adjoint, the message adjoint handed between the agents' blocks inside
+ * the launch by the protocol of nmarl_lstm_bptt_coupled (same ring / ws / status / rev_* / mode / symmetric / ring_slots
+ * semantics; the kernel is that kernel's lstm_dial instantiation):
+ *     dz_t from gates_t, c_{t-1}, dL/dc, dL/dh_t;      [ds_t | dh] = dz_t @ [wx; wh]^T;      d1_t = ds_t * (hm_t > 0)
+ *     dmsg_t[j] = sum over (i, k) with nbr(i, k) == j of (d1_t[i] @ w_msg_i^T)[:, 64 k : 64 k + 64]          (rev_* order)
+ *     d2_t[j]   = dmsg_t[j] * (msg_t[j] > 0);     dL/dh_{t-1}[j] = dh[j] (1 - done_t) + d2_t[j] @ w_mfc_j^T + heads' dL/dh_{t-1}
+ * m_max <= 2 (K = 64 m_max), r_max <= 2, r_row == 2.  hm [N][T][E][..] (row pitch hm_row) / msg [N][>= T][E][64]: the saved
+ * post-relu receiver / sender vectors of step t in slab t.  img, img_m as for nmarl_lstm_bptt_coupled (img of the full [wx; wh]);
+ * img_f = nmarl_lstm_bptt_msg_wimage(K = 64) of w_mfc [N][64][64] (read from global memory: the two other images fill the LDS).
+ * Outputs: dz [N][T][E][4H]; ds, d1, d2 [N][T][E][64] (slab strides *_st: (T + 1)-slab buffers are fine); db_part [N][tiles][4H],
+ * dbm_part / dbf_part [N][tiles][64]: column sums of dz / d1 / d2 per 128-row tile (the three bias gradients = sums over tiles);
+ * dhr_io / dc_io [N][E][64]: scratch, on return the complete dL/d(h, c) of the state the sequence started from.
+ * The heads' gradient: dh_ext or (dy8, hw, O) exactly as in nmarl_bptt_coupled_t.  One-launch form: N * tiles blocks must not exceed
+ * nmarl_handoff_capacity(3, K); otherwise (or mode 2) T + 1 launches of one pass each, same kernel, same results.  As in
+ * nmarl_lstm_bptt_coupled, mode 1 with ring_slots < T also runs step-wise (the one-launch form needs a slot per step).
+ */
+typedef struct nmarl_bptt_dial {
+    int32_t N, T, H, m_max, r_max, r_row, symmetric, mode, ring_slots, O;
+    int64_t E;
+    const float *gates, *c_all, *done, *dh_ext, *dy8, *hw, *img, *img_m, *img_f, *hm, *msg;
+    float *dz, *ds, *d1, *d2, *ring, *db_part, *dbm_part, *dbf_part, *dhr_io, *dc_io;
+    void* ws;
+    int32_t* status;    /* may be NULL: hand-off status words (word 0 <- 1 when a wave gives up) */
+    const int32_t *rev_agent, *rev_col;
+    const float* rev_w;
+    int64_t gates_sn, gates_st, c_sn, c_st, dh_sn, dh_st, dy_sn, dy_st, hw_sn, img_sn, imgm_sn, imgf_sn, hm_sn, hm_st, hm_row, msg_sn,
+        msg_st, dz_sn, dz_st, ds_sn, ds_st, d1_sn, d1_st, d2_sn, d2_st, ring_sn, ring_slot, db_sn, dbm_sn, dbf_sn, io_sn;
+} nmarl_bptt_dial_t;
+int nmarl_lstm_bptt_dial(const nmarl_bptt_dial_t* p, void* stream);
+/*
  * y[n,r,:W] = act(x[n,r,:] + bias[n,:]) for x [N,rows,W] (agent strides in floats, W % 4 == 0);
  * act 0 none / 1 relu / 2 tanh: the bias + activation of `fc` (agents/utils.py:65-73) and of the
  * lstm_comm / lstm_ic3 encoders (agents/utils.py:196-198, 400) after a plain batched GEMM.
@@ -808,11 +839,12 @@ int nmarl_nstep_return(int64_t E, int32_t N, int32_t T, const float* r, const fl
  *   ms += (g*g - ms)*(1-rho);  w -= lr * g / sqrt(ms + eps)
  */
 /*
- * In-launch hand-off (nmarl_lstm_step_x with msg and head kind 3, nmarl_lstm_bptt_coupled one-launch form): blocks wait for flags
+ * In-launch hand-off (nmarl_lstm_step_x with msg and head kind 3, nmarl_lstm_bptt_coupled / nmarl_lstm_bptt_dial one-launch form): blocks wait for flags
  * other blocks of the SAME launch publish, so every block must be co-resident.
  *   nmarl_handoff_capacity(which, K): the number of blocks of that kernel the device holds at once =
  *     hipOccupancyMaxActiveBlocksPerMultiprocessor(kernel, 512 threads, its dynamic LDS) x compute units   (which 1: the
- *     lock-step kernel with a message image of K floats x 64; 2: the coupled BPTT kernel, message rows of K floats);
+ *     lock-step kernel with a message image of K floats x 64; 2: the coupled BPTT kernel, message rows of K floats; 3: its
+ *     lstm_dial instantiations, nmarl_lstm_bptt_dial);
  *     the launchers refuse / fall back to launch-per-step forms above it.  NMARL_TEST_FAKE_CUS=<n> in the environment
  *     replaces the device's compute-unit count (tests: a "smaller GPU").  < 0: error.
  *   status words (int32 x 4, caller-owned, zeroed once): [0] set to 1 -- and left set -- by any hand-off kernel whose wave
