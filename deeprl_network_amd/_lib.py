@@ -191,6 +191,10 @@ SIGNATURES = {
                         _i32, _u64, _i64, _p, _p],
     'nmarl_cacc_step_encode': [C.POINTER(CaccParams), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                _i32, _u64, _i64, _p, C.POINTER(CaccEncode), _p],
+    'nmarl_cacc_step_nv': [C.POINTER(CaccParams), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                           _i32, _u64, _i64, _p, _i32, _p],
+    'nmarl_cacc_reset_nv': [C.POINTER(CaccParams), _i64, _p, _p, _u64, _i64, _p,
+                            _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p],
     'nmarl_grid_reset': [C.POINTER(GridParams), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_grid_step': [C.POINTER(GridParams), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64, _p, _p],
     'nmarl_net_reset': [C.POINTER(NetTopo), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],

@@ -205,6 +205,118 @@ __global__ __launch_bounds__(BLOCK) void cacc_reset_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Platoons of any length 2 <= nv <= 32 (nmarl_cacc_step_nv / nmarl_cacc_reset_nv): one template on the group width GW = the smallest
+// power of two >= nv, five instantiations; a wave steps 64 / GW replicas per tile (cacc_tile_nv, csrc/cacc_tile.h).  As in
+// cacc_step_kernel the inputs of a wave's next two tiles are in flight while it computes (unconditional, clamped loads).
+template <int GW, int BLOCK, int NT, bool COMPACT>
+__global__ __launch_bounds__(BLOCK) void cacc_step_nv_kernel(
+    const nmarl_cacc_params_t p, const int nv, const int64_t E, const uint8_t* __restrict__ action,
+    float* __restrict__ hs, float* __restrict__ vs, float* __restrict__ us,
+    int32_t* __restrict__ ts, uint8_t* __restrict__ coll, float* __restrict__ v0_init,
+    float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
+    float* __restrict__ greward, const int auto_reset, const uint64_t seed,
+    const int64_t env_id_base, int32_t* __restrict__ episode) {
+    constexpr int W = COMPACT ? NF : NOBS;
+    constexpr int REPS = NMARL_WAVE / GW;
+    __shared__ __attribute__((aligned(16))) float lds[BLOCK * W];
+    const int lane = threadIdx.x & (NMARL_WAVE - 1);
+    const int wave = threadIdx.x / NMARL_WAVE;
+    float* lds_wave = lds + wave * NMARL_WAVE * W;
+    const int64_t tiles_total = (E + REPS - 1) / REPS;
+    const int64_t stride = (int64_t)gridDim.x * (BLOCK / NMARL_WAVE);
+    const int rep = lane / GW, a = lane & (GW - 1);
+    const int ac = a < nv ? a : nv - 1;                 // padding lanes mirror the platoon's last vehicle
+
+    int64_t w = (int64_t)blockIdx.x * (BLOCK / NMARL_WAVE) + wave;
+    float h_n = 0.f, v_n = 0.f, v0i_n = 0.f, h_m = 0.f, v_m = 0.f, v0i_m = 0.f;
+    int act_n = 0, t_n = 0, coll_n = 0, act_m = 0, t_m = 0, coll_m = 0;
+#define NMARL_CACC_NV_LOAD(wt, S)                                                          \
+    {                                                                                      \
+        const int64_t wc_ = (wt) < tiles_total ? (wt) : tiles_total - 1;                   \
+        const int64_t er_ = wc_ * REPS + rep;                                              \
+        const int64_t e_ = er_ < E ? er_ : E - 1;                                          \
+        const int64_t g_ = e_ * nv + ac;                                                   \
+        h_##S = hs[g_]; v_##S = vs[g_]; act_##S = action[g_];                              \
+        t_##S = ts[e_]; coll_##S = coll[e_]; v0i_##S = v0_init[e_];                        \
+    }
+    if (w < tiles_total) {
+        NMARL_CACC_NV_LOAD(w, n)
+        NMARL_CACC_NV_LOAD(w + stride, m)
+    }
+    for (; w < tiles_total; w += stride) {
+        float h = h_n, v = v_n;
+        const int act = act_n;
+        const int t = t_n;
+        const bool collided = coll_n != 0;
+        const float v0i = v0i_n;
+        h_n = h_m; v_n = v_m; act_n = act_m; t_n = t_m; coll_n = coll_m; v0i_n = v0i_m;
+        NMARL_CACC_NV_LOAD(w + 2 * stride, m)
+        cacc_tile_nv<GW, NT, COMPACT>(p, nv, E, w, lane, h, v, act, t, collided, v0i, hs, vs, us, ts, coll, v0_init, obs, reward, done,
+                                      greward, auto_reset, seed, env_id_base, episode, lds_wave);
+    }
+#undef NMARL_CACC_NV_LOAD
+}
+
+template <int GW, int BLOCK, bool COMPACT>
+__global__ __launch_bounds__(BLOCK) void cacc_reset_nv_kernel(
+    const nmarl_cacc_params_t p, const int nv, const int64_t E, const uint8_t* __restrict__ mask,
+    const float* __restrict__ u0, const uint64_t seed, const int64_t env_id_base,
+    int32_t* __restrict__ episode, float* __restrict__ hs, float* __restrict__ vs,
+    float* __restrict__ us, int32_t* __restrict__ ts, uint8_t* __restrict__ coll,
+    float* __restrict__ v0_init, float* __restrict__ obs, float* __restrict__ fp, const int A) {
+    constexpr int W = COMPACT ? NF : NOBS;
+    constexpr int REPS = NMARL_WAVE / GW;
+    __shared__ __attribute__((aligned(16))) float lds[BLOCK * W];
+    const int lane = threadIdx.x & (NMARL_WAVE - 1);
+    const int wave = threadIdx.x / NMARL_WAVE;
+    float* lds_wave = lds + wave * NMARL_WAVE * W;
+    const int64_t tiles_total = (E + REPS - 1) / REPS;
+    const int64_t stride = (int64_t)gridDim.x * (BLOCK / NMARL_WAVE);
+    const int rep = lane / GW, a = lane & (GW - 1);
+    const int ac = a < nv ? a : nv - 1;
+
+    for (int64_t w = (int64_t)blockIdx.x * (BLOCK / NMARL_WAVE) + wave; w < tiles_total; w += stride) {
+        const int64_t e_raw = w * REPS + rep;
+        const bool valid = a < nv && e_raw < E;
+        const int64_t e = e_raw < E ? e_raw : E - 1;
+        const int64_t g = e * nv + ac;
+        const bool sel = mask == nullptr || mask[e] != 0;
+
+        float h = hs[g], v = vs[g], u = us[g], v0i = v0_init[e];
+        int t = ts[e];
+        if (sel) {
+            float U;
+            if (u0 != nullptr) {
+                U = u0[e];
+            } else {
+                const int ep = episode[e];
+                U = reset_uniform(seed, env_id_base + e, ep);
+                if (valid && a == 0) episode[e] = ep + 1;
+            }
+            init_state(p, U, a, h, v, v0i);
+            u = 0.0f; t = 0;
+            if (valid) {
+                hs[g] = h; vs[g] = v; us[g] = 0.0f;
+                if (a == 0) { ts[e] = 0; coll[e] = 0; v0_init[e] = v0i; }
+                if (fp != nullptr) {
+                    const float q = 1.0f / (float)A;                    // :184
+                    for (int k = 0; k < A; ++k) fp[g * A + k] = q;
+                }
+            }
+        }
+        const float up_v = __shfl_up(v, 1, GW);
+        const float v_lead = a == 0 ? lead_speed(p, v0i, t) : up_v;
+        const int64_t reps_left = E - w * REPS;
+        const int reps_here = reps_left >= REPS ? REPS : (int)reps_left;
+        // as in cacc_reset_kernel the tile's slab is rewritten as a whole (unselected replicas re-emit their current observation)
+        __builtin_amdgcn_wave_barrier();
+        emit_obs_nv<GW, 0, COMPACT>(p, h, v, u, v_lead, a, nv, rep * nv + (a < nv ? a : 0), lane, lds_wave, obs + w * REPS * nv * W,
+                                    reps_here * nv * W);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Lock-step tail of the batched rollout in ONE launch: the env step AND the next lock-step's input encoders
 // (fc of policies.py:145 / 176-181, w_ob / w_fp of agents/utils.py:186-199) -- the observation the step produces never
 // leaves the CU before it is encoded (it is also written once, compact, for the update).  Saves one launch and the
@@ -331,6 +443,21 @@ inline int pick_grid(int64_t E, int block) {
     return (int)(blocks < cap ? blocks : cap);
 }
 
+inline int pick_grid_nv(int64_t E, int gw, int block) {
+    const int64_t reps = NMARL_WAVE / gw;
+    const int64_t tiles = (E + reps - 1) / reps;
+    const int64_t blocks = (tiles + block / NMARL_WAVE - 1) / (block / NMARL_WAVE);
+    const int64_t cap = NMARL_CACC_GRIDCAP;
+    return (int)(blocks < cap ? blocks : cap);
+}
+
+// the aligned lane group of a platoon: the smallest power of two >= nv (2 <= nv <= 32)
+inline int group_width(int nv) {
+    int g = 2;
+    while (g < nv) g <<= 1;
+    return g;
+}
+
 bool params_ok(const nmarl_cacc_params_t* p) {
     return p != nullptr && p->T > 0 && p->batch_size > 0 && (p->scenario == 0 || p->scenario == 1) &&
            (p->compact_obs == 0 || p->compact_obs == 1) &&
@@ -429,5 +556,79 @@ extern "C" int nmarl_cacc_reset(const nmarl_cacc_params_t* p, int64_t E, const u
     else
         hipLaunchKernelGGL((cacc_reset_kernel<256, false>), dim3(pick_grid(E, 256)), dim3(256), 0, s, *p, E, mask, u0, seed,
                            env_id_base, episode, h, v, u, t, collided, v0_init, obs, fp, A);
+    return nmarl_check_launch();
+}
+
+// nmarl_cacc_step for a platoon of n_vehicle vehicles (2..32).  Small batches are latency bound and cache resident (1-wave blocks,
+// plain stores), large ones stream (non-temporal stores) -- the regimes of nmarl_cacc_step, with the lanes the batch occupies as
+// the threshold.
+extern "C" int nmarl_cacc_step_nv(const nmarl_cacc_params_t* p, int64_t E, const uint8_t* action,
+                                  float* h, float* v, float* u, int32_t* t, uint8_t* collided,
+                                  float* v0_init, float* obs, float* reward, uint8_t* done,
+                                  float* global_reward, int32_t auto_reset, uint64_t seed,
+                                  int64_t env_id_base, int32_t* episode, int32_t n_vehicle, void* stream) {
+    if (!params_ok(p) || n_vehicle < 2 || n_vehicle > 32 || E < 0 ||
+        (E > 0 && (!action || !h || !v || !u || !t || !collided || !v0_init || !obs || !reward || !done || !global_reward)))
+        return NMARL_EINVAL;
+    if (auto_reset && !episode) return NMARL_EINVAL;
+    if (E == 0) return NMARL_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = n_vehicle, gw = group_width(nv);
+    const bool large = E * gw > 256 * 4 * NMARL_WAVE;
+#define NMARL_CACC_NV_LAUNCH(GWV, BLK, NTV, CMP)                                                                                 \
+    hipLaunchKernelGGL((cacc_step_nv_kernel<GWV, BLK, NTV, CMP>), dim3(pick_grid_nv(E, GWV, BLK)), dim3(BLK), 0, s, *p, nv, E, action, h, \
+                       v, u, t, collided, v0_init, obs, reward, done, global_reward, auto_reset, seed, env_id_base, episode)
+#define NMARL_CACC_NV_CASE(GWV)                                                                                                  \
+    case GWV:                                                                                                                    \
+        if (large) {                                                                                                             \
+            if (p->compact_obs) NMARL_CACC_NV_LAUNCH(GWV, NMARL_CACC_BLOCK_LARGE, NMARL_CACC_NT_LARGE, true);                    \
+            else NMARL_CACC_NV_LAUNCH(GWV, NMARL_CACC_BLOCK_LARGE, NMARL_CACC_NT_LARGE, false);                                  \
+        } else {                                                                                                                 \
+            if (p->compact_obs) NMARL_CACC_NV_LAUNCH(GWV, NMARL_CACC_BLOCK_SMALL, NMARL_CACC_NT_SMALL, true);                    \
+            else NMARL_CACC_NV_LAUNCH(GWV, NMARL_CACC_BLOCK_SMALL, NMARL_CACC_NT_SMALL, false);                                  \
+        }                                                                                                                        \
+        break;
+    switch (gw) {
+        NMARL_CACC_NV_CASE(2)
+        NMARL_CACC_NV_CASE(4)
+        NMARL_CACC_NV_CASE(8)
+        NMARL_CACC_NV_CASE(16)
+        NMARL_CACC_NV_CASE(32)
+        default: return NMARL_EINVAL;
+    }
+#undef NMARL_CACC_NV_CASE
+#undef NMARL_CACC_NV_LAUNCH
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_cacc_reset_nv(const nmarl_cacc_params_t* p, int64_t E, const uint8_t* mask,
+                                   const float* u0, uint64_t seed, int64_t env_id_base, int32_t* episode,
+                                   float* h, float* v, float* u, int32_t* t, uint8_t* collided,
+                                   float* v0_init, float* obs, float* fp, int32_t A, int32_t n_vehicle, void* stream) {
+    if (!params_ok(p) || n_vehicle < 2 || n_vehicle > 32 || E < 0 || (E > 0 && (!h || !v || !u || !t || !collided || !v0_init || !obs)))
+        return NMARL_EINVAL;
+    if (!u0 && !episode) return NMARL_EINVAL;
+    if (fp && A <= 0) return NMARL_EINVAL;
+    if (E == 0) return NMARL_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = n_vehicle;
+#define NMARL_CACC_NV_CASE(GWV)                                                                                                  \
+    case GWV:                                                                                                                    \
+        if (p->compact_obs)                                                                                                      \
+            hipLaunchKernelGGL((cacc_reset_nv_kernel<GWV, 256, true>), dim3(pick_grid_nv(E, GWV, 256)), dim3(256), 0, s, *p, nv, E, mask, \
+                               u0, seed, env_id_base, episode, h, v, u, t, collided, v0_init, obs, fp, A);                       \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((cacc_reset_nv_kernel<GWV, 256, false>), dim3(pick_grid_nv(E, GWV, 256)), dim3(256), 0, s, *p, nv, E, mask, \
+                               u0, seed, env_id_base, episode, h, v, u, t, collided, v0_init, obs, fp, A);                       \
+        break;
+    switch (group_width(nv)) {
+        NMARL_CACC_NV_CASE(2)
+        NMARL_CACC_NV_CASE(4)
+        NMARL_CACC_NV_CASE(8)
+        NMARL_CACC_NV_CASE(16)
+        NMARL_CACC_NV_CASE(32)
+        default: return NMARL_EINVAL;
+    }
+#undef NMARL_CACC_NV_CASE
     return nmarl_check_launch();
 }

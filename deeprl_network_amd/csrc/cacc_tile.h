@@ -164,21 +164,32 @@ __device__ __forceinline__ float reset_uniform(uint64_t seed, int64_t env_id, in
 // CACCEnv.step (cacc_env.py:191-242) for this lane's vehicle a of the platoon held by its aligned 8-lane group: new (h, v, u), the
 // sticky collision flag, the per-vehicle reward r and the platoon sum rsum, t + 1, done.  Pure arithmetic + width-8 shuffles; the
 // previous acceleration is only needed by frozen (collided) platoons: `load_u_old` is called for those alone.
-template <class ULoad>
+//
+// GW / PAD / nv: the platoon of nv vehicles sits in an aligned group of GW lanes (GW a power of two >= nv; the callers above the
+// platoon kernels use the defaults GW = nv = 8, PAD = false, whose code is unchanged).  With PAD the lanes a >= nv of a group are
+// PADDING: they run the same instructions on a clamped, in-range copy of a real vehicle's inputs so that the width-GW shuffles
+// stay convergent, contribute +inf to the headway minimum and 0 to the reward sum, and never sit in front of a real lane (vehicle
+// a reads lane a - 1 < nv).  The reward sum is the xor butterfly over the zero-padded group: a FIXED order, deterministic, for
+// GW = nv = 8 NumPy's pairwise tree; for other nv it is not NumPy's order (sequential below 8, eight strided accumulators above).
+// All terms of an un-collided platoon have the same sign, so the two orders differ by at most (nv - 1) * 2^-24 relative
+// (1.8e-6 at nv = 32), inside the per-step rtol 1e-5 of the tests.
+template <int GW = N, bool PAD = false, class ULoad>
 __device__ __forceinline__ void cacc_advance(const nmarl_cacc_params_t& p, const int a, float& h, float& v, const int act, int& t,
                                              bool& collided, const float v0i, float& u_new, float& r, float& rsum_out, bool& is_done_out,
-                                             ULoad load_u_old) {
+                                             ULoad load_u_old, const int nv = GW) {
+    static_assert(GW >= 2 && GW <= 32 && (GW & (GW - 1)) == 0, "a platoon is an aligned power-of-two lane group");
+    const bool pad = PAD && a >= nv;
     const bool frozen = collided;                                   // :193
 
     const float alpha = (act & 1) ? 0.5f : 0.0f;                    // a_map, :275
     const float beta = (act & 2) ? 0.5f : 0.0f;
-    const float up_v = __shfl_up(v, 1, N);
+    const float up_v = __shfl_up(v, 1, GW);
     const float v_lead = a == 0 ? lead_speed(p, v0i, t) : up_v;     // :33-37
     const float u_raw = alpha * (ovm_vh(p, h) - v) + beta * (v_lead - v);   // :385
     float v_next = v + clampf(u_raw, p.u_min, p.u_max) * p.dt;      // :26
     v_next = clampf(v_next, 0.0f, p.v_max);                         // :27
     const float u_c = (v_next - v) / p.dt;                          // :28
-    const float up_vn = __shfl_up(v_next, 1, N);
+    const float up_vn = __shfl_up(v_next, 1, GW);
     const float v_lead_next = a == 0 ? lead_speed(p, v0i, t + 1) : up_vn;
     const float h_next = h + (0.5f * p.dt) * (v_lead + v_lead_next - v - v_next);  // :220
 
@@ -186,10 +197,9 @@ __device__ __forceinline__ void cacc_advance(const nmarl_cacc_params_t& p, const
     else { u_new = load_u_old(); }
 
     // collision test: min over the platoon (:42)
-    float hmin = h;
-    hmin = fminf(hmin, __shfl_xor(hmin, 1, N));
-    hmin = fminf(hmin, __shfl_xor(hmin, 2, N));
-    hmin = fminf(hmin, __shfl_xor(hmin, 4, N));
+    float hmin = pad ? __builtin_inff() : h;
+#pragma unroll
+    for (int m = 1; m < GW; m <<= 1) hmin = fminf(hmin, __shfl_xor(hmin, m, GW));
     if (!frozen && hmin < p.h_min) collided = true;
 
     if (collided) {
@@ -204,10 +214,10 @@ __device__ __forceinline__ void cacc_advance(const nmarl_cacc_params_t& p, const
             r = r + (-5.0f * (c * c));                              // COLLISION_WT, :9
         }
     }
+    if (pad) r = 0.0f;
     float rsum = r;                                                 // np.sum(reward), :229
-    rsum = rsum + __shfl_xor(rsum, 1, N);
-    rsum = rsum + __shfl_xor(rsum, 2, N);
-    rsum = rsum + __shfl_xor(rsum, 4, N);
+#pragma unroll
+    for (int m = 1; m < GW; m <<= 1) rsum = rsum + __shfl_xor(rsum, m, GW);
 
     t += 1;
     is_done_out = (collided && (t % p.batch_size == 0)) || (t == p.T);   // :231-235
@@ -469,6 +479,111 @@ __device__ __forceinline__ void cacc_quad(const nmarl_cacc_params_t& p, const in
             else dst[idx] = val;
         }
     }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Platoons of ANY length 2 <= nv <= 32 (n_vehicle of cacc_env.py:320-343): lane = (replica, vehicle) in an aligned group of GW lanes,
+// GW the smallest power of two >= nv, so a wave64 steps 64 / GW replicas per tile.  HBM stays DENSE -- h, v, u [E][nv], obs [E][nv][W]
+// -- so every consumer is unchanged; only the lanes are padded (cacc_advance<GW, true>).  The arithmetic is cacc_advance /
+// obs_features / init_state, the single definition; GW = nv = 8 gives cacc_tile's results bit for bit (tests/test_gpu_platoon.py).
+
+// The observation of a tile.  With padding lanes the lane index is no longer the output index (emit_obs's assumption), so every
+// real lane writes its row at its DENSE index (replica of the tile * nv + vehicle) into LDS and the wave stores the tile's
+// n_floats contiguous floats with coalesced 4-byte stores (a tile's slab starts at a multiple of nv * W floats: no 16-byte
+// alignment to rely on).  Padding lanes take part in the neighbour shuffles and write nothing.
+template <int GW, int NT, bool COMPACT>
+__device__ __forceinline__ void emit_obs_nv(const nmarl_cacc_params_t& p, float h, float v, float u, float v_lead, const int a,
+                                            const int nv, const int dense, const int lane, float* lds_wave,
+                                            float* __restrict__ obs_tile, const int n_floats) {
+    constexpr int W = COMPACT ? NF : NOBS;
+    float x[NF];
+    obs_features(p, h, v, u, v_lead, x);
+    float* row = lds_wave + dense * W;
+    const bool real = a < nv;
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+        if (real) row[k] = x[k];
+        if (!COMPACT) {
+            const float lo = __shfl_up(x[k], 1, GW);    // vehicle a-1
+            const float hi = __shfl_down(x[k], 1, GW);  // vehicle a+1 (a padding lane's value only where it is discarded below)
+            // slots hold the neighbours in ascending index, left-packed (cacc_env.py:72); nv = 2: one neighbour each, slot 2 zero
+            const float s1 = a == 0 ? hi : lo;
+            const float s2 = (a == 0 || a == nv - 1) ? 0.0f : hi;
+            if (real) { row[NF + k] = s1; row[2 * NF + k] = s2; }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        const int idx = i * NMARL_WAVE + lane;
+        if (idx < n_floats) {
+            if (NT >= 1) __builtin_nontemporal_store(lds_wave[idx], &obs_tile[idx]);
+            else obs_tile[idx] = lds_wave[idx];
+        }
+    }
+}
+
+// One tile = 64 lanes = 64 / GW replicas: cacc_tile for a platoon of nv vehicles.  A lane is REAL where a < nv and VALID where it
+// is real and its replica lies inside the batch; other lanes mirror an in-range vehicle (clamped index) and store nothing.
+template <int GW, int NT, bool COMPACT>
+__device__ __forceinline__ void cacc_tile_nv(const nmarl_cacc_params_t& p, const int nv, const int64_t E, const int64_t w, const int lane,
+                                             float h, float v, const int act, int t, bool collided, float v0i,
+                                             float* __restrict__ hs, float* __restrict__ vs, float* __restrict__ us,
+                                             int32_t* __restrict__ ts, uint8_t* __restrict__ coll, float* __restrict__ v0_init,
+                                             float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
+                                             float* __restrict__ greward, const int auto_reset, const uint64_t seed,
+                                             const int64_t env_id_base, int32_t* __restrict__ episode, float* lds_wave) {
+    constexpr int W = COMPACT ? NF : NOBS;
+    constexpr int REPS = NMARL_WAVE / GW;
+    const int rep = lane / GW, a = lane & (GW - 1);
+    const int64_t e_raw = w * REPS + rep;
+    const bool valid = a < nv && e_raw < E;
+    const int64_t e = e_raw < E ? e_raw : E - 1;
+    const int64_t g = e * nv + (a < nv ? a : nv - 1);
+
+    float u_new, r, rsum;
+    bool is_done;
+    cacc_advance<GW, true>(p, a, h, v, act, t, collided, v0i, u_new, r, rsum, is_done, [&]() { return us[g]; }, nv);
+
+    if (valid) {
+        if (p.per_agent_reward) reward[g] = r;
+        if (a == 0) {
+            if (!p.per_agent_reward) reward[e] = rsum;
+            greward[e] = rsum;
+            done[e] = is_done ? 1 : 0;
+        }
+    }
+
+    if (auto_reset && is_done) {
+        const int ep = episode[e];
+        const float U = reset_uniform(seed, env_id_base + e, ep);
+        init_state(p, U, a, h, v, v0i);
+        u_new = 0.0f; t = 0; collided = false;
+        if (valid && a == 0) episode[e] = ep + 1;
+    }
+
+    if (valid) {
+        if (NT >= 2) {
+            __builtin_nontemporal_store(h, &hs[g]); __builtin_nontemporal_store(v, &vs[g]);
+            __builtin_nontemporal_store(u_new, &us[g]);
+        } else {
+            hs[g] = h; vs[g] = v; us[g] = u_new;
+        }
+        if (a == 0) {
+            ts[e] = t;
+            coll[e] = collided ? 1 : 0;
+            if (auto_reset && is_done) v0_init[e] = v0i;
+        }
+    }
+
+    const float up_v2 = __shfl_up(v, 1, GW);
+    const float v_lead_obs = a == 0 ? lead_speed(p, v0i, t) : up_v2;   // :55, with the new t
+    const int64_t reps_left = E - w * REPS;
+    const int reps_here = reps_left >= REPS ? REPS : (int)reps_left;
+    __builtin_amdgcn_wave_barrier();
+    emit_obs_nv<GW, NT, COMPACT>(p, h, v, u_new, v_lead_obs, a, nv, rep * nv + (a < nv ? a : 0), lane, lds_wave,
+                                 obs + w * REPS * nv * W, reps_here * nv * W);
     __builtin_amdgcn_wave_barrier();
 }
 

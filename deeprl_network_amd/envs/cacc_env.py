@@ -21,6 +21,7 @@ from .. import _lib
 
 N_FEAT = 5
 N_OBS = 15
+N_VEHICLE_MIN, N_VEHICLE_MAX = 2, 32      # a platoon is one aligned power-of-two lane group of a wave (csrc/cacc_tile.h)
 
 
 def _params_from_config(config, train_mode=True):
@@ -59,9 +60,11 @@ def line_graph(n):
 class CACCBatchEnv:
     """E independent platoons stepped in lock-step on one GPU.
 
-    State (HBM, fp32 SoA): h, v, u [E,8]; t [E] i32; collided [E] u8;
-    v0_init [E]; observation slab obs [E,8,15] (own + 2 neighbour slots).
+    N = n_vehicle of the ini (cacc_env.py:320-343), 2 <= N <= 32.  State (HBM, fp32 SoA, dense): h, v, u [E,N]; t [E] i32;
+    collided [E] u8; v0_init [E]; observation slab obs [E,N,15] (own + 2 neighbour slots).
     `env_id_base` makes Philox streams global across data-parallel ranks.
+    N = 8 runs nmarl_cacc_step / nmarl_cacc_reset (and the forms fused with the policy's launches); every other length runs
+    nmarl_cacc_step_nv / nmarl_cacc_reset_nv: one env launch per lock-step, not folded into the policy's.
     """
 
     def __init__(self, config, num_envs=1, device='cuda', env_id_base=0, seed=None):
@@ -72,8 +75,12 @@ class CACCBatchEnv:
             raise _lib.NmarlError('CACCBatchEnv needs a HIP device; there is no CPU path')
         self.params, self.name = _params_from_config(config)
         self.n_agent = config.getint('n_vehicle')
-        if self.n_agent != 8:
-            raise _lib.NmarlError('the gfx950 CACC kernel maps one platoon to an 8-lane group: n_vehicle must be 8')
+        if not N_VEHICLE_MIN <= self.n_agent <= N_VEHICLE_MAX:
+            raise _lib.NmarlError('the gfx950 CACC kernels hold one platoon in a lane group of a wave: n_vehicle must be %d..%d (got %d)'
+                                  % (N_VEHICLE_MIN, N_VEHICLE_MAX, self.n_agent))
+        # the env step fused with the next lock-step's encoders (nmarl_cacc_step_encode) and the one inside the lock-step launch
+        # exist for 8 vehicles only
+        self.supports_fused_encode = self.n_agent == 8
         self.agent = config.get('agent')
         self.coop_gamma = config.getfloat('coop_gamma')
         self.T = self.params.T
@@ -109,8 +116,8 @@ class CACCBatchEnv:
     compact_obs = False
 
     def set_compact_obs(self, flag=True):
-        """Compact observation [E,8,5] (each vehicle's own features, SURVEY.md 8d's 347-B layout) instead of the
-        pre-gathered [E,8,15]: the consumer gathers the neighbours (agents/policies.py `_ob_part`).  Batched engine only
+        """Compact observation [E,N,5] (each vehicle's own features, SURVEY.md 8d's 347-B layout) instead of the
+        pre-gathered [E,N,15]: the consumer gathers the neighbours (agents/policies.py `_ob_part`).  Batched engine only
         (the E = 1 reference duck-type keeps the reference's concatenated observations)."""
         self.compact_obs = bool(flag)
         self.params.compact_obs = 1 if flag else 0
@@ -131,6 +138,14 @@ class CACCBatchEnv:
         the initial-condition uniforms (legacy / test seeds); otherwise they come
         from Philox(seed, env_id, episode) inside the kernel."""
         P = _lib.ptr
+        if self.n_agent != 8:
+            self._check_obs(self.obs)
+            rc = _lib.lib.nmarl_cacc_reset_nv(
+                ctypes.byref(self.params), self.E, P(mask, torch.uint8), P(u0, torch.float32),
+                self.seed, self.env_id_base, P(self.episode), P(self.h), P(self.v), P(self.u), P(self.t),
+                P(self.collided), P(self.v0_init), P(self.obs), P(self.fp), self.n_a, self.n_agent, _lib.stream())
+            _lib.check(rc, 'nmarl_cacc_reset_nv')
+            return self.obs
         rc = _lib.lib.nmarl_cacc_reset(
             ctypes.byref(self.params), self.E, P(mask, torch.uint8), P(u0, torch.float32),
             self.seed, self.env_id_base, P(self.episode), P(self.h), P(self.v), P(self.u), P(self.t),
@@ -138,11 +153,18 @@ class CACCBatchEnv:
         _lib.check(rc, 'nmarl_cacc_reset')
         return self.obs
 
-    supports_fused_encode = True
+    def _check_obs(self, obs):
+        """The observation buffer handed to the any-length kernels is the one `params.compact_obs` describes."""
+        want = (self.E, self.n_agent, N_FEAT if self.params.compact_obs else N_OBS)
+        if tuple(obs.shape) != want:
+            raise _lib.NmarlError('observation buffer %s, but compact_obs = %d describes %s'
+                                  % (tuple(obs.shape), self.params.compact_obs, want))
 
     def inkernel_step(self, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
         """Arguments of `step` for the policy's lock-step launch to run the env step itself behind its action draw
         (csrc/lstm_mfma.hip ENV: ops.step_enc_spec(env=...)): same state tensors, same outputs, the actions are the launch's own."""
+        if self.n_agent != 8:
+            raise _lib.NmarlError('the env step inside the lock-step launch exists for n_vehicle = 8 only (its action word holds 8 agents)')
         if not self.compact_obs:
             raise _lib.NmarlError('the in-launch env step writes the compact observation')
         return dict(params=self.params, h=self.h, v=self.v, u=self.u, t=self.t, collided=self.collided, v0_init=self.v0_init,
@@ -152,16 +174,29 @@ class CACCBatchEnv:
                     seed=self.seed, env_id_base=self.env_id_base, episode=self.episode)
 
     def step(self, action, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None, encode=None):
-        """action [E,8] uint8 -> (obs [E,8,15], reward [E]|[E,8], done [E] u8, global_reward [E]).
+        """action [E,N] uint8 -> (obs [E,N,15], reward [E]|[E,N], done [E] u8, global_reward [E]).
         By default the results land in this env's persistent buffers (overwritten every step); the
         `*_out` tensors redirect them, e.g. straight into slot t of the trainer's rollout buffers.
         encode (compact observation only): dict(w_ob, b_ob[, w_fp, b_fp, fp], nbr_idx, out, act) -- the NEXT lock-step's input
-        encoders run in the same launch on the observation this step produces (nmarl_cacc_step_encode)."""
+        encoders run in the same launch on the observation this step produces (nmarl_cacc_step_encode; n_vehicle = 8 only)."""
         P = _lib.ptr
         obs = self.obs if obs_out is None else obs_out
         reward = self.reward if reward_out is None else reward_out
         done = self.done if done_out is None else done_out
         greward = self.global_reward if greward_out is None else greward_out
+        if self.n_agent != 8:
+            if encode is not None:
+                raise _lib.NmarlError('the env step fused with the encoders exists for n_vehicle = 8 only')
+            self._check_obs(obs)
+            if tuple(action.shape) != (self.E, self.n_agent) or tuple(reward.shape) != tuple(self.reward.shape):
+                raise _lib.NmarlError('action must be [E,%d] and reward %s' % (self.n_agent, tuple(self.reward.shape)))
+            rc = _lib.lib.nmarl_cacc_step_nv(
+                ctypes.byref(self.params), self.E, P(action, torch.uint8), P(self.h), P(self.v), P(self.u),
+                P(self.t), P(self.collided), P(self.v0_init), P(obs, torch.float32), P(reward, torch.float32),
+                P(done, torch.uint8), P(greward, torch.float32), 1 if auto_reset else 0, self.seed,
+                self.env_id_base, P(self.episode), self.n_agent, _lib.stream())
+            _lib.check(rc, 'nmarl_cacc_step_nv')
+            return obs, reward, done, greward
         if encode is not None:
             en = _lib.CaccEncode()
             S = P
@@ -252,7 +287,7 @@ class CACCEnv:
         return
 
     def _state_list(self):
-        x = self.batch.obs[0].cpu().numpy().astype(np.float64)   # [8,15]
+        x = self.batch.obs[0].cpu().numpy().astype(np.float64)   # [N,15]
         fp = np.asarray(self.fp)
         out = []
         for i in range(self.n_agent):

@@ -140,6 +140,30 @@ int nmarl_cacc_step_encode(const nmarl_cacc_params_t* p, int64_t E, const uint8_
                            float* global_reward, int32_t auto_reset, uint64_t seed,
                            int64_t env_id_base, int32_t* episode, const nmarl_cacc_encode_t* enc, void* stream);
 
+/*
+ * nmarl_cacc_step / nmarl_cacc_reset for a platoon of ANY length: n_vehicle (cacc_env.py:320-343, an ordinary ENV_CONFIG key;
+ * masks of :253-268, _get_accel :31-38 and _get_state :67-79 are written for any n_agent), 2 <= n_vehicle <= 32.  Every array
+ * that is [E,8,..] above is DENSE [E,n_vehicle,..] here (h, v, u, action, per-agent reward [E,n_vehicle], obs [E,n_vehicle,5] or
+ * [E,n_vehicle,15], fp [E,n_vehicle,A]); the per-replica arrays, the Philox contract and the fused auto-reset are unchanged.
+ * Vehicle 0 follows the leader profile, vehicle n_vehicle-1 has one neighbour; the gathered observation left-packs the
+ * neighbours in ascending index (:72), so with n_vehicle = 2 the third slot is zero for both vehicles.  The platoon's reward
+ * sum (:229) is a fixed-order tree over the platoon zero-padded to the next power of two: deterministic, NumPy's own order at
+ * n_vehicle = 8, within (n_vehicle - 1) * 2^-24 relative of it otherwise.  At n_vehicle = 8 every output equals
+ * nmarl_cacc_step / nmarl_cacc_reset bit for bit.
+ * NMARL_EINVAL (nothing is launched): n_vehicle outside 2..32, a NULL array, p->compact_obs not 0 / 1 (the caller's obs buffer
+ * must be the one p->compact_obs describes: [E,n_vehicle,5] if 1, [E,n_vehicle,15] if 0).
+ */
+int nmarl_cacc_step_nv(const nmarl_cacc_params_t* p, int64_t E, const uint8_t* action,
+                       float* h, float* v, float* u, int32_t* t, uint8_t* collided,
+                       float* v0_init, float* obs, float* reward, uint8_t* done,
+                       float* global_reward, int32_t auto_reset, uint64_t seed,
+                       int64_t env_id_base, int32_t* episode, int32_t n_vehicle, void* stream);
+int nmarl_cacc_reset_nv(const nmarl_cacc_params_t* p, int64_t E,
+                        const uint8_t* mask, const float* u0,
+                        uint64_t seed, int64_t env_id_base, int32_t* episode,
+                        float* h, float* v, float* u, int32_t* t, uint8_t* collided,
+                        float* v0_init, float* obs, float* fp, int32_t A, int32_t n_vehicle, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Synthetic (SUMO-free) 5x5 ATSC grid -- contract of envs/atsc_env.py +      */
 /* envs/large_grid_env.py; dynamics specified in oracle/grid_ref.py           */
