@@ -30,7 +30,7 @@ if _build.built_hash() != _build.source_hash():
 LIB_PATH = os.environ.get('NMARL_LIB_AB') or LIB_PATH
 lib = C.CDLL(LIB_PATH)
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class CaccParams(C.Structure):
@@ -74,7 +74,7 @@ class StepEnc(C.Structure):
                 ('w_ob', C.c_void_p), ('b_ob', C.c_void_p), ('w_fp', C.c_void_p), ('b_fp', C.c_void_p),
                 ('w_ob_sn', C.c_int64), ('b_ob_sn', C.c_int64), ('w_fp_sn', C.c_int64), ('b_fp_sn', C.c_int64),
                 ('out', C.c_void_p), ('out_sn', C.c_int64), ('out_row', C.c_int64),
-                ('F', C.c_int32), ('A', C.c_int32), ('m_max', C.c_int32), ('pad_', C.c_int32), ('nbr', C.c_int32 * 64),
+                ('F', C.c_int32), ('A', C.c_int32), ('m_max', C.c_int32), ('pad_', C.c_int32), ('nbr', C.c_int32 * 128),
                 ('env', C.POINTER(CaccParams)), ('h', C.c_void_p), ('v', C.c_void_p), ('u', C.c_void_p), ('t', C.c_void_p),
                 ('collided', C.c_void_p), ('v0_init', C.c_void_p), ('obs_out', C.c_void_p), ('reward', C.c_void_p),
                 ('done', C.c_void_p), ('global_reward', C.c_void_p), ('auto_reset', C.c_int32), ('pad2_', C.c_int32),

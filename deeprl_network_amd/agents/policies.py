@@ -758,12 +758,14 @@ class LstmPolicy(BatchedPolicy):
     enc_writes_bits = False       # (the 16-byte sign image belongs to the two-layer encodings: FPPolicy, NCMultiAgentPolicy)
 
     def enc_in_kernel(self, E, compact):
-        """IA2C / ConseNet on CACC (round 6): the policy + value launch runs the observation encoder itself (csrc/lstm_mfma.hip ENC 2)."""
+        """IA2C / ConseNet: the policy + value launch runs the observation encoder itself (csrc/lstm_mfma.hip ENC 2 on the CACC input
+        layout, ENC 4 on the general one: the ATSC grid's 12 features x (1 + 4 neighbours))."""
         m_enc = self.m_max if self.params['fc_w'].shape[1] == self.n_obs else 0       # ConseNet: own features only
         return bool(compact) and self.xside and self.fused_pv and not self.hetero and \
             ops.step_enc1_supported(self.n_feat, m_enc, self.n_fc, self.n_h, self.N)
 
     def _enc_spec(self, x, fp, out, env=None, bits=None):
+        # self.nbrs: the SLAB's slot order (ascending) -- the weight rows follow it whatever order the env concatenates in (`_L_slots`)
         p = self.params
         return ops.step_enc_spec(x, fp, p['fc_w'], p['fc_b'], None, None, self.nbrs, out=out, env=env, bits=None)
 
@@ -812,10 +814,13 @@ class FPPolicy(LstmPolicy):
         return self._fused_spec(('fcs_w', 'fcs_b'), ('fcp_w', 'fcp_b'), fp_next, out) if self.xside else None
 
     def enc_in_kernel(self, E, compact):
+        """IA2C-FP: both input encoders inside the policy + value launch (csrc/lstm_mfma.hip ENC 1 on the CACC input layout, ENC 3
+        on the general one: the ATSC grid's 60 observation and 20 fingerprint inputs)."""
         return bool(compact) and self.xside and self.fused_pv and not self.hetero and \
             ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, self.n_fc, self.n_h, self.N)
 
     def _enc_spec(self, x, fp, out, env=None, bits=None):
+        # self.nbrs: the slab's slot order, which the rows of fcs_w AND fcp_w follow (`_L_slots`, `_L_fp_obs`)
         p = self.params
         return ops.step_enc_spec(x, fp, p['fcs_w'], p['fcs_b'], p['fcp_w'], p['fcp_b'], self.nbrs, out=out, env=env, bits=bits)
 
@@ -892,6 +897,7 @@ class NCMultiAgentPolicy(BatchedPolicy):
         """The one-launch lock-step also runs the two input encoders (and, for the batched CACC engine, the env step): ONE launch per
         lock-step (csrc/lstm_mfma.hip <4,1,1>).  NMARL_NC_ONE_LAUNCH=0: the encoders stay behind the env kernel (nmarl_cacc_step_encode)."""
         return bool(compact) and self.xside and not self.hetero and self.pv_one_launch(E) and \
+            ops.step_enc_cacc_layout(self.n_feat) and \
             ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, self.n_fc, self.n_h, self.N) and \
             os.environ.get('NMARL_NC_ONE_LAUNCH', '1') != '0'
 

@@ -466,7 +466,7 @@ bool params_ok(const nmarl_cacc_params_t* p) {
 
 }  // namespace
 
-extern "C" int nmarl_abi_version(void) { return 3; }
+extern "C" int nmarl_abi_version(void) { return 4; }
 
 #ifndef NMARL_SRC_HASH_STR
 #define NMARL_SRC_HASH_STR "NMARL_SRC_HASH=unknown"

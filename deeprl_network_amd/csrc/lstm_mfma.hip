@@ -287,6 +287,10 @@ struct XArgs {
     unsigned* e_bits; int64_t e_bits_sn;          // [N][E][4] words: which of the 128 encoder outputs are > 0 (nmarl_step_enc_t.relu_bits; may be NULL)
     int e_nbr[64];                                // neighbour table [N][2] (-1 padded) BY VALUE: no dependent table load
     int e_ob_rows;                                // rows of w_ob: 15 = 5 x (1 + 2 slots), or 5 (own features only: m_max = 0)
+    // ENC 3 / 4 (the encoders on a GENERAL input layout: F own features x (1 + m_max <= 4) slots, A fingerprint entries x m_max; the ATSC
+    // grid: 12 x 5 and 5 x 4) take their layout through the SAME words -- the argument block, and with it every other form's code, stays
+    // as it was: e_nbr[n] = agent n's four neighbours, one signed byte each (-1: absent; N <= 32); e_ob_rows = rows of w_ob | rows of
+    // w_fp << 8 | A << 16; F = ob_F
     // ENC 1 + ev_on: the CACC env step of THIS lock-step behind the action draw (see the ENV block at the end of the kernel)
     int ev_on, ev_auto_reset;
     nmarl_cacc_params_t ev_p;
@@ -486,7 +490,15 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     const int64_t e_ob_row = xa.e_ob_row, e_fp_sn = xa.e_fp_sn, e_wob_sn = xa.e_wob_sn, e_bob_sn = xa.e_bob_sn, e_wfp_sn = xa.e_wfp_sn,
                   e_bfp_sn = xa.e_bfp_sn, e_out_sn = xa.e_out_sn, e_out_row = xa.e_out_row;
     int e_nb0 = -1, e_nb1 = -1;
-    if (ENC) {
+    int e_nb2 = -1, e_nb3 = -1;                  // ENC 3 / 4: up to four neighbour slots
+    if (ENC >= 3) {
+        const int ns_ = __builtin_amdgcn_readfirstlane(n);
+        const int nb4_ = xa.e_nbr[ns_];                              // four signed bytes
+        e_nb0 = (nb4_ << 24) >> 24; e_nb1 = (nb4_ << 16) >> 24; e_nb2 = (nb4_ << 8) >> 24; e_nb3 = nb4_ >> 24;
+        asm volatile("" :: "s"(e_ob), "s"(e_fp), "s"(e_wob), "s"(e_bob), "s"(e_wfp), "s"(e_bfp), "s"(e_out), "s"(e_ob_row), "s"(e_fp_sn),
+                     "s"(e_wob_sn), "s"(e_bob_sn), "s"(e_wfp_sn), "s"(e_bfp_sn), "s"(e_out_sn), "s"(e_out_row), "s"(e_nb0), "s"(e_nb1), "s"(e_nb2),
+                     "s"(e_nb3), "s"(e_bits), "s"(e_bits_sn));
+    } else if (ENC) {
         const int ns_ = __builtin_amdgcn_readfirstlane(n);
         e_nb0 = xa.e_nbr[2 * ns_]; e_nb1 = xa.e_nbr[2 * ns_ + 1];
         asm volatile("" :: "s"(e_ob), "s"(e_fp), "s"(e_wob), "s"(e_bob), "s"(e_wfp), "s"(e_bfp), "s"(e_out), "s"(e_ob_row), "s"(e_fp_sn),
@@ -530,9 +542,12 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     constexpr bool DEPH = MSG == 0 && ENC == 0;
     constexpr int NBUF = DEPH ? 3 : 2;
     static_assert(ENC == 0 || (MSG == 0 && HEAD == 3) || (ENC == 1 && MSG == 1 && HEAD == 4), "ENC: the policy + value launch of IA2C(-FP) / ConseNet / NeurComm");
+    static_assert(ENC >= 0 && ENC <= 4 && (ENC < 3 || PREC == 0), "ENC 3 / 4 (general input layout): fp32 only");
     // ENC 1: two encoders [relu(x~ W_ob + b) | relu(p~ W_fp + b)] (128 outputs: IA2C-FP, NeurComm); ENC 2 (round 6): the observation
     // encoder alone (64 outputs: IA2C policies.py:145; ConseNet policies.py:381-390 with its own features only = no neighbour slots)
-    constexpr bool EFP = ENC == 1;
+    // ENC 3 / 4: the same two forms on a GENERAL input layout (EGEN, see the pre-phase behind the prologue's barrier)
+    constexpr bool EFP = ENC == 1 || ENC == 3;
+    constexpr bool EGEN = ENC >= 3;
     constexpr int EMT = EFP ? 8 : 4;                      // 16-column m-tiles of the encoders' output
     // Where the encoders' 128 outputs wait for the K loop: ENC_LDS (uncoupled nets) in lane-private LDS slots; ENC_GLB (NeurComm: the
     // message image and the parked cell state leave no 64 KB of LDS) in the S slot of the saved activations itself -- every lane
@@ -614,10 +629,64 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     if (MSG == 0 && ENC == 0) { NMARL_A_LOAD(0, a0, a1) }
     // ---- ENC: the input encoders' operands (see the kernel's header), REQUESTED here -- behind the two weight chunks, in front of
     // everything else the prologue asks for -- and consumed just before the prologue's barrier
-    float ein[ENC == 1 ? 6 : (ENC ? 4 : 1)];
-    float ewt[ENC == 1 ? 3 : (ENC ? 2 : 1)];
-    f32x4 eacc[ENC == 1 ? 8 : (ENC ? 4 : 1)];
-    if (ENC) {
+    float ein[ENC == 3 ? 24 : ENC == 4 ? 16 : ENC == 1 ? 6 : (ENC ? 4 : 1)];
+    float ewt[ENC == 3 ? 12 : ENC == 4 ? 8 : ENC == 1 ? 3 : (ENC ? 2 : 1)];
+    f32x4 eacc[EFP ? 8 : (ENC ? 4 : 1)];
+    if constexpr (EGEN) {
+        // ---- ENC 3 / 4: F own features x (1 + m_max) observation slots (k-steps 0 .. obk - 1: F is a multiple of 4, so a k-step's four
+        // inputs are features f0 .. f0 + 3 of ONE slot, whose agent is uniform; lane group grp = the feature) and A fingerprint entries
+        // x m_max neighbours (k-steps 0 .. fpk - 1 of the second product: input 4 s + grp = entry (4 s + grp) % A of slot (4 s + grp) / A,
+        // per lane).  Slot k + 1 is neighbour k of the by-value table; an absent slot contributes 0 (its address falls back to the
+        // agent's own first entries: always inside the tensors).  Inputs in their natural order = the weight rows' order.
+        __builtin_amdgcn_sched_barrier(0);                                // (the chunk loads above stay first)
+        const int ns = __builtin_amdgcn_readfirstlane(n);
+        const int F = xa.ob_F, A = (xa.e_ob_rows >> 16) & 255, fp_rows = (xa.e_ob_rows >> 8) & 255;
+        const int obk = (xa.e_ob_rows & 255) >> 2, fpk = (fp_rows + 3) >> 2;  // k-steps of the two products: <= 16, <= 8
+        {
+            const float* obr = e_ob + arow * e_ob_row + grp;
+            int slot = 0, f0 = 0;
+#pragma unroll
+            for (int s_ = 0; s_ < 16; ++s_) {
+                int ag = ns;
+                ag = slot == 1 ? e_nb0 : ag; ag = slot == 2 ? e_nb1 : ag; ag = slot == 3 ? e_nb2 : ag; ag = slot == 4 ? e_nb3 : ag;
+                const bool ok = s_ < obk && ag >= 0;
+                const float v = obr[ok ? ag * F + f0 : ns * F];
+                ein[s_] = ok ? v : 0.0f;
+                f0 += 4;
+                if (f0 >= F) { f0 = 0; ++slot; }
+            }
+            if constexpr (EFP) {
+#pragma unroll
+                for (int s_ = 0; s_ < 8; ++s_) {
+                    const int kk = 4 * s_ + grp;
+                    const int sl = (kk >= A ? 1 : 0) + (kk >= 2 * A ? 1 : 0) + (kk >= 3 * A ? 1 : 0);
+                    int ag = e_nb0;
+                    ag = sl == 1 ? e_nb1 : ag; ag = sl == 2 ? e_nb2 : ag; ag = sl == 3 ? e_nb3 : ag;
+                    const bool ok = s_ < fpk && kk < fp_rows && ag >= 0;
+                    const float v = e_fp[(int64_t)(ok ? ag : ns) * e_fp_sn + arow * A + (ok ? kk - sl * A : 0)];
+                    ein[16 + s_] = ok ? v : 0.0f;
+                }
+            }
+        }
+        // W -> LDS image [k-step s][lane][m-tile] (the order the lanes read it back in: one ds_read_b128 per k-step), the observation
+        // encoder's 16 k-steps first, the fingerprint encoder's 8 behind them.  Rows past the tensors' last (the fingerprint product's
+        // last k-step when A m_max is no multiple of 4) are clamped to it: their input is 0.  A wave fetches one whole 256-byte row.
+#pragma unroll
+        for (int q = 0; q < (EFP ? 12 : 8); ++q) {
+            const int e = (q < 8 ? q : q - 8) * 512 + (int)threadIdx.x;
+            const int s_ = e >> 8, l_ = (e >> 2) & 63, mt_ = e & 3, g_ = l_ >> 4, i_ = l_ & 15;
+            const bool live = s_ < (q < 8 ? obk : fpk);
+            int row = 4 * s_ + g_;
+            row = q < 8 ? row : (row < fp_rows ? row : fp_rows - 1);
+            const float* src = q < 8 ? e_wob + (int64_t)n * e_wob_sn : e_wfp + (int64_t)n * e_wfp_sn;
+            ewt[q] = src[(live ? row : 0) * H + 16 * mt_ + i_];
+        }
+        float4 eb4 = float4{0.f, 0.f, 0.f, 0.f};
+        if (threadIdx.x < (EFP ? 32 : 16))
+            eb4 = *reinterpret_cast<const float4*>((threadIdx.x < 16 ? e_bob + (int64_t)n * e_bob_sn : e_bfp + (int64_t)n * e_bfp_sn - H) + 4 * threadIdx.x);
+        eacc[0] = f32x4{eb4.x, eb4.y, eb4.z, eb4.w};                     // (parked in eacc[0] until it is stored to LDS)
+        __builtin_amdgcn_sched_barrier(0);
+    } else if (ENC) {
         __builtin_amdgcn_sched_barrier(0);                                // (the chunk loads above stay first)
         const int i16 = lane & 15;
         const int ns = __builtin_amdgcn_readfirstlane(n);                // uniform; the table entries came as scalar loads from the
@@ -863,7 +932,14 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     // ENC: [6][64][4] W image + [128] biases -- behind the x slots; ENC_GLB: over the parked-cell-state slots behind the W_msg image
     // (6.5 of their 8 KB; the slots are first written after the message pre-phase, a block barrier behind the image's last read)
     float* e_lds = ENC_GLB ? m_lds + xa.msg_kc * (CH_K * 64) : hw_lds + HW_FLOATS + 8 * 512 * 4;
-    if (ENC) {
+    // ENC 3 / 4: the W image (16 + 8 KB) borrows the x-slot region -- the slots are first written behind the pre-phase's own barrier,
+    // when every wave has read its operands from the image; the biases sit behind the slots like the CACC forms'
+    float* g_lds = hw_lds + HW_FLOATS;
+    if constexpr (EGEN) {
+#pragma unroll
+        for (int q = 0; q < (EFP ? 12 : 8); ++q) g_lds[q * 512 + threadIdx.x] = ewt[q];
+        if (threadIdx.x < (EFP ? 32 : 16)) *reinterpret_cast<float4*>(e_lds + 1536 + 4 * threadIdx.x) = float4{eacc[0][0], eacc[0][1], eacc[0][2], eacc[0][3]};
+    } else if (ENC) {
         NMARL_STAMP(37)
 #pragma unroll
         for (int q = 0; q < (EFP ? 3 : 2); ++q) e_lds[q * 512 + threadIdx.x] = ewt[q];
@@ -877,6 +953,43 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
         // ---- ENC: operands from LDS, 24 MFMAs (k-step outer: four independent accumulators between two dependent ones), relu, park
         // in the lane's LDS slots, save for the update
         const int i16 = lane & 15;
+        if constexpr (EGEN) {
+            // ---- ENC 3 / 4: up to 16 + 8 k-steps, the k-step's weights from the borrowed x-slot region (uniform trip counts)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const float4 b0 = *reinterpret_cast<const float4*>(e_lds + 1536 + 16 * mt + 4 * grp);
+                eacc[mt] = f32x4{b0.x, b0.y, b0.z, b0.w};
+                if constexpr (EFP) {
+                    const float4 b1 = *reinterpret_cast<const float4*>(e_lds + 1536 + H + 16 * mt + 4 * grp);
+                    eacc[4 + mt] = f32x4{b1.x, b1.y, b1.z, b1.w};
+                }
+            }
+            const float4* gi_ = reinterpret_cast<const float4*>(g_lds) + lane;
+            const int obk = (xa.e_ob_rows & 255) >> 2, fpk = (((xa.e_ob_rows >> 8) & 255) + 3) >> 2;
+#pragma unroll
+            for (int s_ = 0; s_ < 16; ++s_) {
+                if (s_ < obk) {
+                    const float4 w_ = gi_[s_ * 64];
+                    eacc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.x, ein[s_], eacc[0], 0, 0, 0);
+                    eacc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.y, ein[s_], eacc[1], 0, 0, 0);
+                    eacc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.z, ein[s_], eacc[2], 0, 0, 0);
+                    eacc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.w, ein[s_], eacc[3], 0, 0, 0);
+                }
+            }
+            if constexpr (EFP) {
+#pragma unroll
+                for (int s_ = 0; s_ < 8; ++s_) {
+                    if (s_ < fpk) {
+                        const float4 w_ = gi_[(16 + s_) * 64];
+                        eacc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.x, ein[16 + s_], eacc[4], 0, 0, 0);
+                        eacc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.y, ein[16 + s_], eacc[5], 0, 0, 0);
+                        eacc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.z, ein[16 + s_], eacc[6], 0, 0, 0);
+                        eacc[7] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_.w, ein[16 + s_], eacc[7], 0, 0, 0);
+                    }
+                }
+            }
+            __syncthreads();                 // every wave has read the image: its LDS becomes the lane-private x slots
+        } else {
         float4 w4[EFP ? 6 : 4];
 #pragma unroll
         for (int s_ = 0; s_ < (EFP ? 6 : 4); ++s_) w4[s_] = reinterpret_cast<const float4*>(e_lds)[s_ * 64 + lane];
@@ -903,6 +1016,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
             eacc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[s_].y, ein[s_], eacc[5], 0, 0, 0);
             eacc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[s_].z, ein[s_], eacc[6], 0, 0, 0);
             eacc[7] = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[s_].w, ein[s_], eacc[7], 0, 0, 0);
+        }
         }
         NMARL_STAMP(50)
         unsigned pos = 0;                    // bit 4 mt + i: output 16 mt + 4 grp + i of row c is > 0 (the relu derivative the update needs)
@@ -1240,7 +1354,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
             __hip_atomic_fetch_add((gu64*)xa.gv_words + 2 * (row0 + lane) + hi_,
                                    ((unsigned long long)act_l << (3 * (n - 13 * hi_))) | (1ull << 59), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (ENC && xa.ev_on) {
+        if (ENC && !EGEN && xa.ev_on) {
             // ---- ENV (1/2): every drawn action goes into its replica's hand-off word by ONE atomic add -- 2 bits of payload per agent
             // + an arrival count above them -- whose return value is looked at after the value re-step (which hides the trip): the
             // lane that finds N - 1 earlier arrivals holds all N actions of that replica.  The strip's env state (16 replicas x 8
@@ -1401,7 +1515,7 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
         NMARL_STAMP(24)
         head_epilogue<3>(a, n, xa.N, row0, lane, a_tile, hw_lds + H * MAXA + MAXA);
         NMARL_STAMP(25)
-        if (ENC && xa.ev_on) {
+        if (ENC && !EGEN && xa.ev_on) {
             // ---- ENV (2/2): envs/cacc_env.py:191-242 for the replicas whose LAST arrival this wave was (on average 2 of its 16).
             // The word's return value carries the other agents' draws, so nothing is read back and no wave ever waits for
             // another: no co-residency requirement, no failure mode, no memory-ordering argument beyond the atomic itself.  The
@@ -1752,6 +1866,54 @@ extern "C" int nmarl_lstm_step_x(const nmarl_step_x_t* s, void* stream) {
         lds_once.done(lds_bit);
     }
     dim3 grid(a.blocks_per_agent * N);
+    if (enc && enc->F != 5) {
+        // the input encoders on a GENERAL input layout (ENC 3: both, ENC 4: the observation encoder alone): F own features (a multiple
+        // of 4) x (1 + m_max) observation slots <= 64 inputs, A <= 8 fingerprint entries x m_max neighbours <= 32 inputs, m_max <= 4;
+        // the uncoupled nets' policy + value step, fp32, no env step inside (the ATSC grid: F = 12, m_max = 4, A = 5)
+        const bool single = !enc->w_fp;
+        const int F = enc->F, A = enc->A, mm = enc->m_max;
+        if (mk != 0 || prec || enc->env || F <= 0 || (F % 4) || mm < 0 || mm > 4 || F * (1 + mm) > H || N > 32 ||
+            KX != (single ? H : 2 * H) || KX2 != 0 || zadd1 || zadd2 ||
+            (!single && (A <= 0 || A > MAXA || mm < 1 || A * mm > 32)))
+            return NMARL_EINVAL;
+        const int ob_rows = F * (1 + mm), fp_rows = single ? 0 : A * mm;
+        if (!enc->ob || !enc->w_ob || !enc->b_ob || enc->ob_row < (int64_t)N * F || enc->w_ob_sn < (int64_t)ob_rows * H || enc->b_ob_sn < H ||
+            (enc->b_ob_sn % 4) || ((uintptr_t)enc->b_ob % 16) ||
+            (!single && (!enc->fp || !enc->b_fp || enc->fp_sn < E * A || enc->w_fp_sn < (int64_t)fp_rows * H || enc->b_fp_sn < H ||
+                         (enc->b_fp_sn % 4) || ((uintptr_t)enc->b_fp % 16))) ||
+            (enc->out && (((uintptr_t)enc->out % 16) || enc->out_row < (single ? H : 2 * H) || (enc->out_row % 4) || (enc->out_sn % 4) ||
+                          enc->out_sn < E * enc->out_row)) ||
+            (enc->relu_bits && (single || ((uintptr_t)enc->relu_bits % 4) || enc->relu_bits_sn < E * 4)))
+            return NMARL_EINVAL;
+        for (int i = 0; i < N * mm; ++i)                           // nbr: [N][m_max], -1 padded
+            if (enc->nbr[i] < -1 || enc->nbr[i] >= N) return NMARL_EINVAL;
+        xa.e_ob = enc->ob; xa.e_ob_row = enc->ob_row; xa.e_fp = enc->fp; xa.e_fp_sn = enc->fp_sn;
+        xa.e_wob = enc->w_ob; xa.e_bob = enc->b_ob; xa.e_wfp = enc->w_fp; xa.e_bfp = enc->b_fp;
+        xa.e_wob_sn = enc->w_ob_sn; xa.e_bob_sn = enc->b_ob_sn; xa.e_wfp_sn = enc->w_fp_sn; xa.e_bfp_sn = enc->b_fp_sn;
+        xa.e_out = enc->out; xa.e_out_sn = enc->out_sn; xa.e_out_row = enc->out_row;
+        xa.e_bits = enc->relu_bits; xa.e_bits_sn = enc->relu_bits_sn;
+        for (int i = 0; i < 64; ++i) {                             // agent i's four slots as signed bytes (see XArgs)
+            unsigned w = 0;
+            for (int k = 0; k < 4; ++k) w |= (unsigned)((i < N && k < mm ? enc->nbr[i * mm + k] : -1) & 255) << (8 * k);
+            xa.e_nbr[i] = (int)w;
+        }
+        xa.ob_F = F; xa.e_ob_rows = ob_rows | (fp_rows << 8) | ((single ? 1 : A) << 16);
+        // same LDS as the CACC forms: the 16 + 8 KB weight image borrows the x-slot region until the pre-phase's barrier
+        const size_t lb_g = (size_t)(2 * CH_FLOATS + HW_FLOATS + 8 * 512 * 4 + 6 * 64 * 4 + 2 * H) * sizeof(float);
+        static NmarlPerDeviceOnce gen_once;
+        if (const unsigned long long bit = gen_once.pending(); bit != ~0ull) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lb_g) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_x_kernel<3, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lb_g) != hipSuccess)
+                return NMARL_EHIP;
+            gen_once.done(bit);
+        }
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (single) hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 4>), grid, dim3(512), lb_g, st, xa);
+        else hipLaunchKernelGGL((lstm_step_x_kernel<3, 0, 3>), grid, dim3(512), lb_g, st, xa);
+        return nmarl_check_launch();
+    }
     if (enc) {
         // the input encoders inside the launch (ENC 1) on the CACC input layout: the uncoupled nets' policy + value step (<3,0,1>), or
         // NeurComm's one-launch lock-step (<4,1,1>: x = the S slot the encoders' [hx | hp] goes to AND the K loop reads it back from)

@@ -391,24 +391,47 @@ def _step_x(h, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs, head, 
     check(lib.nmarl_lstm_step_x(C.byref(a), stream()), what)
 
 
+STEP_ENC_MAX_OB, STEP_ENC_MAX_FP, STEP_ENC_MAX_M, STEP_ENC_MAX_N = 64, 32, 4, 32      # inputs of the two encoders, slots, agents
+
+
+def step_enc_cacc_layout(n_feat):
+    """The CACC input layout (5 own features): the register-only forms ENC 1 / 2, the only ones a coupled net's launch has."""
+    return n_feat == 5
+
+
+def _step_enc_ob_fits(n_feat, m_max):
+    """The observation encoder's input layout: CACC's 5 x (1 + {0, 2}) (ENC 1 / 2), or a multiple of 4 own features x (1 + m_max <= 4
+    neighbour slots) <= 64 inputs (ENC 3 / 4: the ATSC grid's 12 x 5)."""
+    if step_enc_cacc_layout(n_feat):
+        return m_max in (0, 2)
+    return n_feat > 0 and n_feat % 4 == 0 and 0 <= m_max <= STEP_ENC_MAX_M and n_feat * (1 + m_max) <= STEP_ENC_MAX_OB
+
+
 def step_enc1_supported(n_feat, m_max, n_fc, n_h, N):
-    """The observation encoder ALONE fits the lock-step kernel's pre-phase (csrc/lstm_mfma.hip, ENC 2): 5 own features x (1 + m_max
-    neighbours), m_max = 2 (IA2C on CACC) or 0 (ConseNet: own features only) -> 64 outputs."""
-    return n_feat == 5 and m_max in (0, 2) and n_fc == FC_J and n_h == FUSED_H and N <= 32 and \
+    """The observation encoder ALONE fits the lock-step kernel's pre-phase (csrc/lstm_mfma.hip, ENC 2 / 4): n_feat own features x
+    (1 + m_max neighbours) -> 64 outputs; m_max = 0: own features only (ConseNet)."""
+    return _step_enc_ob_fits(n_feat, m_max) and n_fc == FC_J and n_h == FUSED_H and N <= STEP_ENC_MAX_N and \
         os.environ.get('NMARL_INKERNEL_ENCODE', '1') != '0'
 
 
 def step_enc_supported(n_feat, n_a, m_max, n_fc, n_h, N):
-    """The two input encoders of IA2C-FP / NeurComm fit the lock-step kernel's register-only pre-phase (csrc/lstm_mfma.hip, ENC): the
-    CACC input layout -- 5 own features x (1 + 2 neighbours) and 2 x 4 fingerprint entries -> 64 + 64 outputs."""
-    return n_feat == 5 and n_a == 4 and m_max == 2 and n_fc == FC_J and n_h == FUSED_H and N <= 32 and \
+    """The two input encoders of IA2C-FP / NeurComm fit the lock-step kernel's pre-phase (csrc/lstm_mfma.hip, ENC 1 / 3): the CACC
+    input layout -- 5 own features x (1 + 2 neighbours) and 2 x 4 fingerprint entries --, or the general one -- see
+    `_step_enc_ob_fits`, and n_a <= 8 fingerprint entries x m_max >= 1 neighbours <= 32 inputs -- -> 64 + 64 outputs."""
+    if step_enc_cacc_layout(n_feat):
+        fits = n_a == 4 and m_max == 2
+    else:
+        fits = _step_enc_ob_fits(n_feat, m_max) and m_max >= 1 and 1 <= n_a <= 8 and n_a * m_max <= STEP_ENC_MAX_FP
+    return fits and n_fc == FC_J and n_h == FUSED_H and N <= STEP_ENC_MAX_N and \
         os.environ.get('NMARL_INKERNEL_ENCODE', '1') != '0'
 
 
 def step_enc_spec(ob, fp, w_ob, b_ob, w_fp, b_fp, nbrs, out=None, env=None, bits=None):
-    """Description of a lock-step's input encoders for `lstm_step_policy_value(xs=(spec, wx, image))`: ob [E,N,5] the env's
-    compact observation, fp [N,E,4] the previous-step policies, the four parameter tensors as they are, nbrs = the HOST
-    neighbour lists (ascending), out [N,E,128] (a view: slot t of the saved LSTM inputs) or None.
+    """Description of a lock-step's input encoders for `lstm_step_policy_value(xs=(spec, wx, image))`: ob [E,N,F] the env's
+    compact observation, fp [N,E,A] the previous-step policies, the four parameter tensors as they are, nbrs = the HOST
+    neighbour lists in the order of the gathered slab's slots (= of the weight rows: ascending for the policies' slabs), out
+    [N,E,128] (a view: slot t of the saved LSTM inputs) or None.  F = 5, A = 4: the CACC forms; else the general ones
+    (`step_enc_supported`).
     env (optional): the CACC env step of this lock-step inside the launch as well -- CACCBatchEnv.inkernel_step(...).
     bits (optional): [N,E,4] int32 -- which of a row's 128 outputs are > 0 (layout: relu_bits_pack), for fc_concat(bits=)."""
     return dict(ob=ob, fp=fp, w_ob=w_ob, b_ob=b_ob, w_fp=w_fp, b_fp=b_fp, nbrs=nbrs, out=out, env=env, bits=bits)
@@ -442,17 +465,25 @@ def step_env_scratch(N, E, device):
 
 def _step_enc(d, N, E):
     ob, fp = d['ob'], d['fp']
-    if ob.dim() != 3 or ob.shape != (E, N, 5) or not ob.is_contiguous():
-        raise _lib.NmarlError('step_enc: ob must be the compact observation [E,N,5], contiguous')
-    if d.get('w_fp') is not None and (fp.shape != (N, E, 4) or fp.stride(2) != 1 or fp.stride(1) != 4):
-        raise _lib.NmarlError('step_enc: fp must be [N,E,4] with contiguous panels')
+    if ob.dim() != 3 or ob.shape[:2] != (E, N) or not ob.is_contiguous():
+        raise _lib.NmarlError('step_enc: ob must be the compact observation [E,N,F], contiguous')
+    nF = ob.shape[2]
+    single = d.get('w_fp') is None                 # the observation encoder alone: w_ob [N,F(1+m),64] (IA2C) or [N,F,64] (ConseNet)
+    cacc = step_enc_cacc_layout(nF)
+    nA = 4 if (cacc or single) else fp.shape[2]
+    if not single and (fp.dim() != 3 or fp.shape != (N, E, nA) or fp.stride(2) != 1 or fp.stride(1) != nA):
+        raise _lib.NmarlError('step_enc: fp must be [N,E,%d] with contiguous panels' % nA)
     e = _lib.StepEnc()
-    e.ob, e.ob_row = ptr(ob, F32), N * 5
-    single = d.get('w_fp') is None                 # the observation encoder alone (ENC 2): w_ob [N,15,64] (IA2C) or [N,5,64] (ConseNet)
-    m_enc = 2 if (not single or d['w_ob'].shape[1] == 15) else 0
+    e.ob, e.ob_row = ptr(ob, F32), N * nF
+    if cacc:
+        m_enc = 2 if (not single or d['w_ob'].shape[1] == 15) else 0
+    else:                                          # the general layout: the slot count is the weight's (the launcher checks the limits)
+        m_enc = d['w_ob'].shape[1] // nF - 1
+        if d['w_ob'].shape[1] != nF * (1 + m_enc) or m_enc < 0 or m_enc > STEP_ENC_MAX_M:
+            raise _lib.NmarlError('step_enc: w_ob must have F x (1 + m_max <= %d) rows' % STEP_ENC_MAX_M)
     if not single:
         e.fp, e.fp_sn = ptr(fp, F32, strided=True), fp.stride(0)
-    for key, rows in (('w_ob', 5 * (1 + m_enc)),) + (() if single else (('w_fp', 8),)):
+    for key, rows in (('w_ob', nF * (1 + m_enc)),) + (() if single else (('w_fp', nA * m_enc),)):
         w = d[key]
         if w.shape != (N, rows, FC_J):
             raise _lib.NmarlError('step_enc: %s must be [N,%d,64]' % (key, rows))
@@ -470,12 +501,14 @@ def _step_enc(d, N, E):
         if bits.shape != (N, E, 4) or bits.dtype != torch.int32 or bits.stride(2) != 1 or bits.stride(1) != 4:
             raise _lib.NmarlError('step_enc: bits must be [N,E,4] int32 with contiguous panels')
         e.relu_bits, e.relu_bits_sn = ptr(bits, torch.int32, strided=True), bits.stride(0)
-    e.F, e.A, e.m_max = 5, 4, m_enc
-    for i in range(64):
+    e.F, e.A, e.m_max = nF, nA, m_enc
+    for i in range(len(e.nbr)):
         e.nbr[i] = -1
-    for i, lst in enumerate(d['nbrs'] if m_enc else []):
-        for k, j in enumerate(lst[:2]):
-            e.nbr[2 * i + k] = int(j)
+    if m_enc and (N * m_enc > len(e.nbr) or any(len(lst) > m_enc for lst in d['nbrs'])):
+        raise _lib.NmarlError('step_enc: the neighbour table [N,%d] does not fit (N <= %d, at most m_max neighbours each)' % (m_enc, STEP_ENC_MAX_N))
+    for i, lst in enumerate(d['nbrs'] if m_enc else []):       # [N][m_max], -1 padded
+        for k, j in enumerate(lst):
+            e.nbr[m_enc * i + k] = int(j)
     ev = d.get('env')
     if ev is not None:
         e.env = C.pointer(ev['params'])

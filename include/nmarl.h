@@ -468,6 +468,13 @@ typedef struct nmarl_msg {
  * Round 6 -- the observation encoder ALONE (w_fp = NULL; KX = 64, out [N][E][64]): IA2C (policies.py:145, `fc(ob, 'fc', n_fc)`:
  *   m_max = 2, w_ob [N][15][64]) and ConseNet (policies.py:381-390, the agent's own five features only: m_max = 0, w_ob [N][5][64],
  *   nbr ignored); fp / b_fp / relu_bits unused (NULL).
+ * ABI 4 -- the same two forms on a GENERAL input layout (F != 5; the uncoupled nets on the ATSC grid: F = 12, m_max = 4, A = 5):
+ *   ob [E][N][F], F a multiple of 4; 1 + m_max observation slots, m_max <= 4, F (1 + m_max) <= 64 rows of w_ob; fp [N][E][A],
+ *   A <= 8, A m_max <= 32 rows of w_fp (w_fp = NULL: the observation encoder alone, m_max = 0 allowed, out [N][E][64]).  Slot k + 1
+ *   of the observation / slot k of the fingerprints is neighbour nbr[i * m_max + k] of agent i -- the order of the weight rows, i.e.
+ *   of the caller's gathered slab --; an absent neighbour (-1) contributes zeros and its weight rows are not read into the sum.
+ *   nbr is [N][m_max] for every form (N <= 32: 128 entries; ABI 3 had 64).  fp32 only (precision 0), no msg, env = NULL;
+ *   relu_bits as below.  Anything else is NMARL_EINVAL without a launch.
  * enc WITH msg -- NeurComm's WHOLE lock-step in one launch (round 6; agents/utils.py:118-217 `lstm_comm`, utils.py:163-197,
  * envs/cacc_env.py:191-242): head kind 3 and message kind 1 -- the two input encoders [relu(x~ W_ob + b) | relu(p~ W_fp + b)]
  * run in the launch's pre-phase and, with enc->env, the CACC env step behind the action draw.  x (KX = 192: [N][E] rows of
@@ -482,7 +489,7 @@ typedef struct nmarl_step_enc {
     int64_t w_ob_sn, b_ob_sn, w_fp_sn, b_fp_sn;
     float* out; int64_t out_sn, out_row;
     int32_t F, A, m_max, pad_;
-    int32_t nbr[64];
+    int32_t nbr[128];
     /* The CACC env step of THIS lock-step inside the launch too (env != NULL; N = 8, A <= 4): CACCEnv.step (envs/cacc_env.py:191-242)
      * for the actions the launch draws -- one launch per lock-step.  Every drawn action is added into its replica's hand-off word
      * cnt[e] by ONE atomic (2 bits of payload per agent + an arrival count above them); the lane whose add finds N - 1 earlier
