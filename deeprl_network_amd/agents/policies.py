@@ -439,6 +439,8 @@ class BatchedPolicy:
         if self.fused_pv:
             return True
         K = self.n_h * self.m_max if self.msg_kind == ops.MSG_GATHER_RELU else self.n_h
+        if K > ops.MSG_MAX_K:        # lstm_comm with 3 or 4 neighbours: the message term is in-kernel in the launch-per-step forms only
+            return False
         return self.fused_pv_coupled and ops.step_handoff_supported(self.N, E, self.device, K=K)
 
     def _sync_words(self, E):

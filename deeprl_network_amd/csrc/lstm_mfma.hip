@@ -816,7 +816,10 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
     float4 PU[16];
     float PW[4];
     using K0 = std::integral_constant<int, 0>;
+    using K2 = std::integral_constant<int, 2>;
     using K4 = std::integral_constant<int, 4>;
+    // lstm_comm's launch-per-step forms take a message input of up to 256 floats (four neighbour slots): see msg_phase
+    constexpr bool MSG_WIDE = HEAD != 4 && MSG == 1;
     static_assert(CARRY == 0 || (HEAD == 4 && (MSG == 1 || MSG == 2)), "the message carry exists between one-launch lock-steps");
     constexpr bool carried = CARRY == 2;                             // the previous launch's re-step computed this message term
     if (MSG != 0) {
@@ -1089,16 +1092,46 @@ __global__ __launch_bounds__(512, 1) void lstm_step_x_kernel(const XArgs xa) {
         f32x4 macc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) macc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // one round of the gather forms: the four chunks of the two neighbour slots U / W hold = chunks KB .. KB + 3 of the message
+        // input, against the 128 image rows resident in LDS
+#define NMARL_MROUND(KB)                                                                       \
+            _Pragma("unroll")                                                                  \
+            for (int kc = 0; kc < 4; ++kc) {                                                   \
+                if ((KB) + kc < xa.msg_kc) {                                                   \
+                    const float w = W[kc >> 1];                                                \
+                    float4 m0 = U[2 * kc], m1 = U[2 * kc + 1];                                 \
+                    m0.x *= w; m0.y *= w; m0.z *= w; m0.w *= w; m1.x *= w; m1.y *= w; m1.z *= w; m1.w *= w; \
+                    NMARL_MCHUNK(macc, m_lds, kc, m0, m1)                                      \
+                }                                                                              \
+            }
         if (reuse) {
-        } else if (MSG != 2) {              // chunk kc = half (kc & 1) of neighbour slot (kc >> 1), K_m = 64 m_max <= 128
-#pragma unroll
-            for (int kc = 0; kc < 4; ++kc) {
-                if (kc < xa.msg_kc) {
-                    const float w = W[kc >> 1];
-                    float4 m0 = U[2 * kc], m1 = U[2 * kc + 1];
-                    m0.x *= w; m0.y *= w; m0.z *= w; m0.w *= w; m1.x *= w; m1.y *= w; m1.z *= w; m1.w *= w;
-                    NMARL_MCHUNK(macc, m_lds, kc, m0, m1)
+        } else if (MSG != 2) {              // chunk kc = half (kc & 1) of neighbour slot (kc >> 1), K_m = 64 m_max <= 128 resident
+            if constexpr (MSG_WIDE) {
+                if (xa.msg_kc > 4) {
+                    // lstm_comm with 3 or 4 neighbour slots (K_m = 192 / 256): two rounds of two slots into the same accumulators, chunks
+                    // ascending.  The image does not fit LDS whole: rows 0..127 are resident (staged by the prologue), rows 128.. are REQUESTED
+                    // here, in front of round 0's products, and stored over the first half once every wave of the block has read it.  A
+                    // block-uniform branch (msg_kc is a launch argument); K_m = 192: the second half has 64 rows, nothing past the image is read.
+                    const float4* g = reinterpret_cast<const float4*>(xa.msg_img + (int64_t)n * xa.msg_img_sn);
+                    const int lim = xa.msg_kc * (CH_K * 64 / 4);                 // 3072 or 4096 float4 in all, 2048 of them resident
+                    // (named registers: as an array living across the barriers it is demoted to scratch, like the staging registers)
+                    const int i0 = 2048 + (int)threadIdx.x;
+                    const float4 mw0 = g[i0], mw1 = g[i0 + 512], mw2 = g[i0 + 1024 < lim ? i0 + 1024 : 0], mw3 = g[i0 + 1536 < lim ? i0 + 1536 : 0];
+                    NMARL_MROUND(0)
+                    msg_load(second_c, K2{}, U, W);                              // slots 2 and 3 (absent: the own row, weight 0)
+                    __syncthreads();                                             // the first half's last read
+                    {
+                        float4* d = reinterpret_cast<float4*>(m_lds) + threadIdx.x;
+                        d[0] = mw0; d[512] = mw1;
+                        if (i0 + 1024 < lim) { d[1024] = mw2; d[1536] = mw3; }       // (msg_kc 6: rows 192.. do not exist)
+                    }
+                    __syncthreads();
+                    NMARL_MROUND(4)
+                } else {
+                    NMARL_MROUND(0)
                 }
+            } else {
+                NMARL_MROUND(0)
             }
         } else {                            // mean over the existing neighbours (K_m = 64: two chunks), four neighbours per round
             int cnt = 0;
@@ -1768,7 +1801,7 @@ extern "C" int nmarl_lstm_step_x(const nmarl_step_x_t* s, void* stream) {
         return NMARL_EINVAL;
     if (mk && E > 0) {
         if (msg->m_max <= 0 || msg->m_max > 8 || !msg->nbr_idx || !msg->img || !msg->b || msg->b_sn < H ||
-            msg->K != (mk == 2 ? H : H * msg->m_max) || msg->K > 128 || msg->img_sn < (int64_t)msg->K * 64 || (msg->img_sn % 4) ||
+            msg->K != (mk == 2 ? H : H * msg->m_max) || msg->K > ((mk == 1 && (kind == 1 || kind == 2)) ? 256 : 128) || msg->img_sn < (int64_t)msg->K * 64 || (msg->img_sn % 4) ||
             ((uintptr_t)msg->img % 16) || ((uintptr_t)msg->b % 16) || (msg->b_sn % 4) ||
             (mk != 1 && (!msg->enc || msg->enc_row < H || msg->enc_sn < E * msg->enc_row || ((uintptr_t)msg->enc % 16) ||
                          (msg->enc_row % 4) || (msg->enc_sn % 4))) ||
@@ -1849,7 +1882,8 @@ extern "C" int nmarl_lstm_step_x(const nmarl_step_x_t* s, void* stream) {
     static NmarlPerDeviceOnce lds_once;
     // no message pre-phase: three chunk buffers (de-phased wave groups); with it: two + the W_msg image
     const int lb_max = (int)((LDSX_FLOATS + CH_FLOATS) * sizeof(float));
-    const size_t lb = (size_t)(LDSX_FLOATS + (mk ? msg->K * 64 : CH_FLOATS)) * sizeof(float);
+    // (lstm_comm with K > 128, head kinds 1 / 2: 128 rows of the W_msg image are resident at a time, the second half streams in)
+    const size_t lb = (size_t)(LDSX_FLOATS + (mk ? (msg->K < 128 ? msg->K : 128) * 64 : CH_FLOATS)) * sizeof(float);
     if (const unsigned long long lds_bit = lds_once.pending(); lds_bit != ~0ull) {
 #define NMARL_SET_LDS(k) \
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lb_max) != hipSuccess) return NMARL_EHIP;

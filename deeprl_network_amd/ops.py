@@ -254,12 +254,15 @@ def _img_arg(img, N, KX, precision, what):
 
 
 MSG_GATHER_RELU, MSG_MEAN_ADD, MSG_DIAL = 1, 2, 3      # nmarl_msg_t.kind: lstm_comm / lstm_ic3 / lstm_dial
-MSG_MAX_K = 128
+MSG_MAX_K = 128                  # widest message input every form takes, the one-launch lock-step (head kind 3) included
+# per kind, the launch-per-step forms (head kinds 1 and 2): lstm_comm streams W_msg through LDS in two 128-row halves (m_max <= 4);
+# lstm_dial stages a second image behind the first and stays at one resident half
+MSG_KIND_MAX_K = {MSG_GATHER_RELU: 256, MSG_MEAN_ADD: 64, MSG_DIAL: 128}
 
 
 def msg_supported(kind, m_max, n_h):
     """The message term of a coupled net fits the step kernel's pre-phase (csrc/lstm_mfma.hip, MSG)."""
-    return n_h == FUSED_H and m_max <= 8 and (n_h if kind == MSG_MEAN_ADD else n_h * m_max) <= MSG_MAX_K
+    return n_h == FUSED_H and m_max <= 8 and (n_h if kind == MSG_MEAN_ADD else n_h * m_max) <= MSG_KIND_MAX_K.get(kind, 0)
 
 
 def lstm_msg_wimage(w_msg, out=None):

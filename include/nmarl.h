@@ -392,7 +392,8 @@ typedef struct nmarl_head {
  * msg (NULL: none; needs a head, no x2 / zadd1 / zadd2): the policy / value step of a COUPLED net, its message term computed
  * inside the kernel from the neighbours' previous, un-masked h (quirk Q3; h_in of the other agents, agent stride h_sn) instead
  * of by separate gather / GEMM / bias-activation launches:
- *   kind 1  lstm_comm (agents/utils.py:182-199): hm = relu([h_j : j in nbr(i)] @ w_msg + b_msg), K = 64*m_max <= 128;
+ *   kind 1  lstm_comm (agents/utils.py:182-199): hm = relu([h_j : j in nbr(i)] @ w_msg + b_msg), K = 64*m_max <= 256 with head
+ *           kinds 1 and 2 (K > 128, m_max 3 or 4: w_msg goes through LDS in two 128-row halves), <= 128 with head kind 3;
  *           the LSTM input is [x (KX-64 columns: [hx | hp]) | hm]
  *   kind 2  lstm_ic3 (agents/utils.py:395-400): s = mean_j(h_j) @ w_msg + b_msg + enc, K = 64; the LSTM input is s (KX = 64)
  *   kind 3  lstm_dial (agents/utils.py:515-599): hm = relu([msg_j : j in nbr(i)] @ w_msg + b_msg), K = 64*m_max <= 128, from
