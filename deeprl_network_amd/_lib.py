@@ -85,7 +85,7 @@ class StepEnc(C.Structure):
 class NetParams(C.Structure):
     """nmarl_net_params_t (include/nmarl.h)."""
     _fields_ = [('norm_wave', C.c_float), ('clip_wave', C.c_float), ('flow_rate', C.c_float), ('T', C.c_int32),
-                ('per_agent_reward', C.c_int32)]
+                ('per_agent_reward', C.c_int32), ('objective', C.c_int32), ('coef_wait', C.c_float), ('head_wait', C.c_void_p)]
 
 
 class NetTopo(C.Structure):
@@ -198,6 +198,7 @@ SIGNATURES = {
     'nmarl_grid_reset': [C.POINTER(GridParams), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_grid_step': [C.POINTER(GridParams), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64, _p, _p],
     'nmarl_net_reset': [C.POINTER(NetTopo), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    'nmarl_net_reset_obj': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_net_step': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64,
                        _p, _p],
     'nmarl_nbr_gather_fwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],

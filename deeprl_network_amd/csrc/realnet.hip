@@ -17,6 +17,23 @@
 // through LDS with coalesced accesses.  Algorithmic bytes per replica-step: q, transit 2*4*sum(n_s) in and out +
 // action/prev N + 20 B + the slab 4*L*(1+m_max)*N (12.3 KB for Monaco, of which 4*sum_i(n_s_i + sum_nbr n_s_j) =
 // 5.0 KB are non-padding).  The intended bound is HBM; today the kernel is instruction-bound.
+//
+// Objectives `wait` / `hybrid` (atsc_env.py:87-96, 383-418; net_step_kernel<REPS, WAIT = true>).  SPECIFICATION -- the grid's
+// step 6 (oracle/grid_ref.py:42-48) carried to links; parity unpinned like the rest of the synthetic dynamics:
+//   one more state array head_wait [E,N,L] f32 holds the seconds the front vehicle of a link has been standing.  With q the
+//   queue at the START of the step and served = D * scale the quantity of oracle/realnet_ref.py step 3,
+//       moved      = served > WAIT_EPS  or  q <= WAIT_EPS            (WAIT_EPS = 1e-3 veh, the grid's constant)
+//       head_wait' = 0 if moved else head_wait + 5                   (seconds; links k >= n_s_i stay 0)
+//       wait_i     = sum over the node's n_s_i links of head_wait'   (ascending link, the order of the queue sum)
+//       reward_i   = -wait_i (`wait`)   or   -queue_i - coef_wait * wait_i (`hybrid`; queue_i as for `queue`)
+//   the global reward is the sum over nodes; the objective changes rewards only, never q / transit / the observation;
+//   every reset (plain, masked, the fused auto-reset of an episode's last step) clears the replica's head_wait.
+// Staging of head_wait: the WAIT forms add NO LDS (a third staging area per replica would cost 3 072 B x REPS next to the 6 272 B
+// x REPS + the 13 568-byte table image) and keep 2 / 4 / 8 replicas per block: head_wait is staged THROUGH cnt / acc WHERE THEY
+// ARE DEAD.  The rows are loaded with q / transit (all loads in flight together), parked in registers over phase A, passed
+// through cnt between phase A and the observation (cnt holds nothing from the barrier behind phase A to the wave write), and
+// written back through acc in a further pass behind transit's (one more barrier per step).  WAIT = false compiles to what it
+// was: same loads, stores, LDS and registers (profiles/r12_net_wait.txt).
 #include "common.h"
 #include <stdlib.h>
 
@@ -26,11 +43,12 @@ constexpr int NMAX = 32;          // nodes (lanes of a half wave)
 constexpr int LMAX = 24;          // links per node kept in registers
 constexpr int AMAX = 8;           // phases per node
 constexpr float DT = 5.0f, YELLOW = 2.0f, YELLOW_EFF = 1.0f, SAT = 0.5f, Q_MAX = 26.0f, DET_CAP = 7.0f;
+constexpr float WAIT_EPS = 1e-3f;    // veh: a discharge / a standing queue below this does not count (oracle/grid_ref.py)
 
 struct RepShared {
     float out[NMAX];
     float acc[NMAX * LMAX];          // also the coalesced staging area of q (load) / the new q (store)
-    float cnt[NMAX * LMAX];          // also the staging area of transit
+    float cnt[NMAX * LMAX];          // also the staging area of transit (and, WAIT, of head_wait on its way in)
 };
 
 __device__ __forceinline__ void half_barrier() { __syncthreads(); }   // the replicas of a block run in lock step
@@ -44,7 +62,7 @@ __device__ __forceinline__ float activity_b(const int piece) {
     return (piece < 3 || piece > 10) ? 0.0f : (piece == 3 || piece == 10) ? 1.0f : (piece == 4 || piece == 9) ? 2.0f : 4.0f;
 }
 
-template <int REPS>
+template <int REPS, bool WAIT>
 __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
     const nmarl_net_params_t p, const nmarl_net_topo_t tp, const int64_t E, const uint8_t* __restrict__ action,
     float* __restrict__ qs, float* __restrict__ trs, uint8_t* __restrict__ prev, int32_t* __restrict__ ts,
@@ -93,6 +111,8 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
         const bool live = e < E;
         const int64_t ec = live ? e : E - 1;
         float q[LMAX], tr[LMAX], D[LMAX];
+        [[maybe_unused]] float lh[WAIT ? NMAX * LMAX / 32 : 1];              // WAIT: the replica's head_wait rows as loaded (coalesced)
+        [[maybe_unused]] float* __restrict__ const hws = p.head_wait;
         int a = 0, pa = 0;
         const int t = ts[ec];
         if (node) {
@@ -107,6 +127,7 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
                 const int i = it * 32 + l32;
                 lq[it] = i < N * L ? qs[ec * N * L + i] : 0.0f;
                 lt[it] = i < N * L ? trs[ec * N * L + i] : 0.0f;
+                if constexpr (WAIT) lh[it] = i < N * L ? hws[ec * N * L + i] : 0.0f;
             }
 #pragma unroll
             for (int it = 0; it < NMAX * LMAX / 32; ++it) {
@@ -137,6 +158,16 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
             }
         }
         half_barrier();                                      // everybody has read its staged rows
+        if constexpr (WAIT) {                                // cnt is dead until the wave write: head_wait goes through it
+#pragma unroll
+            for (int it = 0; it < NMAX * LMAX / 32; ++it) {
+                const int i = it * 32 + l32;
+                if (i < N * L) {
+                    const int r = (i * Lmagic) >> 16;
+                    s.cnt[r * LMAX + (i - r * L)] = lh[it];
+                }
+            }
+        }
         if (node) s.out[n] = t_fan[n] > 0.0f ? out / t_fan[n] : 0.0f;      // what each fed link is offered
         half_barrier();
         // ---- B. what every fed link accepts
@@ -151,6 +182,7 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
         half_barrier();
         // ---- C. delivered per feeder (fixed order), served flows, queue update, arrivals, counts, reward
         float r_node = 0.0f;
+        [[maybe_unused]] float hw[WAIT ? LMAX : 1];                           // WAIT: the links' standing times (registers, as q / tr)
         // external arrivals of this step per flow group: flow_rate * activity_g(t) / 3600 * DT * xi_g  (x the link's share)
         const int piece = (t * 5) / 300;
         const float ra = p.flow_rate * activity_a(piece) / 3600.0f * DT, rb = p.flow_rate * activity_b(piece) / 3600.0f * DT;
@@ -163,10 +195,17 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
                 for (int f = f0; f < f1; ++f) delivered += s.acc[t_dnpair[f]];
             }
             const float scale = out > 1e-6f ? delivered / fmaxf(out, 1e-6f) : 0.0f;
+            [[maybe_unused]] float wait = 0.0f;
 #pragma unroll
-            for (int k = 0; k < LMAX; ++k)
+            for (int k = 0; k < LMAX; ++k) {
+                if constexpr (WAIT) hw[k] = 0.0f;
                 if (k < ns) {
                     const float served = D[k] * scale;
+                    if constexpr (WAIT) {                    // the front vehicle left / no queue stood at the start of the step
+                        const bool moved = served > WAIT_EPS || q[k] <= WAIT_EPS;
+                        hw[k] = moved ? 0.0f : s.cnt[n * LMAX + k] + DT;
+                        wait += hw[k];
+                    }
                     q[k] = q[k] - served + tr[k];
                     const int grp = t_group[n * LMAX + k];
                     float in = s.acc[n * LMAX + k];
@@ -175,6 +214,11 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
                     const float c = fminf(q[k], DET_CAP);
                     r_node -= c;
                 }
+            }
+            if constexpr (WAIT) r_node = p.objective == 1 ? -wait : r_node - p.coef_wait * wait;
+        } else if constexpr (WAIT) {
+#pragma unroll
+            for (int k = 0; k < LMAX; ++k) hw[k] = 0.0f;
         }
         float gsum = r_node;
         for (int off = 16; off > 0; off >>= 1) gsum += __shfl_xor(gsum, off, 32);
@@ -188,6 +232,7 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
                 wv[k] = 0.0f;
                 if (k < ns) {
                     if (rst) { q[k] = 0.0f; tr[k] = 0.0f; }
+                    if constexpr (WAIT) if (rst) hw[k] = 0.0f;
                     float w = fminf(q[k], DET_CAP);
                     if (p.norm_wave != 1.0f) w = w / p.norm_wave;
                     if (p.clip_wave >= 0.0f) w = fminf(fmaxf(w, 0.0f), p.clip_wave);
@@ -228,6 +273,14 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
                 }
             }
         }
+        if constexpr (WAIT) {                                // a further pass through acc (dead behind transit's write-back)
+            half_barrier();
+            if (node) {
+#pragma unroll
+                for (int k = 0; k < LMAX; ++k)
+                    if (k < L) s.acc[n * LMAX + k] = hw[k];
+            }
+        }
         if (live && l32 == 0) {
             if (!p.per_agent_reward) reward[e] = gsum;
             greward[e] = gsum;
@@ -243,6 +296,18 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
         }
         half_barrier();
         if (live && rst && l32 == 4) episode[e] = episode[e] + 1;
+        if constexpr (WAIT) {
+            if (live) {
+#pragma unroll
+                for (int it = 0; it < NMAX * LMAX / 32; ++it) {
+                    const int i = it * 32 + l32;
+                    if (i < N * L) {
+                        const int r = (i * Lmagic) >> 16;
+                        hws[e * N * L + i] = s.acc[r * LMAX + (i - r * L)];
+                    }
+                }
+            }
+        }
         // ---- D. the neighbour-gathered observation slab [N, (1 + m_max) * L]: one 4 L-byte piece per store, rows contiguous
         // (assembling the slab in LDS and streaming it out as float4 was slower: 2-way conflicts on the 110-float rows)
         if (live) {
@@ -265,13 +330,15 @@ __global__ __launch_bounds__(256) void net_reset_kernel(
     const nmarl_net_topo_t tp, const int64_t E, const uint8_t* __restrict__ mask, const float* __restrict__ u0,
     float* __restrict__ qs, float* __restrict__ trs, uint8_t* __restrict__ prev, int32_t* __restrict__ ts,
     float* __restrict__ xi, float* __restrict__ obs, const uint64_t seed, const int64_t env_id_base,
-    int32_t* __restrict__ episode) {
+    int32_t* __restrict__ episode, float* __restrict__ hws) {      // hws: head_wait of a `wait` / `hybrid` env, else NULL
     const int l32 = threadIdx.x & 31, sub = threadIdx.x >> 5;
     const int NL = tp.N * tp.L, NW = tp.N * tp.L * (1 + tp.m_max);
     constexpr int REPS = 8;
     for (int64_t e = (int64_t)blockIdx.x * REPS + sub; e < E; e += (int64_t)gridDim.x * REPS) {
         if (mask != nullptr && mask[e] == 0) continue;
         for (int i = l32; i < NL; i += 32) { qs[e * NL + i] = 0.0f; trs[e * NL + i] = 0.0f; }
+        if (hws != nullptr)
+            for (int i = l32; i < NL; i += 32) hws[e * NL + i] = 0.0f;
         for (int i = l32; i < NW; i += 32) obs[e * NW + i] = 0.0f;
         if (l32 < tp.N) prev[e * tp.N + l32] = 0;
         if (l32 == 0) ts[e] = 0;
@@ -297,6 +364,10 @@ inline int net_blocks(int64_t E, int reps) {
     return (int)(b < 4096 ? b : 4096);
 }
 
+inline bool objective_ok(const nmarl_net_params_t* p) {
+    return p && p->objective >= 0 && p->objective <= 2 && (p->objective == 0 || p->head_wait != nullptr);
+}
+
 inline bool topo_ok(const nmarl_net_topo_t* tp) {
     return tp && tp->N > 0 && tp->N <= NMAX && tp->L > 0 && tp->L <= LMAX && tp->A > 0 && tp->A <= AMAX && tp->m_max > 0 &&
            tp->m_max <= 8 && tp->n_s && tp->image && ((uintptr_t)tp->image % 16) == 0;
@@ -308,31 +379,53 @@ extern "C" int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_
                               float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
                               float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
                               int64_t env_id_base, int32_t* episode, void* stream) {
-    if (!p || !topo_ok(tp) || p->T <= 0 || p->norm_wave <= 0.f || E < 0 ||
+    if (!objective_ok(p) || !topo_ok(tp) || p->T <= 0 || p->norm_wave <= 0.f || E < 0 ||
         (E > 0 && (!action || !q || !transit || !prev_action || !t || !xi || !obs || !reward || !done || !global_reward)))
         return NMARL_EINVAL;
     if (auto_reset && !episode) return NMARL_EINVAL;
     if (E == 0) return NMARL_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // replicas per block: enough blocks to cover the 256 CUs a few times at small E, 8 per block at large E
-#define NMARL_NET_LAUNCH(R) hipLaunchKernelGGL(net_step_kernel<R>, dim3(net_blocks(E, R)), dim3(32 * R), 0, st, *p, *tp, E, action, q, \
-                                               transit, prev_action, t, xi, obs, reward, done, global_reward, auto_reset, seed,   \
-                                               env_id_base, episode)
+#define NMARL_NET_LAUNCH(R, WAIT) hipLaunchKernelGGL((net_step_kernel<R, WAIT>), dim3(net_blocks(E, R)), dim3(32 * R), 0, st, *p, *tp, E, \
+                                                     action, q, transit, prev_action, t, xi, obs, reward, done, global_reward,      \
+                                                     auto_reset, seed, env_id_base, episode)
     static int reps_env = -1;
     if (reps_env < 0) { const char* ev = getenv("NMARL_NET_REPS"); reps_env = ev ? atoi(ev) : 0; }
     const int reps = reps_env ? reps_env : (E <= 2048 ? 4 : 8);
-    if (reps == 2) NMARL_NET_LAUNCH(2); else if (reps == 4) NMARL_NET_LAUNCH(4); else NMARL_NET_LAUNCH(8);
+    if (p->objective == 0) {
+        if (reps == 2) NMARL_NET_LAUNCH(2, false); else if (reps == 4) NMARL_NET_LAUNCH(4, false); else NMARL_NET_LAUNCH(8, false);
+    } else {
+        if (reps == 2) NMARL_NET_LAUNCH(2, true); else if (reps == 4) NMARL_NET_LAUNCH(4, true); else NMARL_NET_LAUNCH(8, true);
+    }
 #undef NMARL_NET_LAUNCH
     return nmarl_check_launch();
 }
 
-extern "C" int nmarl_net_reset(const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0, uint64_t seed,
-                               int64_t env_id_base, int32_t* episode, float* q, float* transit, uint8_t* prev_action,
-                               int32_t* t, float* xi, float* obs, void* stream) {
+namespace {
+
+int net_reset(const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0, uint64_t seed, int64_t env_id_base,
+              int32_t* episode, float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
+              float* head_wait, void* stream) {
     if (!topo_ok(tp) || E < 0 || (E > 0 && (!q || !transit || !prev_action || !t || !xi || !obs))) return NMARL_EINVAL;
     if (!u0 && !episode) return NMARL_EINVAL;
     if (E == 0) return NMARL_OK;
     hipLaunchKernelGGL(net_reset_kernel, dim3(net_blocks(E, 8)), dim3(256), 0, static_cast<hipStream_t>(stream), *tp, E, mask,
-                       u0, q, transit, prev_action, t, xi, obs, seed, env_id_base, episode);
+                       u0, q, transit, prev_action, t, xi, obs, seed, env_id_base, episode, head_wait);
     return nmarl_check_launch();
+}
+
+}  // namespace
+
+extern "C" int nmarl_net_reset(const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0, uint64_t seed,
+                               int64_t env_id_base, int32_t* episode, float* q, float* transit, uint8_t* prev_action,
+                               int32_t* t, float* xi, float* obs, void* stream) {
+    return net_reset(tp, E, mask, u0, seed, env_id_base, episode, q, transit, prev_action, t, xi, obs, nullptr, stream);
+}
+
+extern "C" int nmarl_net_reset_obj(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask,
+                                   const float* u0, uint64_t seed, int64_t env_id_base, int32_t* episode, float* q,
+                                   float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs, void* stream) {
+    if (!objective_ok(p)) return NMARL_EINVAL;
+    return net_reset(tp, E, mask, u0, seed, env_id_base, episode, q, transit, prev_action, t, xi, obs,
+                     p->objective ? p->head_wait : nullptr, stream);
 }

@@ -5,8 +5,9 @@ envs/real_net_env.py + envs/atsc_env.py for the `atsc_real_net` scenario: 28 HET
 The reference drives an external SUMO process on a net file that is not in its repository; this path keeps the
 reference's *contract* -- node set, directed neighbour lists, phase sets (real_net_env.py:21-69), node order and
 neighbour / BFS distance masks (152-195), 5 s control / 2 s yellow, 720-step episodes, `wave` observation, queue
-reward with per-agent spatial discount, the flow_rate demand schedule (real_net_data/build_file.py:70-96) -- and
-replaces the microsimulation by the store-and-forward link-graph model specified in oracle/realnet_ref.py, stepped
+reward with per-agent spatial discount (or the `wait` / `hybrid` objectives of atsc_env.py:383-418 over one more state
+array, head_wait: csrc/realnet.hip header), the flow_rate demand schedule (real_net_data/build_file.py:70-96), the rule-based
+`greedy` agent (real_net_env.py:112-145) -- and replaces the microsimulation by the store-and-forward link-graph model specified in oracle/realnet_ref.py, stepped
 by csrc/realnet.hip for E lock-stepped replicas.  Observations come out already padded to the widest node and
 gathered over the listed neighbours: the input layout of the heterogeneous (identical=False) nets.
 """
@@ -63,6 +64,34 @@ PHASE_SETS = {
             'rrrGGGrrrrrrrrrrrrGGGG', 'rrrGGGrrrrrGGGgrrrGGGg'),
 }
 N_GROUP = 4
+OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
+
+
+class RealNetController:
+    """The reference's rule-based `greedy` agent (real_net_env.py:112-145): per node the phase whose green links hold the most
+    vehicles.  A link counts for a phase where its signal is the capital 'G' (the reference tests `signal == 'G'`: a permitted
+    'g' does not count); the reference adds every incoming lane once per phase, and in the synthetic network every link is its
+    own lane, so nothing is de-duplicated.  `ob` is the node's own wave vector, one entry per link.  Same `forward(obs) ->
+    actions` duck-type as LargeGridController; `reset` / `load` exist so that Trainer.perform / main.py evaluate drive it."""
+    name = 'greedy'
+    n_step = 1
+
+    def __init__(self, node_names):
+        self.node_names = list(node_names)
+        self._phases = {name: PHASE_SETS[key] for name, key, _ in NODE_DEFS}
+
+    def greedy(self, ob, node_name):
+        flows = [sum(ob[k] for k, signal in enumerate(phase) if signal == 'G') for phase in self._phases[node_name]]
+        return int(np.argmax(np.array(flows)))               # the first maximum
+
+    def forward(self, obs):
+        return [self.greedy(ob, node_name) for ob, node_name in zip(obs, self.node_names)]
+
+    def reset(self):
+        return
+
+    def load(self, model_dir, checkpoint=None):
+        return True
 
 
 class NetTopology:
@@ -172,9 +201,12 @@ def net_params_from_config(config):
     """ENV_CONFIG section -> nmarl_net_params_t; keys of atsc_env.py:79-99 + real_net_env.py:147."""
     if config.getint('control_interval_sec') != 5 or config.getint('yellow_interval_sec') != 2:
         raise _lib.NmarlError('the synthetic network is specified for control 5 s / yellow 2 s')
-    if config.get('objective') != 'queue':
-        raise NotImplementedError('only the `queue` objective of the shipped real-net configs is modelled')
+    obj = config.get('objective')
+    if obj not in OBJECTIVES:
+        raise ValueError('objective must be one of queue, wait, hybrid (atsc_env.py:87, 411-416), got %r' % obj)
     p = _lib.NetParams()
+    p.objective = OBJECTIVES[obj]
+    p.coef_wait = config.getfloat('coef_wait', fallback=0.0)
     p.norm_wave = config.getfloat('norm_wave')
     p.clip_wave = config.getfloat('clip_wave')
     p.flow_rate = config.getfloat('flow_rate')
@@ -201,7 +233,7 @@ class RealNetBatchEnv:
         self.n_agent, self.n_a, self.n_a_ls = tp.N, tp.A, list(tp.n_a_ls)
         self.n_feat, self.n_feat_ls = tp.L, list(tp.n_s_ls)               # own observation widths (heterogeneous)
         self.neighbor_mask, self.distance_mask = tp.neighbor_mask, tp.distance_mask
-        if self.agent.startswith('ma2c'):
+        if self.agent.startswith('ma2c') or self.agent == 'greedy':      # (greedy: atsc_env.py:256-257)
             self.n_s_ls = list(tp.n_s_ls)
         else:                                                            # own + listed neighbours' (atsc_env.py:263-269)
             self.n_s_ls = [tp.n_s_ls[i] + sum(tp.n_s_ls[j] for j in tp.nbrs[i]) for i in range(tp.N)]
@@ -213,6 +245,10 @@ class RealNetBatchEnv:
         self.prev_action = torch.zeros(E, N, dtype=torch.uint8, device=d)
         self.t = torch.zeros(E, dtype=torch.int32, device=d)
         self.xi = torch.ones(E, N_GROUP, **f32)
+        # `wait` / `hybrid` objectives: the front vehicle's standing time per link (csrc/realnet.hip header)
+        self.head_wait = torch.zeros(E, N, L, **f32) if self.params.objective else None
+        if self.head_wait is not None:
+            self.params.head_wait = self.head_wait.data_ptr()
         self.obs = torch.zeros(E, N, L * (1 + tp.m_max), **f32)
         self.reward = torch.zeros((E, N) if self.params.per_agent_reward else (E,), **f32)
         self.done = torch.zeros(E, dtype=torch.uint8, device=d)
@@ -221,14 +257,17 @@ class RealNetBatchEnv:
         self.batch_size = None     # episodes end at T only; any n_step dividing T works
 
     def state_tensors(self):
-        return [self.q, self.transit, self.prev_action, self.t, self.xi, self.obs, self.episode, self.done]
+        return [self.q, self.transit, self.prev_action, self.t, self.xi, self.obs, self.episode, self.done] + \
+            ([self.head_wait] if self.head_wait is not None else [])
 
     def reset(self, mask=None, u0=None):
         P = _lib.ptr
-        rc = _lib.lib.nmarl_net_reset(ctypes.byref(self.topo.c), self.E, P(mask, torch.uint8), P(u0, torch.float32),
-                                      self.seed, self.env_id_base, P(self.episode), P(self.q), P(self.transit),
-                                      P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
-        _lib.check(rc, 'nmarl_net_reset')
+        args = (ctypes.byref(self.topo.c), self.E, P(mask, torch.uint8), P(u0, torch.float32), self.seed, self.env_id_base,
+                P(self.episode), P(self.q), P(self.transit), P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
+        if self.head_wait is None:
+            _lib.check(_lib.lib.nmarl_net_reset(*args), 'nmarl_net_reset')
+        else:                                                            # the same reset, which also clears head_wait
+            _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(self.params), *args), 'nmarl_net_reset_obj')
         return self.obs
 
     def step(self, action, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
@@ -248,7 +287,7 @@ class RealNetBatchEnv:
 
 class RealNetEnv:
     """Reference duck-type (atsc_env.py:77-524 / real_net_env.py:145-198) for ONE replica: ragged observation lists
-    (`ma2c*`: the node's own links; `ia2c*`: own + listed neighbours' in ascending node index, + their fingerprints
+    (`ma2c*` / `greedy`: the node's own links; `ia2c*`: own + listed neighbours' in ascending node index, + their fingerprints
     for ia2c_fp), ragged fingerprints, per-agent rewards."""
 
     def __init__(self, config, port=0, device='cuda', **_):
@@ -324,7 +363,7 @@ class RealNetEnv:
         _, reward, done, g = self.batch.step(a)
         global_reward = float(g.item())
         done = bool(done.item())
-        if self.coop_gamma < 0 and self.train_mode:
+        if self.agent == 'greedy' or (self.coop_gamma < 0 and self.train_mode):     # atsc_env.py:205-206
             reward = global_reward
         else:
             reward = reward[0].cpu().numpy().astype(np.float64) if self.coop_gamma >= 0 else global_reward

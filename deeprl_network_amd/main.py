@@ -10,6 +10,7 @@ import torch
 from .agents.models import IA2C, IA2C_CU, IA2C_FP, MA2C_DIAL, MA2C_IC3, MA2C_NC
 from .envs import init_env, make_batch_env
 from .envs.large_grid_env import LargeGridController
+from .envs.real_net_env import RealNetController
 from .utils import (BatchedTrainer, Counter, Evaluator, SummaryWriter, Trainer, check_dir, copy_file, find_file,
                     init_dir, init_log)
 
@@ -42,8 +43,10 @@ def parse_args(argv=None):
 
 
 def init_agent(env, config, total_step, seed, **kw):
-    if env.agent == 'greedy':                  # rule-based baseline of the ATSC scenarios (large_grid_env.py:30-45)
-        return LargeGridController(getattr(env, 'node_names', None)) if env.name.endswith('large_grid') else None
+    if env.agent == 'greedy':                  # rule-based baseline of the ATSC scenarios (large_grid_env.py:30-45, real_net_env.py:112-145)
+        if env.name.endswith('large_grid'):
+            return LargeGridController(getattr(env, 'node_names', None))
+        return RealNetController(env.node_names) if env.name.endswith('real_net') else None
     cls = AGENTS.get(env.agent)
     if cls is None:
         return None

@@ -223,6 +223,11 @@ typedef struct nmarl_net_params {
     float flow_rate;          /* veh/h of one flow, real_net_env.py:147                  */
     int32_t T;                /* ceil(episode_length_sec / control_interval_sec) = 720   */
     int32_t per_agent_reward; /* coop_gamma >= 0 -> reward [E,N], else global [E]        */
+    int32_t objective;        /* atsc_env.py:87, 383-418: 0 `queue` (the shipped configs), 1 `wait`, 2 `hybrid` = queue + coef_wait * wait */
+    float coef_wait;          /* atsc_env.py:96 (hybrid only)                            */
+    float* head_wait;         /* [E,N,L] f32 state, REQUIRED when objective != 0 (else NULL): seconds the front vehicle of each
+                                 link has been standing (csrc/realnet.hip header); links k >= n_s_i stay 0; reset
+                                 to 0 with the replica (nmarl_net_reset_obj, the fused auto-reset) */
 } nmarl_net_params_t;
 
 /* The static network (built by the host from the reference's NODES / PHASES tables): N <= 32 nodes, L <= 24 = widest
@@ -254,7 +259,9 @@ typedef struct nmarl_net_topo {
 /* TrafficSimulator.reset / step (atsc_env.py:164-207) as nmarl_grid_reset / nmarl_grid_step, for the network:
  * q, transit [E,N,L] f32; prev_action [E,N] u8; t [E]; xi [E,4]; obs [E,N,L*(1+m_max)] (slot 0 own `wave`, slots
  * 1.. the listed neighbours' in ascending node index, each L wide and zero padded -- the padded input layout of the
- * heterogeneous nets); action[e,i] in 0..n_a_i-1; reward [E] or [E,N]. */
+ * heterogeneous nets); action[e,i] in 0..n_a_i-1; reward [E] or [E,N].
+ * nmarl_net_step: NMARL_EINVAL for p->objective outside 0..2 and for p->objective != 0 with a NULL p->head_wait.
+ * nmarl_net_reset does not know the objective and leaves head_wait alone: an env with one resets through nmarl_net_reset_obj. */
 int nmarl_net_reset(const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0, uint64_t seed,
                     int64_t env_id_base, int32_t* episode, float* q, float* transit, uint8_t* prev_action,
                     int32_t* t, float* xi, float* obs, void* stream);
@@ -262,6 +269,11 @@ int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int6
                    float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
                    float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
                    int64_t env_id_base, int32_t* episode, void* stream);
+/* nmarl_net_reset for an env with an objective: the same reset, which also clears p->head_wait of the reset replicas when
+ * p->objective != 0 (then p->head_wait must not be NULL; objective outside 0..2 is NMARL_EINVAL). */
+int nmarl_net_reset_obj(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0,
+                        uint64_t seed, int64_t env_id_base, int32_t* episode, float* q, float* transit, uint8_t* prev_action,
+                        int32_t* t, float* xi, float* obs, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Neighbourhood aggregation over the fixed adjacency (agent-major [N,E,F])   */
