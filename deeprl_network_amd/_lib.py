@@ -201,6 +201,8 @@ SIGNATURES = {
     'nmarl_net_reset_obj': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_net_step': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64,
                        _p, _p],
+    'nmarl_atsc_traffic_begin': [_i64, _i32, _i32, _p, _p, _p, _p, _p],
+    'nmarl_atsc_traffic_step': [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_nbr_gather_fwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],
     'nmarl_nbr_gather_bwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],
     'nmarl_nbr_mean_fwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],

@@ -220,12 +220,17 @@ class LargeGridEnv:
         self.cur_episode = 0
         self.train_mode = True
         self.is_record = False
+        self.record = None           # the traffic / trip tables of an evaluation (envs/traffic_record.py): init_data(is_record=True)
         self._nbr = [np.where(self.neighbor_mask[i] == 1)[0] for i in range(self.n_agent)]
 
     def init_data(self, is_record, record_stats, output_path):
         self.is_record, self.output_path = is_record, output_path
-        if is_record:
-            self.control_data = []
+        if is_record:                                                    # atsc_env.py:142-145
+            from .traffic_record import EpisodeRecord
+            self.control_data, self.traffic_data, self.trip_data = [], [], []
+            self.record = EpisodeRecord(self)
+        else:
+            self.record = None
 
     def init_test_seeds(self, test_seeds):
         self.test_num, self.test_seeds = len(test_seeds), test_seeds
@@ -244,12 +249,14 @@ class LargeGridEnv:
         return
 
     def collect_tripinfo(self):
-        return
+        """The finished episode's rows of `_traffic.csv` and its row of `_trip.csv` (atsc_env.py:107-124, 464-499)."""
+        if self.record is not None:
+            self.record.collect(self.traffic_data, self.trip_data)
 
     def output_data(self):
         if self.is_record:
-            import pandas as pd
-            pd.DataFrame(self.control_data).to_csv(self.output_path + ('%s_%s_control.csv' % (self.name, self.agent)))
+            from .traffic_record import write_tables
+            write_tables(self)
 
     def _state_list(self):
         own = self.batch.obs[0, :, :N_FEAT].cpu().numpy().astype(np.float64)      # every node's own wave vector leads its row
@@ -268,6 +275,8 @@ class LargeGridEnv:
         self.batch.seed = seed
         self.batch.episode.zero_()
         self.batch.reset()
+        if self.record is not None:
+            self.record.begin()
         self.cur_episode += 1
         self.fp = [np.ones(self.n_a) / self.n_a for _ in range(self.n_agent)]
         self.seed += 1
@@ -276,6 +285,8 @@ class LargeGridEnv:
     def step(self, action):
         a = torch.as_tensor(np.asarray(action, dtype=np.uint8).reshape(1, -1), device=self.batch.device)
         _, reward, done, g = self.batch.step(a)
+        if self.record is not None:
+            self.record.step()                                         # one launch behind the step, nothing read back here
         global_reward = float(g.item())
         done = bool(done.item())
         if self.agent == 'greedy' or self.coop_gamma < 0:                           # atsc_env.py:205-206

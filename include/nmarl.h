@@ -276,6 +276,26 @@ int nmarl_net_reset_obj(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp,
                         int32_t* t, float* xi, float* obs, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Traffic record of an ATSC evaluation -- the rows of `_traffic.csv` and the */
+/* sums of `_trip.csv` (envs/atsc_env.py:107-124, 464-499), measured on the    */
+/* state of either synthetic env; specification in csrc/traffic.hip, DESIGN 6  */
+/* ------------------------------------------------------------------------- */
+/* N nodes x S state slots per node (grid: 25 x 6 lanes; network: N x L links); q, transit [E,N,S] f32, t [E] i32, xi [E,4] f32 are
+ * the env's own arrays and are only read.  Static tables (device): mult [N,S] i32 = detector entries of `ilds_in` per slot (0: the
+ * slot does not exist), demand [4,12] f64 = veh/h of flow group g in 5-minute piece p.  Recorder state, owned by the caller:
+ * stand [E,N,S] f32, prev_total [E] f64, cum [E,4] f64 (sum departed, sum arrived, sum total * 5 s, sum halting * 5 s).
+ * nmarl_atsc_traffic_begin clears the state of the replicas selected by mask ([E] u8, NULL = all).
+ * nmarl_atsc_traffic_step, called behind an env step without auto-reset (t >= 1), writes one row per replica to rec_row [E,8] f32:
+ * number_total_car, number_departed_car, number_arrived_car, avg_wait_sec, avg_speed_mps, std_queue, avg_queue, time_sec; one
+ * launch for any E, no host synchronisation.
+ * Both: NMARL_EINVAL without a launch for a NULL pointer (mask excepted), E < 1, N outside 1..32, S outside 1..24. */
+int nmarl_atsc_traffic_begin(int64_t E, int32_t N, int32_t S, const uint8_t* mask, float* stand, double* prev_total, double* cum,
+                             void* stream);
+int nmarl_atsc_traffic_step(int64_t E, int32_t N, int32_t S, const int32_t* mult, const double* demand, const float* q,
+                            const float* transit, const int32_t* t, const float* xi, float* stand, double* prev_total, double* cum,
+                            float* rec_row, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Neighbourhood aggregation over the fixed adjacency (agent-major [N,E,F])   */
 /* ------------------------------------------------------------------------- */
 /*
