@@ -1,6 +1,10 @@
-// The synthetic 5x5 ATSC grid step as DEVICE code shared by the env kernel (csrc/grid.hip) and by the env role of the CommNet
-// lock-step launch (csrc/lstm_mfma.hip, round 6).  Contract: envs/atsc_env.py:181-207 (step), 216-240 (yellow), 383-462 (reward /
-// state); envs/large_grid_env.py:23-27 (phases), 58-105 (topology); build_file.py:268-326 (demand); dynamics: oracle/grid_ref.py.
+// The synthetic ATSC grid step as DEVICE code shared by the env kernel (csrc/grid.hip) and by the env role of the CommNet
+// lock-step launch (csrc/lstm_mfma.hip, round 6).  ONE body for two shapes: the fixed 5x5 lattice (RT = false: every shape constant
+// folds, the code of the 5x5 kernels is what it was before the shape became a parameter) and a runtime rows x cols lattice of
+// 2..32 nodes (RT = true, nmarl_grid_step_rc: rows, cols, N uniform values; lanes >= N hold no node; the entry group of a
+// (node, approach) follows from the rule of DESIGN.md 6 instead of the 5x5 table).
+// Contract: envs/atsc_env.py:181-207 (step), 216-240 (yellow), 383-462 (reward / state); envs/large_grid_env.py:23-27 (phases),
+// 58-105 (topology); build_file.py:268-326 (demand); dynamics: oracle/grid_ref.py.
 #pragma once
 #include "common.h"
 #include <cstddef>
@@ -9,6 +13,7 @@ namespace nmarl_grid {
 
 constexpr int NN = NMARL_GRID_N;        // 25
 constexpr int SIDE = 5;
+constexpr int NMAX = NMARL_GRID_N_MAX;  // 32: a lattice of any shape fits the 32 lanes of a half wave
 constexpr int NL = 12;                  // signal links per node
 constexpr int NLANE = 6;
 constexpr int NSLOT = 5;                // own + 4 neighbour slots
@@ -71,28 +76,46 @@ __device__ __forceinline__ float demand_rate(int group, int sec, float peak1, fl
     return peak2 * (group == 2 ? 0.6f : 1.0f) * c_ratio2[piece - 3];
 }
 
-constexpr int NQ = NN * NLANE;      // 150 floats of q (and of transit) per replica
+constexpr int NQ = NN * NLANE;      // 150 floats of q (and of transit) per replica (5x5)
+constexpr int NQ_MAX = NMAX * NLANE;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct Lds {           // per replica (q / transit live in the block-wide staging arrays: 8 replicas = 4800 contiguous bytes)
-    union {
-        float D[NN * NL];         // phases B, C: the desired link flows (read by the neighbouring nodes' lanes)
-        float wave[NN * NL];      // phases D, E: the wave vectors (D is dead behind phase C's barrier); 16-byte aligned for the emit
-    };
-    union {
-        float space[NN * 4];      // phase B -> C: read by the node's own lane, which then writes
-        float inflow[NN * 4];     // phase C -> D: ... the scaled inflow of the same approach over it
-    };
-    float scale[NN * 4];
+// The lattice: compile-time constants for 5x5, uniform runtime values else.  inv_cols = ceil(2^16 / cols): n * inv_cols >> 16 ==
+// n / cols for every n < 32 and cols <= 32 (the error n (inv_cols - 2^16 / cols) / 2^16 < 31 / 2^16 stays below 1 / cols).
+template <bool RT> struct Shape;
+template <> struct Shape<false> {
+    static constexpr int rows = SIDE, cols = SIDE, nn = NN;
+    __device__ __forceinline__ int row_of(int n) const { return n / SIDE; }
 };
+template <> struct Shape<true> {
+    int rows, cols, nn, inv_cols;
+    __device__ __forceinline__ int row_of(int n) const { return (n * inv_cols) >> 16; }
+};
+
+template <int CAP>
+struct LdsT {          // per replica (q / transit live in the block-wide staging arrays: 8 replicas = 4800 contiguous bytes at 5x5)
+    union {
+        float D[CAP * NL];        // phases B, C: the desired link flows (read by the neighbouring nodes' lanes)
+        float wave[CAP * NL];     // phases D, E: the wave vectors (D is dead behind phase C's barrier); 16-byte aligned for the emit
+    };
+    union {
+        float space[CAP * 4];     // phase B -> C: read by the node's own lane, which then writes
+        float inflow[CAP * 4];    // phase C -> D: ... the scaled inflow of the same approach over it
+    };
+    float scale[CAP * 4];
+};
+typedef LdsT<NN> Lds;             // 5x5
+typedef LdsT<NMAX> LdsRc;         // any shape: sized for 32 nodes
 static_assert(offsetof(Lds, wave) % 16 == 0 && sizeof(Lds) % 16 == 0, "Lds::wave must be 16-byte aligned in every array slot");
+static_assert(offsetof(LdsRc, wave) % 16 == 0 && sizeof(LdsRc) % 16 == 0, "LdsRc::wave must be 16-byte aligned in every array slot");
 
 __device__ __forceinline__ void half_barrier() { __builtin_amdgcn_wave_barrier(); }
 
-// ascending-index neighbour k of node n (or -1): order S(n-5), W(n-1), E(n+1), N(n+5)
-__device__ __forceinline__ int nbr_of(int n, int k) {
-    const int r = n / SIDE, c = n - r * SIDE;
-    int cand[4] = {r > 0 ? n - SIDE : -1, c > 0 ? n - 1 : -1, c < SIDE - 1 ? n + 1 : -1, r < SIDE - 1 ? n + SIDE : -1};
+// ascending-index neighbour k of node n (or -1): order S(n-cols), W(n-1), E(n+1), N(n+cols)
+template <bool RT = false>
+__device__ __forceinline__ int nbr_of(int n, int k, const Shape<RT> sh = Shape<RT>()) {
+    const int r = sh.row_of(n), c = n - r * sh.cols;
+    int cand[4] = {r > 0 ? n - sh.cols : -1, c > 0 ? n - 1 : -1, c < sh.cols - 1 ? n + 1 : -1, r < sh.rows - 1 ? n + sh.cols : -1};
     int cnt = 0;
     for (int i = 0; i < 4; ++i) {
         if (cand[i] >= 0) {
@@ -103,25 +126,25 @@ __device__ __forceinline__ int nbr_of(int n, int k) {
     return -1;
 }
 
-template <int NT, bool COMPACT>
-__device__ __forceinline__ void emit_obs_slab(const Lds& s, float* __restrict__ obs_env, int l32) {
+template <int NT, bool COMPACT, bool RT, typename LDS>
+__device__ __forceinline__ void emit_obs_slab(const LDS& s, float* __restrict__ obs_env, int l32, const Shape<RT> sh) {
     float4* dst = reinterpret_cast<float4*>(obs_env);
     if (COMPACT) {
-        // 25 x 12 floats = 75 float4: the wave vectors as they sit in LDS
+        // N x 12 floats = 3 N float4 (75 at 5x5): the wave vectors as they sit in LDS
         const float4* src = reinterpret_cast<const float4*>(s.wave);
-        for (int v = l32; v < NN * NL / 4; v += 32) {
+        for (int v = l32; v < sh.nn * NL / 4; v += 32) {
             const float4 val = src[v];
             if (NT) __builtin_nontemporal_store(f32x4{val.x, val.y, val.z, val.w}, reinterpret_cast<f32x4*>(dst) + v);
             else dst[v] = val;
         }
         return;
     }
-    // 25 x 60 floats = 375 float4, coalesced
-    for (int v = l32; v < NN * OBSW / 4; v += 32) {
+    // N x 60 floats = 15 N float4 (375 at 5x5), coalesced
+    for (int v = l32; v < sh.nn * OBSW / 4; v += 32) {
         const int node = v / (OBSW / 4);
         const int w = (v - node * (OBSW / 4)) * 4;          // first float within the 60-wide row
         const int slot = w / NL, f = w - slot * NL;          // 12 % 4 == 0: a float4 never straddles slots
-        const int src = slot == 0 ? node : nbr_of(node, slot - 1);
+        const int src = slot == 0 ? node : nbr_of<RT>(node, slot - 1, sh);
         float4 val = float4{0.f, 0.f, 0.f, 0.f};
         if (src >= 0) {
             const float* p = s.wave + src * NL + f;
@@ -135,19 +158,21 @@ __device__ __forceinline__ void emit_obs_slab(const Lds& s, float* __restrict__ 
 // The step of groups of NREP replicas (one per 32-lane half wave; NREP x 32 threads of the calling block), groups first_group,
 // first_group + group_stride, ...: the body of grid_step_kernel (csrc/grid.hip) and of the env role of the one-launch lock-step
 // (csrc/lstm_mfma.hip) -- ONE definition, so the two are bit-identical by construction.  lds / blk_*: the caller's LDS
-// (Lds[NREP], NREP x 150 floats each of q, transit[, head wait]).
-template <int NT, bool COMPACT, bool WAIT, int NREP, bool WORDS>
+// (Lds[NREP], NREP x 150 floats each of q, transit[, head wait]; RT: LdsRc[NREP], NREP x 6 N floats each, room for N = 32).
+template <int NT, bool COMPACT, bool WAIT, int NREP, bool WORDS, bool RT = false, typename LDS = Lds>
 __device__ __forceinline__ void grid_step_groups(
     const nmarl_grid_params_t& p, const int64_t E, const int64_t first_group, const int64_t group_stride,
     const uint8_t* __restrict__ action, unsigned long long* __restrict__ words, int32_t* status, const unsigned max_spins,
     float* __restrict__ qs, float* __restrict__ trs, uint8_t* __restrict__ prev, int32_t* __restrict__ ts,
     float* __restrict__ xi, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
     float* __restrict__ greward, const int auto_reset, const uint64_t seed, const int64_t env_id_base,
-    int32_t* __restrict__ episode, Lds* lds, float* blk_q, float* blk_tr, float* blk_w) {
+    int32_t* __restrict__ episode, LDS* lds, float* blk_q, float* blk_tr, float* blk_w, const Shape<RT> sh = Shape<RT>()) {
+    static_assert(!(RT && WORDS), "the hand-off words pack 13 + 12 actions: the env role of the lock-step launch is 5x5 only");
+    const int NN = sh.nn, NQ = sh.nn * NLANE;               // (shadow the 5x5 constants: the same values when !RT)
     float* __restrict__ const hws = p.head_wait;
     const int l32 = threadIdx.x & 31;
     const int sub = threadIdx.x >> 5;                       // replica slot in the block (0 .. NREP - 1)
-    Lds& s = lds[sub];
+    LDS& s = lds[sub];
     float* const sq = blk_q + sub * NQ;
     float* const str = blk_tr + sub * NQ;
     float* const sw = blk_w + (WAIT ? sub * NQ : 0);
@@ -196,7 +221,7 @@ __device__ __forceinline__ void grid_step_groups(
         __syncthreads();
         const int n = l32;
         const bool node = n < NN;
-        const int row = n / SIDE, col = n - row * SIDE;
+        const int row = sh.row_of(n), col = n - row * sh.cols;
         int a = 0, pa = 0;
         float q[NLANE], tr[NLANE], D[NL];
         if (node) {
@@ -229,8 +254,8 @@ __device__ __forceinline__ void grid_step_groups(
             for (int r = 0; r < 4; ++r) {
                 const int rr = row + c_from[r][0], cc = col + c_from[r][1];
                 float in = 0.0f;
-                if (rr >= 0 && rr < SIDE && cc >= 0 && cc < SIDE) {
-                    const float* Dm = s.D + (rr * SIDE + cc) * NL;
+                if (rr >= 0 && rr < sh.rows && cc >= 0 && cc < sh.cols) {
+                    const float* Dm = s.D + (rr * sh.cols + cc) * NL;
                     in = Dm[c_feed[r][0]] + Dm[c_feed[r][1]] + Dm[c_feed[r][2]];
                 }
                 const float sc = fminf(1.0f, s.space[n * 4 + r] / fmaxf(in, 1e-6f));
@@ -247,7 +272,7 @@ __device__ __forceinline__ void grid_step_groups(
             for (int k = 0; k < NL; ++k) {
                 const int rr = row + c_dest[k][0], cc = col + c_dest[k][1];
                 float fl = D[k];
-                if (rr >= 0 && rr < SIDE && cc >= 0 && cc < SIDE) fl = D[k] * s.scale[(rr * SIDE + cc) * 4 + c_dest[k][2]];
+                if (rr >= 0 && rr < sh.rows && cc >= 0 && cc < sh.cols) fl = D[k] * s.scale[(rr * sh.cols + cc) * 4 + c_dest[k][2]];
                 served[c_link_lane[k]] += fl;
             }
             float inflow[4];
@@ -255,7 +280,16 @@ __device__ __forceinline__ void grid_step_groups(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 inflow[r] = s.inflow[n * 4 + r];
-                const int grp = c_entry[n][r];
+                int grp;
+                if constexpr (RT) {
+                    // the entry rule (it yields c_entry at 5x5): north / south into the interior columns of the top /
+                    // bottom row, west / east into the even rows of the first / last column
+                    const bool mid = col >= 1 && col <= sh.cols - 2, even = (row & 1) == 0;
+                    grp = r == 0 ? (row == sh.rows - 1 && mid ? 1 : 0) : r == 1 ? (col == sh.cols - 1 && even ? 4 : 0)
+                        : r == 2 ? (row == 0 && mid ? 3 : 0) : (col == 0 && even ? 2 : 0);
+                } else {
+                    grp = c_entry[n][r];
+                }
                 if (grp) inflow[r] += demand_rate(grp - 1, sec, p.peak1, p.peak2) / 3600.0f * DT * xi[ec * 4 + grp - 1];
             }
             float hw[NLANE];
@@ -285,7 +319,7 @@ __device__ __forceinline__ void grid_step_groups(
                 for (int l = 0; l < NLANE; ++l) sw[n * NLANE + l] = hw[l];
             }
         }
-        float gsum = r_node;                     // sum over the 25 nodes of the half wave
+        float gsum = r_node;                     // sum over the nodes of the half wave (a lane without a node adds 0)
         for (int off = 16; off > 0; off >>= 1) gsum += __shfl_xor(gsum, off, 32);
         const int t_new = t + 1;
         const bool is_done = t_new >= p.T;       // atsc_env.py:189-191
@@ -339,7 +373,7 @@ __device__ __forceinline__ void grid_step_groups(
                 xi[e * 4 + l32] = 0.8f + 0.4f * u01_from_bits(w);
             }
             if (rst && l32 == 4) episode[e] = episode[e] + 1;
-            emit_obs_slab<NT, COMPACT>(s, obs + e * NN * (COMPACT ? NL : OBSW), l32);
+            emit_obs_slab<NT, COMPACT, RT>(s, obs + e * NN * (COMPACT ? NL : OBSW), l32, sh);
         }
         __syncthreads();                          // the staging arrays are refilled by the next group of replicas
     }

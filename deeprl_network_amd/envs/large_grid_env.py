@@ -1,4 +1,4 @@
-"""Synthetic (SUMO-free) 5x5 ATSC grid on MI355X -- host mirror of the reference's
+"""Synthetic (SUMO-free) ATSC grid on MI355X -- host mirror of the reference's
 envs/large_grid_env.py + envs/atsc_env.py for the `atsc_large_grid` scenario.
 
 The reference drives an external SUMO process over TraCI; this path keeps the reference's
@@ -6,6 +6,9 @@ The reference drives an external SUMO process over TraCI; this path keeps the re
 yellow, 720-step episodes, the peak_flow demand schedule, neighbour / distance masks) and
 replaces the microsimulation by the store-and-forward model specified in
 oracle/grid_ref.py, stepped by csrc/grid.hip for E lock-stepped replicas.
+
+ENV_CONFIG's optional keys `grid_rows` / `grid_cols` (absent: 5) give the lattice any shape of 2..32 intersections -- the same
+per-node model, the external entries placed by the rule of `grid_entries`; 5x5 is the reference's grid.
 """
 import ctypes
 
@@ -15,28 +18,55 @@ import torch
 from .. import _lib
 
 N_NODE, N_FEAT, N_OBS, N_PHASE = 25, 12, 60, 5
+N_NODE_MAX = 32                   # one replica per 32-lane half wave, lane = intersection (csrc/grid_tile.h)
 OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
 
 
-def grid_masks():
-    """neighbor_mask / distance_mask of large_grid_env.py:58-105 (node i = nt{i+1})."""
-    idx = np.arange(N_NODE)
-    r, c = idx // 5, idx % 5
+def grid_shape_from_config(config):
+    """(rows, cols) from ENV_CONFIG's optional `grid_rows` / `grid_cols` (absent: 5)."""
+    rows, cols = config.getint('grid_rows', fallback=5), config.getint('grid_cols', fallback=5)
+    if rows < 1 or cols < 1 or not 2 <= rows * cols <= N_NODE_MAX:
+        raise _lib.NmarlError('grid_rows x grid_cols must be at least 1 x 1 with 2 <= grid_rows * grid_cols <= %d intersections, '
+                              'got %d x %d' % (N_NODE_MAX, rows, cols))
+    return rows, cols
+
+
+def grid_masks(rows=5, cols=5):
+    """neighbor_mask / distance_mask of large_grid_env.py:58-105 (node i = row * cols + col = nt{i+1}): Manhattan distance 1 /
+    Manhattan distance."""
+    idx = np.arange(rows * cols)
+    r, c = idx // cols, idx % cols
     dist = (np.abs(r[:, None] - r[None, :]) + np.abs(c[:, None] - c[None, :])).astype(int)
     return (dist == 1).astype(int), dist
 
 
-def grid_neighbor_order():
+def grid_neighbor_order(rows=5, cols=5):
     """For every node its neighbours in the order the reference's `neighbor_map` lists them (large_grid_env.py:58-85: north,
-    east, south, west, the absent ones skipped; node i = row * 5 + col = nt{i+1}, north = i + 5).  This -- not the ascending
+    east, south, west, the absent ones skipped; node i = row * cols + col = nt{i+1}, north = i + cols).  This -- not the ascending
     index -- is the order in which an IA2C / IA2C-FP agent's observation concatenates the neighbours' wave vectors and
     fingerprints (atsc_env.py:263-271); neighbour ACTIONS and the MA2C nets' gathers use the mask order (ascending)."""
     out = []
-    for i in range(N_NODE):
-        r, c = divmod(i, 5)
+    for i in range(rows * cols):
+        r, c = divmod(i, cols)
         cand = [(r + 1, c), (r, c + 1), (r - 1, c), (r, c - 1)]
-        out.append([rr * 5 + cc for rr, cc in cand if 0 <= rr < 5 and 0 <= cc < 5])
+        out.append([rr * cols + cc for rr, cc in cand if 0 <= rr < rows and 0 <= cc < cols])
     return out
+
+
+def grid_n_s_ls(agent, neighbor_mask):
+    """Observation width per node: an `ia2c*` agent sees its own and its neighbours' wave vectors, every other its own."""
+    return [N_FEAT * (1 + int(row.sum())) if agent.startswith('ia2c') else N_FEAT for row in np.asarray(neighbor_mask)]
+
+
+def grid_entries(rows=5, cols=5):
+    """The external entries (node, approach, flow group) of a rows x cols lattice, by the rule that yields the reference's twelve
+    at 5x5 (large_grid_data/build_file.py:285-295), in its order: group 0 from the north into approach 0 of the top-row nodes at
+    the interior columns 1..cols-2, group 1 from the west into approach 3 of the first-column nodes at even rows, group 2 from
+    the south into approach 2 of the bottom-row nodes at the interior columns, group 3 from the east into approach 1 of the
+    last-column nodes at even rows.  (What csrc/grid_tile.h evaluates per (node, approach).)"""
+    top, even = (rows - 1) * cols, range(0, rows, 2)
+    return ([(top + c, 0, 0) for c in range(cols - 2, 0, -1)] + [(r * cols, 3, 1) for r in reversed(even)] +
+            [(c, 2, 2) for c in range(1, cols - 1)] + [(r * cols + cols - 1, 1, 3) for r in even])
 
 
 # link -> physical lane (oracle/grid_ref.py LINK_LANE): the 12-wide wave vector counts duplicated lanes (SURVEY.md 8a)
@@ -94,6 +124,12 @@ def grid_params_from_config(config):
 
 
 class LargeGridBatchEnv:
+    rows, cols = 5, 5                 # the reference's lattice unless ENV_CONFIG's grid_rows / grid_cols say otherwise
+
+    @property
+    def entries(self):
+        return grid_entries(self.rows, self.cols)
+
     def __init__(self, config, num_envs=1, device='cuda', env_id_base=0, seed=None):
         self.config = config
         self.E = int(num_envs)
@@ -110,27 +146,29 @@ class LargeGridBatchEnv:
         p = grid_params_from_config(config)
         self.params = p
         self.T = p.T
-        self.n_agent = N_NODE
+        self.rows, self.cols = grid_shape_from_config(config)
+        self.fixed_shape = (self.rows, self.cols) == (5, 5)       # the 5x5 kernels; any other shape: the `_rc` entries
+        N = self.rows * self.cols
+        self.n_agent = N
         self.n_a = N_PHASE
-        self.n_a_ls = [N_PHASE] * N_NODE
-        self.neighbor_mask, self.distance_mask = grid_masks()
-        self.neighbor_order = grid_neighbor_order()
-        self.n_s_ls = [N_FEAT * (1 + int(self.neighbor_mask[i].sum())) if self.agent.startswith('ia2c') else N_FEAT
-                       for i in range(N_NODE)]
+        self.n_a_ls = [N_PHASE] * N
+        self.neighbor_mask, self.distance_mask = grid_masks(self.rows, self.cols)
+        self.neighbor_order = grid_neighbor_order(self.rows, self.cols)
+        self.n_s_ls = grid_n_s_ls(self.agent, self.neighbor_mask)
         self.train_mode = True
         E, d = self.E, self.device
         f32 = dict(dtype=torch.float32, device=d)
-        self.q = torch.zeros(E, N_NODE, 6, **f32)
-        self.transit = torch.zeros(E, N_NODE, 6, **f32)
-        self.prev_action = torch.zeros(E, N_NODE, dtype=torch.uint8, device=d)
+        self.q = torch.zeros(E, N, 6, **f32)
+        self.transit = torch.zeros(E, N, 6, **f32)
+        self.prev_action = torch.zeros(E, N, dtype=torch.uint8, device=d)
         self.t = torch.zeros(E, dtype=torch.int32, device=d)
         self.xi = torch.ones(E, 4, **f32)
         # `wait` / `hybrid` objectives: the front vehicle's standing time per lane (oracle/grid_ref.py step 6)
-        self.head_wait = torch.zeros(E, N_NODE, 6, **f32) if p.objective else None
+        self.head_wait = torch.zeros(E, N, 6, **f32) if p.objective else None
         if self.head_wait is not None:
             p.head_wait = self.head_wait.data_ptr()
-        self.obs = torch.zeros(E, N_NODE, N_OBS, **f32)
-        self.reward = torch.zeros((E, N_NODE) if p.per_agent_reward else (E,), **f32)
+        self.obs = torch.zeros(E, N, N_OBS, **f32)
+        self.reward = torch.zeros((E, N) if p.per_agent_reward else (E,), **f32)
         self.done = torch.zeros(E, dtype=torch.uint8, device=d)
         self.global_reward = torch.zeros(E, **f32)
         self.episode = torch.zeros(E, dtype=torch.int32, device=d)
@@ -143,19 +181,22 @@ class LargeGridBatchEnv:
     compact_obs = False
 
     def set_compact_obs(self, flag=True):
-        """Compact observation [E,25,12]: every node's OWN wave vector -- what the reference hands an MA2C agent
-        (atsc_env.py:253-262) -- instead of the gathered [E,25,60] slab; the consumer gathers the neighbours
+        """Compact observation [E,N,12]: every node's OWN wave vector -- what the reference hands an MA2C agent
+        (atsc_env.py:253-262) -- instead of the gathered [E,N,60] slab; the consumer gathers the neighbours
         (agents/policies.py `_ob_part`).  Batched engine only: the E = 1 reference duck-type keeps the slab."""
         self.compact_obs = bool(flag)
         self.params.compact_obs = 1 if flag else 0
-        self.obs = torch.zeros(self.E, N_NODE, N_FEAT if flag else N_OBS, dtype=torch.float32, device=self.device)
+        self.obs = torch.zeros(self.E, self.n_agent, N_FEAT if flag else N_OBS, dtype=torch.float32, device=self.device)
         return True
 
     def reset(self, mask=None, u0=None):
         P = _lib.ptr
-        rc = _lib.lib.nmarl_grid_reset(ctypes.byref(self.params), self.E, P(mask, torch.uint8), P(u0, torch.float32),
-                                       self.seed, self.env_id_base, P(self.episode), P(self.q), P(self.transit),
-                                       P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
+        args = (ctypes.byref(self.params), self.E, P(mask, torch.uint8), P(u0, torch.float32), self.seed, self.env_id_base,
+                P(self.episode), P(self.q), P(self.transit), P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
+        if self.fixed_shape:
+            rc = _lib.lib.nmarl_grid_reset(*args)
+        else:
+            rc = _lib.lib.nmarl_grid_reset_rc(*args, self.rows, self.cols)
         _lib.check(rc, 'nmarl_grid_reset')
         return self.obs
 
@@ -163,15 +204,18 @@ class LargeGridBatchEnv:
 
     def inkernel_step_supported(self):
         """CommNet's one-launch lock-step can run this env's step as a role of the same launch (csrc/lstm_mfma.hip GENV): compact
-        observation, queue objective, and compute units left idle by the LSTM blocks."""
+        observation, queue objective, the 5x5 lattice (the hand-off words pack 13 + 12 actions), and compute units left idle by
+        the LSTM blocks."""
         from .. import ops
-        return self.compact_obs and not self.params.objective and ops.step_grid_env_blocks(N_NODE, self.E) > 0
+        return (self.fixed_shape and self.compact_obs and not self.params.objective and
+                ops.step_grid_env_blocks(self.n_agent, self.E) > 0)
 
     def inkernel_step(self, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
         """Arguments of `step` for the policy's lock-step launch to run the env step itself, on the actions it draws
         (ops._step_x msg['genv'], nmarl_lstm_step_x with genv): same state tensors, same outputs."""
-        if not self.compact_obs or self.params.objective:
-            raise _lib.NmarlError('the in-launch grid env step writes the compact observation and knows the queue objective')
+        if not self.fixed_shape or not self.compact_obs or self.params.objective:
+            raise _lib.NmarlError('the in-launch grid env step writes the compact observation and knows the queue objective on '
+                                  'the 5x5 lattice')
         if self._words is None:          # hand-off words of the launch ([E][2] u64): zeroed once, every launch leaves them zero
             self._words = torch.zeros(_lib.lib.nmarl_lstm_step_grid_words(self.E), dtype=torch.int64, device=self.device)
         return dict(params=self.params, q=self.q, transit=self.transit, prev_action=self.prev_action, t=self.t, xi=self.xi,
@@ -191,11 +235,13 @@ class LargeGridBatchEnv:
         reward = self.reward if reward_out is None else reward_out
         done = self.done if done_out is None else done_out
         greward = self.global_reward if greward_out is None else greward_out
-        rc = _lib.lib.nmarl_grid_step(ctypes.byref(self.params), self.E, P(action, torch.uint8), P(self.q),
-                                      P(self.transit), P(self.prev_action), P(self.t), P(self.xi),
-                                      P(obs, torch.float32), P(reward, torch.float32), P(done, torch.uint8),
-                                      P(greward, torch.float32), 1 if auto_reset else 0, self.seed,
-                                      self.env_id_base, P(self.episode), _lib.stream())
+        args = (ctypes.byref(self.params), self.E, P(action, torch.uint8), P(self.q), P(self.transit), P(self.prev_action),
+                P(self.t), P(self.xi), P(obs, torch.float32), P(reward, torch.float32), P(done, torch.uint8),
+                P(greward, torch.float32), 1 if auto_reset else 0, self.seed, self.env_id_base, P(self.episode), _lib.stream())
+        if self.fixed_shape:
+            rc = _lib.lib.nmarl_grid_step(*args)
+        else:
+            rc = _lib.lib.nmarl_grid_step_rc(*args, self.rows, self.cols)
         _lib.check(rc, 'nmarl_grid_step')
         return obs, reward, done, greward
 
@@ -209,6 +255,7 @@ class LargeGridEnv:
     def __init__(self, config, port=0, device='cuda', **_):
         self.batch = LargeGridBatchEnv(config, num_envs=1, device=device)
         b = self.batch
+        self.rows, self.cols = b.rows, b.cols
         self.name, self.agent, self.coop_gamma, self.T = b.name, b.agent, b.coop_gamma, b.T
         self.n_agent, self.n_a, self.n_a_ls, self.n_s_ls = b.n_agent, b.n_a, b.n_a_ls, b.n_s_ls
         self.neighbor_mask, self.distance_mask = b.neighbor_mask, b.distance_mask

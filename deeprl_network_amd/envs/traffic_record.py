@@ -36,16 +36,17 @@ def net_mult(n_s_ls, L):
     return (np.arange(L)[None, :] < np.asarray(n_s_ls)[:, None]).astype(np.int32)
 
 
-def grid_demand(peak1, peak2):
-    """[4,12] f64 veh/h: 3 entries per flow group x the per-entry rate of large_grid_data/build_file.py:296-321 (what
-    csrc/grid_tile.h demand_rate evaluates): first wave in pieces 0..6, second wave, from 900 s, in pieces 3..9."""
+def grid_demand(peak1, peak2, n_entry=(3, 3, 3, 3)):
+    """[4,12] f64 veh/h: the flow group's entries (3 each on the 5x5 grid; `n_entry` per group for another shape) x the
+    per-entry rate of large_grid_data/build_file.py:296-321 (what csrc/grid_tile.h demand_rate evaluates): first wave in pieces
+    0..6, second wave, from 900 s, in pieces 3..9."""
     d = np.zeros((N_GROUP, N_PIECE))
     for g in range(N_GROUP):
         for p in range(N_PIECE):
             if g < 2 and p < 7:
-                d[g, p] = 3.0 * (peak1 * (0.6 if g == 0 else 1.0) * _GRID_RATIOS1[p])
+                d[g, p] = float(n_entry[g]) * (peak1 * (0.6 if g == 0 else 1.0) * _GRID_RATIOS1[p])
             elif g >= 2 and 3 <= p < 10:
-                d[g, p] = 3.0 * (peak2 * (0.6 if g == 2 else 1.0) * _GRID_RATIOS2[p - 3])
+                d[g, p] = float(n_entry[g]) * (peak2 * (0.6 if g == 2 else 1.0) * _GRID_RATIOS2[p - 3])
     return d
 
 
@@ -62,7 +63,8 @@ class TrafficRecorder:
         from .real_net_env import RealNetBatchEnv
         if isinstance(batch_env, LargeGridBatchEnv):
             mult = grid_mult(batch_env.n_agent)
-            demand = grid_demand(float(batch_env.params.peak1), float(batch_env.params.peak2))
+            n_entry = [sum(1 for e in batch_env.entries if e[2] == g) for g in range(N_GROUP)]
+            demand = grid_demand(float(batch_env.params.peak1), float(batch_env.params.peak2), n_entry)
         elif isinstance(batch_env, RealNetBatchEnv):
             mult = net_mult(batch_env.topo.n_s_ls, batch_env.topo.L)
             demand = net_demand(float(batch_env.params.flow_rate))

@@ -172,6 +172,7 @@ int nmarl_cacc_reset_nv(const nmarl_cacc_params_t* p, int64_t E,
 #define NMARL_GRID_NF 12      /* wave features = signal links per node (:25-26)         */
 #define NMARL_GRID_OBS 60     /* own 12 + 4 neighbour slots (ascending index, 0 padded) */
 #define NMARL_GRID_LANES 6    /* physical incoming lanes per node                       */
+#define NMARL_GRID_N_MAX 32   /* nmarl_grid_*_rc: rows x cols lattices of 2..32 nodes   */
 
 typedef struct nmarl_grid_params {
     float norm_wave;          /* atsc_env.py:91-92                                       */
@@ -211,6 +212,24 @@ int nmarl_grid_step(const nmarl_grid_params_t* p, int64_t E, const uint8_t* acti
                     float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
                     float* reward, uint8_t* done, float* global_reward, int32_t auto_reset,
                     uint64_t seed, int64_t env_id_base, int32_t* episode, void* stream);
+/*
+ * The same two calls for a rows x cols lattice (rows >= 1, cols >= 1, 2 <= rows * cols <= NMARL_GRID_N_MAX, else NMARL_EINVAL):
+ * N = rows * cols nodes, node i = row * cols + col (row 0 at the bottom), neighbours N = i + cols, E = i + 1, S = i - cols,
+ * W = i - 1; per-node model and arguments as above with every 25 read as N (q, transit, head_wait [E,N,6]; prev_action, action
+ * [E,N]; obs [E,N,60] or [E,N,12]; reward [E] or [E,N]), all dense.  External entries (flow group -> approach): 0 from the north
+ * into the top-row nodes at columns 1..cols-2, 2 from the south into the bottom-row nodes at the same columns, 1 from the west
+ * into the first-column nodes at even rows, 3 from the east into the last-column nodes at even rows; per-entry rates and xi as
+ * above.  rows = cols = 5 is the model of nmarl_grid_step (bit-identical results, on the runtime-shape kernel).
+ */
+int nmarl_grid_reset_rc(const nmarl_grid_params_t* p, int64_t E, const uint8_t* mask, const float* u0,
+                        uint64_t seed, int64_t env_id_base, int32_t* episode, float* q, float* transit,
+                        uint8_t* prev_action, int32_t* t, float* xi, float* obs, void* stream,
+                        int32_t rows, int32_t cols);
+int nmarl_grid_step_rc(const nmarl_grid_params_t* p, int64_t E, const uint8_t* action, float* q,
+                       float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
+                       float* reward, uint8_t* done, float* global_reward, int32_t auto_reset,
+                       uint64_t seed, int64_t env_id_base, int32_t* episode, void* stream,
+                       int32_t rows, int32_t cols);
 
 /* ------------------------------------------------------------------------- */
 /* Synthetic signalised NETWORK with heterogeneous intersections -- contract   */
