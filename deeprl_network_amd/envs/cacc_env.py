@@ -57,6 +57,29 @@ def line_graph(n):
     return (dist == 1).astype(int), dist
 
 
+def cacc_traffic_table(hist, rewards, episode, dt, n_agent):
+    """One episode's traffic table with the column set of cacc_env.py:90-109.  hist: the physical state (h, v, u) after the
+    reset and after every step, [steps + 1, 3, N]; rewards: 0 for the reset row, then every step's global reward."""
+    hist = np.array(hist)
+    hs, vs, us = hist[:, 0], hist[:, 1], hist[:, 2]
+    df = pd.DataFrame()
+    df['episode'] = np.ones(len(hs)) * episode
+    df['time_sec'] = np.arange(len(hs)) * dt
+    df['reward'] = np.array(rewards)
+    df['lead_headway_m'] = hs[:, 0]
+    df['avg_headway_m'] = np.mean(hs[:, 1:], axis=1)
+    df['std_headway_m'] = np.std(hs[:, 1:], axis=1)
+    df['avg_speed_mps'] = np.mean(vs, axis=1)
+    df['std_speed_mps'] = np.std(vs, axis=1)
+    df['avg_accel_mps2'] = np.mean(us, axis=1)
+    df['std_accel_mps2'] = np.std(us, axis=1)
+    for i in range(n_agent):
+        df['headway_%d_m' % (i + 1)] = hs[:, i]
+        df['velocity_%d_mps' % (i + 1)] = vs[:, i]
+        df['accel_%d_mps2' % (i + 1)] = us[:, i]
+    return df
+
+
 class CACCBatchEnv:
     """E independent platoons stepped in lock-step on one GPU.
 
@@ -342,24 +365,7 @@ class CACCEnv:
 
     def _log_traffic_data(self):
         """Per-episode traffic table with the column set of cacc_env.py:90-109."""
-        hist = np.array(self._hist)
-        hs, vs, us = hist[:, 0], hist[:, 1], hist[:, 2]
-        df = pd.DataFrame()
-        df['episode'] = np.ones(len(hs)) * self.cur_episode
-        df['time_sec'] = np.arange(len(hs)) * self.dt
-        df['reward'] = np.array(self._rewards)
-        df['lead_headway_m'] = hs[:, 0]
-        df['avg_headway_m'] = np.mean(hs[:, 1:], axis=1)
-        df['std_headway_m'] = np.std(hs[:, 1:], axis=1)
-        df['avg_speed_mps'] = np.mean(vs, axis=1)
-        df['std_speed_mps'] = np.std(vs, axis=1)
-        df['avg_accel_mps2'] = np.mean(us, axis=1)
-        df['std_accel_mps2'] = np.std(us, axis=1)
-        for i in range(self.n_agent):
-            df['headway_%d_m' % (i + 1)] = hs[:, i]
-            df['velocity_%d_mps' % (i + 1)] = vs[:, i]
-            df['accel_%d_mps2' % (i + 1)] = us[:, i]
-        self.traffic_data.append(df)
+        self.traffic_data.append(cacc_traffic_table(self._hist, self._rewards, self.cur_episode, self.dt, self.n_agent))
 
     def output_data(self):
         if not self.is_record:

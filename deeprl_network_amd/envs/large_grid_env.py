@@ -104,6 +104,21 @@ class LargeGridController:
         return True
 
 
+# the five phases of LargeGridController.greedy as sets of lanes [N, E lane 0, E lane 1, S, W lane 0, W lane 1] (large_grid_env.py:25-26)
+_GREEDY_PHASE_LANES = ((0, 3), (2, 5), (1, 4), (1, 2), (4, 5))
+
+
+def grid_greedy_table(rows=5, cols=5):
+    """(n_a [N] i32, mask [N,8] u32) of nmarl_atsc_greedy for a rows x cols grid: bit k of mask[i][a] = feature k of the node's
+    wave vector counts for phase a.  The lanes are read at their first links, so the five bit sets are {0,6}, {5,11}, {3,9},
+    {3,5}, {9,11} -- what LargeGridController.greedy adds -- and every node of any shape has the same."""
+    N = rows * cols
+    mask = np.zeros((N, 8), dtype=np.uint32)
+    for a, lanes in enumerate(_GREEDY_PHASE_LANES):
+        mask[:, a] = sum(1 << _LANE_FIRST_LINK[lane] for lane in lanes)
+    return np.full(N, N_PHASE, dtype=np.int32), mask
+
+
 def grid_params_from_config(config):
     """ENV_CONFIG section -> nmarl_grid_params_t; keys of atsc_env.py:79-99 + large_grid_env.py:50-52."""
     if config.getint('control_interval_sec') != 5 or config.getint('yellow_interval_sec') != 2:
@@ -199,6 +214,23 @@ class LargeGridBatchEnv:
             rc = _lib.lib.nmarl_grid_reset_rc(*args, self.rows, self.cols)
         _lib.check(rc, 'nmarl_grid_reset')
         return self.obs
+
+    def reset_replica(self, e, seed):
+        """Replica e alone, to the state the one-replica env takes for this seed (`LargeGridEnv.reset`: Philox key = seed, env id
+        0, episode 0): the reset entry point on the replica's contiguous slices, E = 1.  A batch whose replicas are the test
+        seeds of an evaluation starts every one of them where the E = 1 path starts it, whatever its position in the batch."""
+        P, s = _lib.ptr, slice(e, e + 1)
+        p = _lib.GridParams.from_buffer_copy(self.params)
+        if self.head_wait is not None:
+            p.head_wait = self.head_wait[s].data_ptr()
+        self.episode[s].zero_()
+        args = (ctypes.byref(p), 1, None, None, int(seed), 0, P(self.episode[s]), P(self.q[s]), P(self.transit[s]),
+                P(self.prev_action[s]), P(self.t[s]), P(self.xi[s]), P(self.obs[s]), _lib.stream())
+        if self.fixed_shape:
+            rc = _lib.lib.nmarl_grid_reset(*args)
+        else:
+            rc = _lib.lib.nmarl_grid_reset_rc(*args, self.rows, self.cols)
+        _lib.check(rc, 'nmarl_grid_reset')
 
     _words = None
 

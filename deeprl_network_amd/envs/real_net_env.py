@@ -94,6 +94,20 @@ class RealNetController:
         return True
 
 
+def net_greedy_table(node_names):
+    """(n_a [N] i32, mask [N,8] u32) of nmarl_atsc_greedy for the network's nodes in the given order: bit k of mask[i][a] is set
+    where link k of node i shows the capital 'G' in phase a -- the links RealNetController.greedy adds."""
+    key = {name: k for name, k, _ in NODE_DEFS}
+    n_a = np.zeros(len(node_names), dtype=np.int32)
+    mask = np.zeros((len(node_names), 8), dtype=np.uint32)
+    for i, name in enumerate(node_names):
+        phases = PHASE_SETS[key[name]]
+        n_a[i] = len(phases)
+        for a, phase in enumerate(phases):
+            mask[i, a] = sum(1 << k for k, signal in enumerate(phase) if signal == 'G')
+    return n_a, mask
+
+
 class NetTopology:
     """Static arrays of the network (host NumPy + device copies + the nmarl_net_topo_t handed to the kernels)."""
 
@@ -269,6 +283,20 @@ class RealNetBatchEnv:
         else:                                                            # the same reset, which also clears head_wait
             _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(self.params), *args), 'nmarl_net_reset_obj')
         return self.obs
+
+    def reset_replica(self, e, seed):
+        """Replica e alone, to the state the one-replica env takes for this seed (`RealNetEnv.reset`: Philox key = seed, env id 0,
+        episode 0): the reset entry point on the replica's contiguous slices, E = 1."""
+        P, s = _lib.ptr, slice(e, e + 1)
+        self.episode[s].zero_()
+        args = (ctypes.byref(self.topo.c), 1, None, None, int(seed), 0, P(self.episode[s]), P(self.q[s]), P(self.transit[s]),
+                P(self.prev_action[s]), P(self.t[s]), P(self.xi[s]), P(self.obs[s]), _lib.stream())
+        if self.head_wait is None:
+            _lib.check(_lib.lib.nmarl_net_reset(*args), 'nmarl_net_reset')
+        else:
+            p = _lib.NetParams.from_buffer_copy(self.params)
+            p.head_wait = self.head_wait[s].data_ptr()
+            _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(p), *args), 'nmarl_net_reset_obj')
 
     def step(self, action, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
         P = _lib.ptr

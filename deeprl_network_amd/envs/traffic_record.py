@@ -124,6 +124,20 @@ class TrafficRecorder:
                 'wait_step': cum[:, 3] / DT / done, 'wait_sec': cum[:, 3] / done}
 
 
+def traffic_rows(rec, episode):
+    """One replica's record rec [steps, 8] f32 -> its rows of `_traffic.csv` (atsc_env.py:490-499), in step order."""
+    out = []
+    for row in np.asarray(rec).astype(np.float64):
+        cur = dict(zip(TRAFFIC_COLUMNS, row.tolist()))
+        out.append({'episode': episode, 'time_sec': int(cur.pop('time_sec')), **cur})
+    return out
+
+
+def trip_row(trip, e, episode):
+    """Replica e of `TrafficRecorder.trip()` -> its row of `_trip.csv` (atsc_env.py:113-120)."""
+    return {'episode': episode, 'id': 'fluid', **{k: trip[k][e].item() for k in TRIP_COLUMNS[2:]}}
+
+
 class EpisodeRecord:
     """What LargeGridEnv / RealNetEnv (one replica) share: the recorder next to `control_data`, and the two tables."""
 
@@ -145,11 +159,8 @@ class EpisodeRecord:
         if self.slot == 0:
             return
         episode = self.env.cur_episode
-        for row in self.recorder.rows()[:self.slot, 0].astype(np.float64):
-            cur = dict(zip(TRAFFIC_COLUMNS, row.tolist()))
-            traffic_data.append({'episode': episode, 'time_sec': int(cur.pop('time_sec')), **cur})
-        trip = self.recorder.trip()
-        trip_data.append({'episode': episode, 'id': 'fluid', **{k: trip[k][0].item() for k in TRIP_COLUMNS[2:]}})
+        traffic_data.extend(traffic_rows(self.recorder.rows()[:self.slot, 0], episode))
+        trip_data.append(trip_row(self.recorder.trip(), 0, episode))
         self.slot = 0
 
 

@@ -9,9 +9,10 @@ import torch
 
 from .agents.models import IA2C, IA2C_CU, IA2C_FP, MA2C_DIAL, MA2C_IC3, MA2C_NC
 from .envs import init_env, make_batch_env
+from .envs.greedy import GreedyBatchController
 from .envs.large_grid_env import LargeGridController
 from .envs.real_net_env import RealNetController
-from .utils import (BatchedTrainer, Counter, Evaluator, SummaryWriter, Trainer, check_dir, copy_file, find_file,
+from .utils import (BatchedEvaluator, BatchedTrainer, Counter, Evaluator, SummaryWriter, Trainer, check_dir, copy_file, find_file,
                     init_dir, init_log)
 
 AGENTS = {'ia2c': IA2C, 'ia2c_fp': IA2C_FP, 'ma2c_nc': MA2C_NC, 'ma2c_ic3': MA2C_IC3, 'ma2c_cu': IA2C_CU,
@@ -34,6 +35,8 @@ def parse_args(argv=None):
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
                     help='random seeds for evaluation, split by ,')
+    sp.add_argument('--batched', action='store_true',
+                    help='all evaluation seeds as the replicas of one device-resident batch (BatchedEvaluator); same CSVs')
     sp.add_argument('--demo', action='store_true', help='kept for CLI compatibility (no SUMO gui here)')
     args = parser.parse_args(argv)
     if not args.option:
@@ -130,6 +133,11 @@ def _open_run(run_dir):
     return cfg
 
 
+def model_config(cfg):
+    """The run's MODEL_CONFIG section; None where the ini has none (config_greedy.ini: the rule-based agent reads no model keys)."""
+    return cfg['MODEL_CONFIG'] if cfg.has_section('MODEL_CONFIG') else None
+
+
 def evaluate(args):
     """`main.py evaluate` (reference main.py:112-155): the run under --base-dir is rebuilt from its own ini, its newest checkpoint
     loaded, and the Evaluator replays the test seeds into <run>/eva_data (port 1, no GUI: the synthetic envs have neither)."""
@@ -141,12 +149,33 @@ def evaluate(args):
     cfg = _open_run(run_dir)
     if cfg is None:
         return
+    if args.batched:
+        return evaluate_batched(cfg, seeds, run_dir, out['eva_data'])
     env = init_env(cfg['ENV_CONFIG'], port=1)
     env.init_test_seeds(seeds)
-    model = init_agent(env, cfg['MODEL_CONFIG'], 0, 0)
+    model = init_agent(env, model_config(cfg), 0, 0)
     if model is None or not model.load(os.path.join(run_dir, 'model') + '/'):
         return
     Evaluator(env, model, out['eva_data'], gui=False).run()
+
+
+def evaluate_batched(cfg, seeds, run_dir, output_path):
+    """`main.py evaluate --batched`: the seeds are the replicas of one batch env, the policy is built for that many replicas (or
+    is the batched greedy controller), and BatchedEvaluator writes the CSVs the loop above writes.  A scenario / agent pair the
+    batch engine cannot build raises the engine's own error."""
+    E = len(seeds)
+    if E < 1:
+        logging.error('Evaluation: no evaluation seeds')
+        return None
+    env_cfg = cfg['ENV_CONFIG']
+    env = make_batch_env(env_cfg, num_envs=E)
+    if env.agent == 'greedy':
+        model = GreedyBatchController(env)
+    else:
+        model = init_agent(env, model_config(cfg), 0, 0, num_envs=E)
+    if model is None or not model.load(os.path.join(run_dir, 'model') + '/'):
+        return None
+    return BatchedEvaluator(env, model, seeds, output_path).run()
 
 
 def main(argv=None):

@@ -1732,6 +1732,22 @@ def sample_actions(pi, out, mode, u=None, seed=0, env_id_base=0, step=0, step_de
     return out
 
 
+def atsc_greedy(n_a, mask, obs, out, a_max=8):
+    """nmarl_atsc_greedy: the rule-based ATSC agent for every (replica, node) in one launch.  n_a [N] i32 and mask [N,8] i32
+    (bit k of mask[i][a]: feature k counts for phase a of node i) are the scenario's table (envs/large_grid_env.py
+    grid_greedy_table, envs/real_net_env.py net_greedy_table); obs [E,N,obs_row] f32 is an env's observation buffer, whose rows
+    lead with the node's own wave vector; out [E,N] u8 receives the actions; a_max: an upper bound of n_a (phases at or above it are
+    not evaluated)."""
+    if obs.dim() != 3 or tuple(out.shape) != tuple(obs.shape[:2]) or tuple(mask.shape) != (obs.shape[1], 8) or \
+            tuple(n_a.shape) != (obs.shape[1],):
+        raise _lib.NmarlError('atsc_greedy: obs [E,N,row], out [E,N], n_a [N], mask [N,8] (got %s, %s, %s, %s)'
+                              % (tuple(obs.shape), tuple(out.shape), tuple(n_a.shape), tuple(mask.shape)))
+    E, N, row = obs.shape
+    check(lib.nmarl_atsc_greedy(E, N, int(a_max), ptr(n_a, torch.int32), ptr(mask, torch.int32), ptr(obs, F32), row,
+                                ptr(out, torch.uint8), stream()), 'nmarl_atsc_greedy')
+    return out
+
+
 A2C_LOSS_MAX_A = 8
 
 

@@ -675,28 +675,19 @@ class BatchedTrainer:
         done straight into per-step slots.  The episode statistics (alive mask, sums, action histogram) are formed from those
         slots after the last step instead of ~10 elementwise launches per step."""
         from .envs import make_batch_env
-        dev, model, N = self.device, self.model, self.N
+        dev, model = self.device, self.model
         env = make_batch_env(self.env.config, num_envs=n_envs, device=dev, seed=seed, env_id_base=10 ** 9)
         env.train_mode = False
-        T, A, p = env.T, model.n_a, model.policy
+        T, A = env.T, model.n_a
         f64 = dict(dtype=torch.float64, device=dev)
-        hs = [torch.zeros(N, n_envs, model.n_lstm, device=dev) for _ in range(2)]      # ping-pong: a coupled net's message term
-        cs = [torch.zeros(N, n_envs, model.n_lstm, device=dev) for _ in range(2)]      # reads the others' h while h' is written
-        fps = [model.fp_uniform.expand(N, n_envs, A).clone() for _ in range(2)]
-        done1, done0 = torch.ones(n_envs, device=dev), torch.zeros(n_envs, device=dev)
-        acts = torch.zeros(T, n_envs, N, dtype=torch.uint8, device=dev)
-        G = torch.zeros(T, n_envs, device=dev)
-        D = torch.zeros(T, n_envs, dtype=torch.uint8, device=dev)
-        rew = torch.zeros_like(env.reward)
+        steps_ = _PolicyLockSteps(env, model)
+        acts, G, D = steps_.acts, steps_.G, steps_.D
         total, steps, hist = torch.zeros(n_envs, **f64), torch.zeros(n_envs, **f64), torch.zeros(A, **f64)
         a_ids = torch.arange(A, device=dev).view(1, 1, 1, -1)
-        fused = p.fused_heads
 
         def prepare():
             env.episode.zero_()                       # the same test episode every time
-            hs[0].zero_()
-            cs[0].zero_()
-            fps[0].copy_(model.fp_uniform.expand_as(fps[0]))
+            steps_.prepare()
 
         def episode():
             # (captured: launches of this library only -- the state resets in front and the statistics behind run eagerly around
@@ -704,19 +695,7 @@ class BatchedTrainer:
             # replayed its reductions on stale data once the trainer's own graphs existed: the episode's reward sums came out
             # right and the action histogram did not (seen in round 5's learning runs; tests/test_gpu_trainer.py pins it).)
             env.reset()
-            p.refresh_wimage()
-            for t in range(T):
-                a, b = t & 1, (t + 1) & 1
-                enc = p.encode(env.obs, fps[a])
-                if fused:
-                    p.step_policy(enc, hs[a], cs[a], done1 if t == 0 else done0, hs[b], cs[b], fps[b], acts[t], t > 0,
-                                  mode=ops.SAMPLE_ARGMAX)
-                else:
-                    p.step(enc, hs[a], cs[a], done1 if t == 0 else done0, hs[b], cs[b], t > 0)
-                    with torch.no_grad():
-                        fps[b].copy_(p.pi(hs[b]))
-                    ops.sample_actions(fps[b], acts[t], ops.SAMPLE_ARGMAX)
-                env.step(acts[t], reward_out=rew, done_out=D[t], greward_out=G[t])
+            steps_.run()
 
         def statistics():
             # alive[t] = no `done` before step t; an episode's statistics stop with its first done
@@ -791,3 +770,266 @@ class BatchedTrainer:
             log_row(final=True)                           # final row: never leave train_reward.csv empty / without a test
         if self.output_path is not None and self.rank == 0:
             pd.DataFrame(self.data).to_csv(self.output_path + 'train_reward.csv')
+
+
+# ------------------------------------------------------------------ test episodes of E replicas without host synchronisation
+class _PolicyLockSteps:
+    """The T lock-steps of a test episode of `env`'s E replicas under a learned policy, ~4 launches each: encoder, ONE fused
+    kernel for LSTM step + actor head + action choice (the rollout's policy-step kernel; its policy output IS the next
+    fingerprint), env step writing done / global reward straight into per-step slots.  Owns the ping-pong recurrent state and
+    fingerprints (a coupled net's message term reads the others' h while h' is written) and the per-step slots acts [T,E,N] u8,
+    G [T,E] f32, D [T,E] u8.  Shared by BatchedTrainer's in-training test (arg max) and BatchedEvaluator (arg max on CACC,
+    supplied uniforms on ATSC); launches of this library only, so `run` may be captured."""
+
+    def __init__(self, env, model):
+        self.env, self.model = env, model
+        dev, N, E, T, A = env.device, env.n_agent, env.E, env.T, model.n_a
+        self.hs = [torch.zeros(N, E, model.n_lstm, device=dev) for _ in range(2)]
+        self.cs = [torch.zeros(N, E, model.n_lstm, device=dev) for _ in range(2)]
+        self.fps = [model.fp_uniform.expand(N, E, A).clone() for _ in range(2)]
+        self.done1, self.done0 = torch.ones(E, device=dev), torch.zeros(E, device=dev)
+        self.acts = torch.zeros(T, E, N, dtype=torch.uint8, device=dev)
+        self.G = torch.zeros(T, E, device=dev)
+        self.D = torch.zeros(T, E, dtype=torch.uint8, device=dev)
+        self.rew = torch.zeros_like(env.reward)
+
+    def prepare(self):
+        """A fresh episode: zero recurrent state, uniform fingerprints (eager fills: outside any capture)."""
+        self.hs[0].zero_()
+        self.cs[0].zero_()
+        self.fps[0].copy_(self.model.fp_uniform.expand_as(self.fps[0]))
+
+    def run(self, uniforms=None, after_step=None):
+        """uniforms [T,E,N] f32: the actions are drawn from them (SAMPLE_UNIFORM); None: arg max.  after_step(t): launches
+        behind lock-step t's env step."""
+        env, p = self.env, self.model.policy
+        hs, cs, fps = self.hs, self.cs, self.fps
+        fused = p.fused_heads
+        p.refresh_wimage()
+        for t in range(env.T):
+            a, b = t & 1, (t + 1) & 1
+            draw = dict(mode=ops.SAMPLE_ARGMAX) if uniforms is None else dict(mode=ops.SAMPLE_UNIFORM, u=uniforms[t])
+            enc = p.encode(env.obs, fps[a])
+            if fused:
+                p.step_policy(enc, hs[a], cs[a], self.done1 if t == 0 else self.done0, hs[b], cs[b], fps[b], self.acts[t], t > 0,
+                              **draw)
+            else:
+                p.step(enc, hs[a], cs[a], self.done1 if t == 0 else self.done0, hs[b], cs[b], t > 0)
+                with torch.no_grad():
+                    fps[b].copy_(p.pi(hs[b]))
+                ops.sample_actions(fps[b], self.acts[t], **draw)
+            env.step(self.acts[t], reward_out=self.rew, done_out=self.D[t], greward_out=self.G[t])
+            if after_step is not None:
+                after_step(t)
+
+
+class _GreedyLockSteps:
+    """The same T lock-steps under the rule-based controller: one nmarl_atsc_greedy launch on the env's observation buffer,
+    then the env step."""
+
+    def __init__(self, env, controller):
+        self.env, self.controller = env, controller
+        dev, N, E, T = env.device, env.n_agent, env.E, env.T
+        self.acts = torch.zeros(T, E, N, dtype=torch.uint8, device=dev)
+        self.G = torch.zeros(T, E, device=dev)
+        self.D = torch.zeros(T, E, dtype=torch.uint8, device=dev)
+        self.rew = torch.zeros_like(env.reward)
+
+    def prepare(self):
+        return
+
+    def run(self, uniforms=None, after_step=None):
+        env = self.env
+        for t in range(env.T):
+            self.controller.forward_batch(env.obs, self.acts[t])
+            env.step(self.acts[t], reward_out=self.rew, done_out=self.D[t], greward_out=self.G[t])
+            if after_step is not None:
+                after_step(t)
+
+
+def cacc_eval_u0(seeds, run_seed=1):
+    """seeds -> u0 [E] f64, the initial-condition uniform of every CACC test episode as the one-replica path draws it
+    (CACCEnv.reset): np.random.seed(seed); rand().  The condition of that reset is kept -- the episode whose running env seed
+    (`run_seed` + its 1-based number) is 0 takes 0.5 instead --; for every other episode the value depends on its seed alone."""
+    return np.array([np.random.RandomState(s).rand() if run_seed + e + 1 else 0.5 for e, s in enumerate(seeds)], dtype=np.float64)
+
+
+def eval_uniforms(seeds, T, N):
+    """seeds -> u [T,E,N] f32 with u[t, e, :] = RandomState(seeds[e]).random_sample((T, N))[t]: the uniforms a batched ATSC
+    evaluation draws its actions from (ops.SAMPLE_UNIFORM).  A replica's stream depends on its seed alone -- not on its position in
+    the batch, not on E."""
+    u = np.empty((T, len(seeds), N), dtype=np.float32)
+    for e, s in enumerate(seeds):
+        u[:, e, :] = np.random.RandomState(s).random_sample((T, N))
+    return u
+
+
+def eval_row_counts(D):
+    """D [T,E] done flags -> (rows [E]: steps up to and including the replica's first done, T if it has none; finished [E])."""
+    D = np.asarray(D) != 0
+    finished = D.any(axis=0)
+    return np.where(finished, D.argmax(axis=0) + 1, D.shape[0]).astype(np.int64), finished
+
+
+def eval_control_rows(acts, G, rows, atsc, dt):
+    """The rows of `_control.csv` from the per-step buffers acts [T,E,N], G [T,E], in the one-replica writers' form
+    (LargeGridEnv / RealNetEnv / CACCEnv.step): episode e + 1; after lock-step k the env's clock stands at k + 1 steps -- ATSC:
+    time_sec = 5 (k + 1) as int, step = time_sec / 5; CACC: time_sec = (k + 1) dt, step = k + 1."""
+    out = []
+    for e, n in enumerate(rows):
+        for k in range(int(n)):
+            if atsc:
+                sec = (k + 1) * int(dt)
+                when = {'time_sec': sec, 'step': sec / int(dt)}
+            else:
+                when = {'time_sec': (k + 1) * dt, 'step': k + 1}
+            out.append({'episode': e + 1, **when, 'action': ','.join('%d' % x for x in acts[k, e]), 'reward': float(G[k, e])})
+    return out
+
+
+def eval_cacc_traffic(hist, G, rows, finished, dt):
+    """hist [T+1,E,3,N] f32 (h, v, u after the reset and after every step), G [T,E] -> one table per replica that reached a
+    done, cut at it: the statements of CACCEnv._log_traffic_data (envs.cacc_env.cacc_traffic_table)."""
+    from .envs.cacc_env import cacc_traffic_table
+    out = []
+    for e, n in enumerate(rows):
+        if finished[e]:
+            n = int(n)
+            out.append(cacc_traffic_table(np.asarray(hist[:n + 1, e]).astype(np.float64), [0] + [float(g) for g in G[:n, e]],
+                                          e + 1, dt, hist.shape[3]))
+    return out
+
+
+def eval_atsc_tables(rec, trip, rows):
+    """rec [T,E,8] = TrafficRecorder.rows(), trip = TrafficRecorder.trip() -> (traffic rows, trip rows) in seed order, with the
+    column handling of EpisodeRecord.collect."""
+    from .envs.traffic_record import traffic_rows, trip_row
+    traffic, trips = [], []
+    for e, n in enumerate(rows):
+        traffic.extend(traffic_rows(rec[:int(n), e], e + 1))
+        trips.append(trip_row(trip, e, e + 1))
+    return traffic, trips
+
+
+class BatchedEvaluator:
+    """`main.py evaluate --batched`: all test seeds as the replicas of ONE batch env (replica e = seeds[e]), nothing read back
+    until the episode is over, then the CSVs of the one-replica `Evaluator` (same names, columns, row order).
+
+      * initial state: the one-replica path's, bit for bit -- ATSC: every replica reset alone with Philox key = its seed, env id
+        0, episode 0 (`reset_replica`); CACC: one reset launch with u0[e] = RandomState(seeds[e]).rand() (`cacc_eval_u0`);
+      * policy: arg max on CACC, as `perform`; on ATSC the stochastic on-policy draw from SUPPLIED uniforms (`eval_uniforms`,
+        uploaded once) -- a stream of its own, comparable to the one-replica path's unseeded host np.random.choice in
+        distribution only; `agent = greedy`: nmarl_atsc_greedy on the env's observation buffer (the grid) or on the
+        own vectors staged from it (the network, whose rows are no multiple of 16 bytes: GreedyBatchController);
+      * per lock-step: policy step (or greedy launch), env step without auto-reset writing D[t] / G[t], on ATSC the traffic
+        recorder's launch, on CACC one copy of (h, v, u) into hist[t + 1];
+      * afterwards: one copy of each buffer to the host; a replica's rows stop with its first done.
+    env: make_batch_env(..., num_envs=len(seeds)); model: a policy built with num_envs=len(seeds), or GreedyBatchController.
+    use_graph: the T lock-steps as one captured hipGraph (launches of this library only inside, plus the network controller's
+    staging copy, a torch kernel node); eager is the default and, as measured, no slower (profiles/r15_batched_evaluate.txt)."""
+
+    def __init__(self, env, model, seeds, output_path, use_graph=False):
+        self.env, self.model, self.seeds, self.output_path = env, model, [int(s) for s in seeds], output_path
+        if env.E != len(self.seeds):
+            raise ValueError('the batch env has %d replicas for %d evaluation seeds' % (env.E, len(self.seeds)))
+        self.atsc = env.name.startswith('atsc')
+        self.greedy = hasattr(model, 'forward_batch')
+        if self.greedy and not self.atsc:
+            raise ValueError('the greedy agent is defined for the ATSC scenarios')
+        env.train_mode = False
+        self.use_graph = bool(use_graph) and env.device.type == 'cuda'
+        self.graph = None
+        dev, E, T, N = env.device, env.E, env.T, env.n_agent
+        self.steps = _GreedyLockSteps(env, model) if self.greedy else _PolicyLockSteps(env, model)
+        self.uniforms = None
+        if self.atsc and not self.greedy:
+            self.uniforms = torch.from_numpy(eval_uniforms(self.seeds, T, N)).to(dev)
+        self.recorder = self.hist = None
+        if self.atsc:
+            from .envs.traffic_record import TrafficRecorder
+            self.recorder = TrafficRecorder(env, T)
+            self.dt = env.config.getint('control_interval_sec')
+        else:
+            # (h, v, u) after the reset and after every step; [T+1,3,E,N] on the device, so that a slot takes the env's three
+            # contiguous arrays in one copy launch, handed to the tables as hist [T+1,E,3,N]
+            self.hist = torch.zeros(T + 1, 3, E, N, dtype=torch.float32, device=dev)
+            self.dt = env.dt
+
+    def _phys(self, slot):
+        e = self.env
+        ops.copy_multi([(self.hist[slot, 0], e.h), (self.hist[slot, 1], e.v), (self.hist[slot, 2], e.u)])
+
+    def reset(self):
+        """Every replica to the state the one-replica path gives its seed."""
+        env = self.env
+        if self.atsc:
+            for e, s in enumerate(self.seeds):
+                env.reset_replica(e, s)
+            self.recorder.begin()
+        else:
+            u0 = cacc_eval_u0(self.seeds, env.config.getint('seed'))
+            env.reset(u0=torch.from_numpy(u0.astype(np.float32)).to(env.device))
+            self._phys(0)
+        self.steps.prepare()
+
+    def _after_step(self, t):
+        if self.recorder is not None:
+            self.recorder.step(t)
+        else:
+            self._phys(t + 1)
+
+    def _episode(self):
+        self.steps.run(uniforms=self.uniforms, after_step=self._after_step)
+
+    def run(self):
+        """-> the per-seed mean global reward; writes the CSVs."""
+        self.reset()
+        return self.run_episode()
+
+    def run_episode(self):
+        """The episode from the state `reset` left, the read-back, the tables."""
+        env = self.env
+        if not self.use_graph:
+            self._episode()
+        else:
+            if self.graph is None:
+                snap = [t.clone() for t in env.state_tensors()]
+                rec = None if self.recorder is None else [t.clone() for t in (self.recorder.stand, self.recorder.prev_total, self.recorder.cum)]
+                calls = 0 if self.recorder is None else self.recorder.n_calls
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self._episode()                   # warm-up (allocator, library handles)
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._episode()
+                for t, v in zip(env.state_tensors(), snap):
+                    t.copy_(v)
+                if rec is not None:
+                    for t, v in zip((self.recorder.stand, self.recorder.prev_total, self.recorder.cum), rec):
+                        t.copy_(v)
+                    self.recorder.n_calls = calls
+                self.steps.prepare()
+            self.graph.replay()
+            if self.recorder is not None:
+                self.recorder.n_calls += env.T         # (a replay runs no Python: the host's call count follows by hand)
+        # ---- the only read-back: every buffer once
+        acts, G, D = self.steps.acts.cpu().numpy(), self.steps.G.cpu().numpy(), self.steps.D.cpu().numpy()
+        rows, finished = eval_row_counts(D)
+        self.control_data = eval_control_rows(acts, G, rows, self.atsc, self.dt)
+        means = [float(np.mean([float(g) for g in G[:int(n), e]])) for e, n in enumerate(rows)]
+        stem = self.output_path + '%s_%s_' % (env.name, env.agent)
+        pd.DataFrame(self.control_data).to_csv(stem + 'control.csv')
+        if self.atsc:
+            self.traffic_data, self.trip_data = eval_atsc_tables(self.recorder.rows(), self.recorder.trip(), rows)
+            pd.DataFrame(self.traffic_data).to_csv(stem + 'traffic.csv')
+            pd.DataFrame(self.trip_data).to_csv(stem + 'trip.csv')
+        else:
+            self.traffic_data = eval_cacc_traffic(self.hist.cpu().numpy().transpose(0, 2, 1, 3), G, rows, finished, self.dt)
+            # (every replica reaches a done by step T, so the list is never empty today; an empty one writes an empty table)
+            (pd.concat(self.traffic_data) if self.traffic_data else pd.DataFrame()).to_csv(stem + 'traffic.csv')
+        for k, m in enumerate(means):
+            logging.info('test %i, avg reward %.2f' % (k, m))
+        return means

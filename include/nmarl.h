@@ -315,6 +315,26 @@ int nmarl_atsc_traffic_step(int64_t E, int32_t N, int32_t S, const int32_t* mult
                             float* rec_row, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* The rule-based `greedy` agent of the ATSC scenarios for E replicas         */
+/* (envs/large_grid_env.py:30-45, envs/real_net_env.py:112-145 of the         */
+/* reference); kernel and mapping in csrc/greedy.hip, rule in DESIGN 6         */
+/* ------------------------------------------------------------------------- */
+/* Node i of replica e reads its OWN wave vector at obs + (e * N + i) * obs_row floats (obs 16-byte aligned, obs_row % 4 == 0: the
+ * compact grid observation [E,N,12] and the grid slab [E,N,60] lead with it; the network's rows of 22 (1 + m_max) floats are no
+ * multiple of 4, so its own vectors are handed over staged in rows of 24).  Static
+ * tables (device): n_a [N] i32 = phases of node i, 1..A_max (the caller's contract: a value outside is clamped, not reported);
+ * mask [N][8] u32, bit k of mask[i][a] set = feature k counts for phase a of node i (features 0..23; a bit at or above
+ * min(24, obs_row) counts nothing).  Rule, for every (e, i):
+ *     score_a     = sum of (double) obs_k over the set bits k of mask[i][a], k ascending from 0,   a < n_a[i]
+ *     action[e,i] = the smallest a with the largest score_a                                        -> action [E,N] u8
+ * i.e. LargeGridController.greedy / RealNetController.greedy in float64 on the float32 observation (ascending sums, np.argmax's
+ * first maximum).  One launch for any E, no host synchronisation, independent of E and of the launch grid.
+ * NMARL_EINVAL without a launch: E < 1, N outside 1..32, A_max outside 1..8, a NULL array, obs_row not a positive multiple of 4,
+ * obs not 16-byte aligned. */
+int nmarl_atsc_greedy(int64_t E, int32_t N, int32_t A_max, const int32_t* n_a, const uint32_t* mask, const float* obs,
+                      int64_t obs_row, uint8_t* action, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Neighbourhood aggregation over the fixed adjacency (agent-major [N,E,F])   */
 /* ------------------------------------------------------------------------- */
 /*
