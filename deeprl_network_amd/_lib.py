@@ -123,6 +123,13 @@ class BatchEpilogue(C.Structure):
                                            'fp_uniform', 'x_T', 'fp_0', 'x_0', 'done_pre', 'scratch', 'skip_if')])
 
 
+class TrainRecord(C.Structure):
+    """nmarl_train_record_t (include/nmarl.h)."""
+    _fields_ = ([('rows', C.c_int64)] + [(k, C.c_int32) for k in ('N', 'A', 'G', 'K')] + [('lr', C.c_float), ('e_coef', C.c_float)] +
+                [(k, C.c_void_p) for k in ('n_a', 'terms', 'grad_norm', 'lr_dev', 'R', 'Adv', 'action', 'ring', 'count', 'skip_if',
+                                           'ws')])
+
+
 class BpttCoupled(C.Structure):
     """nmarl_bptt_coupled_t (include/nmarl.h): arguments of nmarl_lstm_bptt_coupled."""
     _fields_ = ([(k, C.c_int32) for k in ('kind', 'N', 'T', 'H', 'm_max', 'r_max', 'r_row', 'symmetric', 'mode', 'ring_slots')] +
@@ -262,6 +269,8 @@ SIGNATURES = {
     'nmarl_handoff_capacity': [_i32, _i32],
     'nmarl_test_handoff_fault': [_i32],
     'nmarl_batch_epilogue': [C.POINTER(BatchEpilogue), _p],
+    'nmarl_train_record_ws_bytes': [_i32, _i64],
+    'nmarl_train_record': [C.POINTER(TrainRecord), _p],
     'nmarl_timestamp': [_p, _p],
     'nmarl_timestamp_rate_khz': [],
     'nmarl_copy_multi': [_i32, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), _p, _p],

@@ -24,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, train_record
 from .policies import (ConsensusPolicy, DIALMultiAgentPolicy, FPPolicy, IC3MultiAgentPolicy, LstmPolicy,
                        NCMultiAgentPolicy)
 from .utils import Scheduler
@@ -183,6 +183,7 @@ class IA2C:
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
         self.last_loss = None
+        self._terms = None                # [N,3] terms tensor of the last update where a native loss produced one
         # steps whose pre-step done flag may be non-zero (None = any, the reference API); the batched trainer
         # sets (0,) because episodes start only at batch boundaries (quirk Q4)
         self.masked_steps = None
@@ -465,7 +466,7 @@ class IA2C:
         as_dy = self.save_acts and p.bptt_takes_head_dy and os.environ.get('NMARL_BPTT_HEAD_DY', '1') != '0'
         r = ops.heads_loss(Hs.detach(), prm['pi_w'], prm['pi_b'], prm['v_w'], prm['v_b'], action, p.nbr_idx, self.n_a,
                            self.Adv.view(N, T * E), self.R.view(N, T * E), self.v_coef, self.e_coef, want_dh=not as_dy)
-        terms = r['terms']
+        terms = self._terms = r['terms']
         self.last_loss = (terms[:, 0], terms[:, 1], terms[:, 2], terms.sum(dim=1))
         for k in ('pi_w', 'pi_b', 'v_w', 'v_b'):
             prm[k].grad = r[k].reshape(prm[k].shape)
@@ -490,6 +491,7 @@ class IA2C:
             adv = adv.sum(dim=0, keepdim=True).expand(N, T * E).contiguous()
         if ops.a2c_loss_supported(self.n_a):
             per_agent, terms = ops.a2c_loss(logits, v, action, adv, R, self.v_coef, self.e_coef)
+            self._terms = terms
             self.last_loss = (terms[:, 0], terms[:, 1], terms[:, 2], per_agent.detach())
             return per_agent.sum()
         pi = torch.softmax(logits, dim=-1)
@@ -501,8 +503,17 @@ class IA2C:
         value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
         entropy_loss = -entropy.mean(-1) * self.e_coef
         per_agent = policy_loss + value_loss + entropy_loss
+        self._terms = None
         self.last_loss = (policy_loss.detach(), value_loss.detach(), entropy_loss.detach(), per_agent.detach())
         return per_agent.sum()
+
+    def loss_terms(self):
+        """[N,3] contiguous (policy, value, entropy) loss terms of the last update: the `terms` tensor of ops.heads_loss /
+        ops.a2c_loss itself on the two native paths (inside a captured update its address is the graph's), a stack on the
+        torch path."""
+        if self._terms is not None:
+            return self._terms
+        return torch.stack(self.last_loss[:3], dim=1).contiguous()
 
     def update(self, R_end, rotate=True):
         """model.backward (models.py:34-42 / 211-215) for all replicas: R_end [N,E].  rotate=False: the caller hands the
@@ -696,6 +707,11 @@ class IA2C:
             # the reference API has no trainer that re-runs a batch: a timed-out in-launch hand-off (whose optimiser step the
             # device refused) is an error here, not a silent no-op (this path synchronises every lock-step anyway)
             ops.check_coupled_status(self.device)
+        if summary_writer is not None:
+            # the reference's six scalars of this update (policies.py:40-48, 116-117 / 212-213, 265-273) at global_step: plain
+            # host reads, this path synchronises every lock-step anyway (the batched engine: train_record.TrainRecorder)
+            train_record.write_scalars(summary_writer, self.policy.summary_name, self.per_agent_optimizer,
+                                       [global_step], [train_record.host_row(self)], extras=False)
 
     def reset(self):
         self.reset_states()

@@ -225,6 +225,7 @@ class BatchedPolicy:
     """Common part: heads, rollout step (Q1 double step handled by the caller), unroll."""
 
     name = 'policy'
+    summary_name = 'policy'       # the reference policy's scope name (policies.py:7-11): the <name> of its TensorBoard tags
     fused_coupled = True          # coupled policies: use agents/sequence.py in the update
 
     def __init__(self, n_feat, n_a, neighbor_mask, n_fc=64, n_h=64, device='cuda', n_feat_ls=None, n_a_ls=None, obs_order=None,
@@ -731,6 +732,7 @@ class BatchedPolicy:
 class LstmPolicy(BatchedPolicy):
     """IA2C: fc(n_s -> n_fc, relu) -> LSTM -> heads (policies.py:136-149)."""
     name = 'lstm'
+    summary_name = 'lstm_0'      # IA2C hands the writer to policy 0 alone (models.py:38-42)
     k_wh, k_b, k_wx = 'lstm_wh', 'lstm_b', 'lstm_wx'
     k_ob = 'fc_w'                 # the observation encoder's weight
     coupled = False               # the recurrence has no cross-agent term -> fused sequence op
@@ -831,6 +833,7 @@ class NCMultiAgentPolicy(BatchedPolicy):
     """NeurComm: s = [relu(x~ W_ob), relu(p~ W_fp), relu(m~ W_msg)] -> LSTM(3H) (agents/utils.py:182-208).
     m~ = neighbours' previous h, NOT done-masked (Q3: agents/utils.py:182-183)."""
     name = 'nc'
+    summary_name = 'nc'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
     k_ob = 'w_ob'
     scope = 'nc/lstm_comm_%d'
@@ -943,6 +946,7 @@ class IC3MultiAgentPolicy(BatchedPolicy):
     """CommNet ("IC3"): s = tanh(x~ W_ob + b) + mean_nbr(h_prev) W_msg + b_msg -> LSTM(H)
     (agents/utils.py:385-408)."""
     name = 'ic3'
+    summary_name = 'ic3'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
     k_ob = 'w_ob'
     scope = 'ic3/lstm_ic3_%d'
@@ -1045,6 +1049,7 @@ class ConsensusPolicy(LstmPolicy):
     optimiser; after every update each agent's LSTM weights are replaced by the mean over itself and its
     neighbours (`_get_critic_wts` averages only the `lstm_%da` scope)."""
     name = 'cu'
+    summary_name = 'cu'
     k_ob = 'fc_w'
 
     def _phases(self):
@@ -1098,6 +1103,7 @@ class DIALMultiAgentPolicy(BatchedPolicy):
         return BatchedPolicy.bptt_takes_head_dy.fget(self) and ops.dial_bptt_table(self.nbr_idx, self.n_h) is not None
 
     name = 'dial'
+    summary_name = 'dial'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
     k_ob = 'w_ob'
     coupled = True

@@ -28,6 +28,8 @@ def parse_args(argv=None):
                     help='experiment config path')
     sp.add_argument('--num-envs', type=int, default=None, help='replicas per GPU (overrides ENV_CONFIG num_envs)')
     sp.add_argument('--no-graph', action='store_true', help='do not capture the rollout in a hipGraph')
+    sp.add_argument('--no-train-record', action='store_true',
+                    help='batched training: no per-update loss / lr / gradnorm scalars and no train_summary.csv')
     sp.add_argument('--lstm-precision', choices=('fp32', 'bf16x3'), default=None,
                     help='arithmetic of the rollout\'s LSTM products (overrides MODEL_CONFIG lstm_precision; default fp32). '
                          'bf16x3: opt-in split-bf16 form, IA2C / IA2C-FP / ConseNet only; the update stays fp32')
@@ -111,7 +113,8 @@ def train(args):
         model = init_agent(env, config['MODEL_CONFIG'], total_step, seed, num_envs=num_envs, device=device,
                            dist_group=group)
         trainer = BatchedTrainer(env, model, counter, writer, output_path=dirs['data'],
-                                 use_graph=not args.no_graph, rank=rank, world_size=world)
+                                 use_graph=not args.no_graph, rank=rank, world_size=world,
+                                 record=False if args.no_train_record else None)
         trainer.run()
     if rank == 0:
         final_step = counter.cur_step

@@ -1846,6 +1846,41 @@ def batch_epilogue(g, done, ep_sum, ep_sq, ep_len, fin, T_env, h_fw, c_fw, h_bw,
     check(lib.nmarl_batch_epilogue(C.byref(a), stream()), 'nmarl_batch_epilogue')
 
 
+TRAIN_RECORD_COLS = 24      # NMARL_TRAIN_RECORD_COLS
+TRAIN_RECORD_MAX_N, TRAIN_RECORD_MAX_A = 32, 8
+
+
+def train_record_ws(N, rows, device):
+    """The scratch of `train_record` for N agents x rows entries (nmarl_train_record_ws_bytes), as float64 words."""
+    nbytes = lib.nmarl_train_record_ws_bytes(int(N), int(rows))
+    if nbytes <= 0:
+        raise _lib.NmarlError('train_record: no workspace for N = %d, rows = %d (N <= %d)' % (N, rows, TRAIN_RECORD_MAX_N))
+    return torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def train_record(terms, grad_norm, lr, e_coef, R, Adv, action, ring, count, ws, n_a=None, lr_dev=None, skip_if=None, A=None):
+    """nmarl_train_record (include/nmarl.h; columns: csrc/train_record.hip): appends one row per agent to ring [K,N,24] f32 at slot
+    count % K and advances count (one int64 on the device) -- two kernel launches on the current stream, nothing synchronised.
+    terms [N,3], grad_norm [G] (G = N or 1), R / Adv [N,rows] f32, action [rows,N] u8, n_a [N] i32 or None (every agent has A
+    actions; A defaults to the width the caller's heads are padded to and must be given when n_a is None), lr_dev: device
+    scalar that overrides lr, skip_if: int32 device word -- while != 0 the call changes nothing."""
+    N, rows = R.shape
+    K = ring.shape[0]
+    if tuple(terms.shape) != (N, 3) or tuple(Adv.shape) != (N, rows) or tuple(action.shape) != (rows, N) or \
+            tuple(ring.shape) != (K, N, TRAIN_RECORD_COLS) or count.numel() != 1 or grad_norm.dim() != 1 or A is None:
+        raise _lib.NmarlError('train_record: terms [N,3], grad_norm [G], R / Adv [N,rows], action [rows,N], ring [K,N,24], one count, A')
+    a = _lib.TrainRecord()
+    a.rows, a.N, a.A, a.G, a.K = rows, N, int(A), grad_norm.shape[0], K
+    a.lr, a.e_coef = float(lr), float(e_coef)
+    a.n_a, a.terms, a.grad_norm, a.lr_dev = ptr(n_a, torch.int32), ptr(terms, F32), ptr(grad_norm, F32), ptr(lr_dev, F32, strided=True)
+    a.R, a.Adv, a.action = ptr(R, F32), ptr(Adv, F32), ptr(action, torch.uint8)
+    a.ring, a.count, a.ws = ptr(ring, F32), ptr(count, torch.int64, strided=True), ptr(ws, torch.float64)
+    a.skip_if = ptr(skip_if, torch.int32, strided=True)
+    if ws.numel() * 8 < lib.nmarl_train_record_ws_bytes(N, rows):
+        raise _lib.NmarlError('train_record: workspace too small for N = %d, rows = %d' % (N, rows))
+    check(lib.nmarl_train_record(C.byref(a), stream()), 'nmarl_train_record')
+
+
 COPY_MAX = 16      # NMARL_COPY_MAX
 
 

@@ -21,7 +21,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from . import ops
+from . import ops, train_record
 
 
 # ------------------------------------------------------------------ small helpers (the names main.py imports, utils.py:11-60)
@@ -289,7 +289,12 @@ class BatchedTrainer:
 
     def __init__(self, env, model, global_counter=None, summary_writer=None, output_path=None,
                  use_graph=True, rank=0, world_size=1, save_activations=True, compact_obs=True, fused_encode=True,
-                 capture_update=True, rearm_after=200, keep_graphs=False):
+                 capture_update=True, rearm_after=200, keep_graphs=False, record=None, record_slots=64):
+        """record: the training record (train_record.TrainRecorder: per update and agent the reference's loss / lr / gradnorm
+        scalars and critic diagnostics, two kernel launches behind the optimiser step, drained where a row is logged).  None:
+        on iff a summary_writer is given; False: nothing is allocated or launched; record_slots: updates the ring holds
+        between two logged rows.  Under data parallelism every rank records its own replicas' loss terms and statistics
+        (gradnorm is that of the reduced gradient); rank 0 writes its own rows -- there is no collective for the record."""
         self.env, self.model = env, model
         if rank == 0:
             prec = getattr(getattr(model, 'policy', None), 'precision', 'fp32')
@@ -359,6 +364,10 @@ class BatchedTrainer:
         self._pending = None                  # (pinned copy of the status words, event) of the batch launched last
         self.data = []
         self.n_batches = 0
+        if record is None:
+            record = summary_writer is not None
+        self.recorder = train_record.TrainRecorder(model, K=record_slots) if record else None
+        self.train_summary = []               # rows of train_summary.csv (rank 0)
         env.train_mode = True
         model.reset_states()
         model.masked_steps = (0,)             # only the first lock-step of a batch can start an episode (Q4)
@@ -477,6 +486,12 @@ class BatchedTrainer:
                            m.h_fw, m.c_fw, m.h_bw, m.c_bw, m.buf_fp[T], m.buf_fp[0], m.fp_uniform, m.buf_x[T], m.buf_x[0],
                            self.done_pre, skip_if=self._status[:1] if self.handoff_guard else None)
 
+    def _record(self, lr, lr_dev=None):
+        """The training record's launches: directly behind `update_apply` (grad_norm is final), in front of `_epilogue`, refused
+        with it (the same skip_if) -- a batch the device refuses leaves no row."""
+        if self.recorder is not None:
+            self.recorder.record(lr, lr_dev=lr_dev, skip_if=self._status[:1] if self.handoff_guard else None)
+
     def _capture_update(self):
         """Capture the update of a batch as hipGraphs (after at least one eager batch: the library GEMMs are tuned, every
         lazily built table and workspace exists).  One graph [rewards, returns, loss, backward, clip + RMSProp, epilogue];
@@ -503,12 +518,14 @@ class BatchedTrainer:
                 m.update_grads(self.R_end)
                 if not split:
                     m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
+                    self._record(0.0, lr_dev=self.lr_dev)
                     if inside:
                         self._epilogue()
             if split:
                 g2 = self._new_graph()
                 with torch.cuda.graph(g2):
                     m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
+                    self._record(0.0, lr_dev=self.lr_dev)
                     if inside:
                         self._epilogue()
             self._upd = dict(grads=g1, apply=g2, epilogue_inside=inside)
@@ -531,7 +548,8 @@ class BatchedTrainer:
                 torch.cuda.synchronize()
         if self._upd is None:
             m.load_rewards(self.buf_rraw)
-            m.update(self.R_end, rotate=False)
+            m.update(self.R_end, rotate=False)         # (ends with update_apply; update_end launches nothing)
+            self._record(m.cur_lr)
             return False
         lr = m.update_begin()
         if lr != self._lr_dev_host:            # the schedule moved (never for lr_decay = constant): one tiny launch
@@ -555,6 +573,8 @@ class BatchedTrainer:
             # the counter (like the reference's global step and the lr schedule) counts LOCK-steps, i.e. environment
             # steps per replica: `total_step` of the ini keeps its meaning (1e6 -> 16 667 updates at n_step 60)
             self.global_counter.advance(self.n_step)
+        if self.recorder is not None:         # the global step this update's row is logged at (the reference's: after the batch's steps)
+            self.recorder.note(self.global_counter.cur_step if self.global_counter is not None else self.n_batches * self.n_step)
         if self.handoff_guard:
             self._probe_handoff_status()
         elif self.handoff_fallbacks and self._wants_guard:
@@ -622,6 +642,8 @@ class BatchedTrainer:
         m.policy.invalidate_cached_msg()
         m.lr_scheduler.rewind(self.n_step * batches)       # the refused updates advanced the schedule
         self.n_batches -= batches
+        if self.recorder is not None:
+            self.recorder.drop(batches)        # (the refused batches left no row on the device either)
         if self.global_counter is not None:
             self.global_counter.advance(-self.n_step * batches)
         self.handoff_guard, self._pending = False, None
@@ -738,9 +760,18 @@ class BatchedTrainer:
                             % (total, log_every * self.n_step))
         rows_done = 0
         last_eval = [float('nan'), float('nan'), 0]
+        rec = self.recorder
+        assert rec is None or log_every <= rec.K, 'log_every %d > the %d updates the training record holds' % (log_every, rec.K)
 
         def log_row(final=False):
             st = self.stats()
+            if rec is not None:               # (stats() synchronised and resolved every pending hand-off check) one copy
+                upd_steps, upd_rows = rec.rows()
+                if self.rank == 0:
+                    self.train_summary.extend(train_record.csv_rows(upd_steps, upd_rows, rec.A))
+                    if self.summary_writer is not None:
+                        train_record.write_scalars(self.summary_writer, self.model.policy.summary_name,
+                                                   self.model.per_agent_optimizer, upd_steps, upd_rows)
             step = self.global_counter.cur_step
             row = {'agent': self.env.agent, 'step': step, 'test_id': -1, 'avg_reward': st['avg_reward'],
                    'std_reward': st['std_reward'], 'train_avg_reward': st['avg_reward'],
@@ -770,6 +801,8 @@ class BatchedTrainer:
             log_row(final=True)                           # final row: never leave train_reward.csv empty / without a test
         if self.output_path is not None and self.rank == 0:
             pd.DataFrame(self.data).to_csv(self.output_path + 'train_reward.csv')
+            if rec is not None:
+                train_record.write_csv(self.output_path + 'train_summary.csv', self.train_summary, rec.A)
 
 
 # ------------------------------------------------------------------ test episodes of E replicas without host synchronisation

@@ -1009,6 +1009,36 @@ int nmarl_copy_multi(int32_t n, void* const* dst, const void* const* src, const 
                      void* stream);
 
 /*
+ * Training record (csrc/train_record.hip; specification: its header and DESIGN.md 6): behind the optimiser step of an update,
+ * one row of 24 floats per agent -- the reference's per-update TensorBoard scalars (agents/policies.py:40-48, 265-273: policy /
+ * value / entropy / total loss, lr, gradnorm) and critic diagnostics of the batch (return and advantage moments, mean value,
+ * explained variance, mean entropy, action shares) -- appended to ring[count % K] of a device-resident ring; then count += 1
+ * (the call's last store).  Two kernel launches, no host synchronisation, no memcpy / memset; only terms, grad_norm, lr_dev, R,
+ * Adv and action are read.  Sums are float64 in a fixed order: the same (N, rows, A) gives the same bits on every run.
+ * NMARL_EINVAL without a launch: N outside 1..32, rows outside 1..2^31, A outside 1..8, G outside 1..N, K < 1, a NULL pointer
+ * (n_a, lr_dev, skip_if excepted), action not 4-byte or ws / count not 8-byte aligned.
+ */
+typedef struct nmarl_train_record {
+    int64_t rows;             /* T * E entries per agent */
+    int32_t N, A, G, K;       /* agents; padded action count; entries of grad_norm (N: per-agent optimiser, else 1); ring slots */
+    float lr, e_coef;
+    const int32_t* n_a;       /* [N] own action counts, or NULL: A for every agent */
+    const float* terms;       /* [N,3] policy, value, entropy loss (nmarl_heads_loss / nmarl_a2c_loss_fwd) */
+    const float* grad_norm;   /* [G]; agent i reads entry min(i, G - 1) */
+    const float* lr_dev;      /* NULL, or a device scalar that overrides lr (as in nmarl_rmsprop_tf_clip_guarded) */
+    const float *R, *Adv;     /* [N,rows] */
+    const uint8_t* action;    /* [rows,N] env-major */
+    float* ring;              /* [K,N,24] */
+    int64_t* count;           /* rows committed so far */
+    const int32_t* skip_if;   /* NULL, or a device word: while it is != 0 the call writes NOTHING and count stays (the contract of
+                               * nmarl_batch_epilogue / nmarl_copy_multi: a refused batch leaves no row) */
+    void* ws;                 /* nmarl_train_record_ws_bytes(N, rows) bytes of scratch, 8-byte aligned */
+} nmarl_train_record_t;
+#define NMARL_TRAIN_RECORD_COLS 24
+int nmarl_train_record_ws_bytes(int32_t N, int64_t rows);
+int nmarl_train_record(const nmarl_train_record_t* p, void* stream);
+
+/*
  * Measurement (kernel durations against the roofline; the reference has no counterpart): nmarl_timestamp stores the
  * device's constant-rate wall clock into *out (device pointer) from a one-thread kernel on `stream`; nmarl_timestamp_rate_khz
  * returns the clock's rate in kHz (hipDeviceAttributeWallClockRate of the current device; < 0: error).  Two stamps around a
