@@ -327,7 +327,7 @@ def run_scripted(name, agent, topo, seed, n_step, n_batch=3, coop_gamma=-1):
                                                  np.round(LOSS[0][:, 1], 4)[:3]))
 
 
-def run_batched(name, agent, topo, seed, n_step, K=4):
+def run_batched(name, agent, topo, seed, n_step, K=4, coop_gamma=-1):
     """The E > 1 update contract: K independent replicas of the reference model with IDENTICAL
     weights each roll out one n_step batch (models.py:26-51 / 198-227, Trainer.explore order) and run `backward`
     (models.py:34-42, 211-215) -- with the optimiser step intercepted, so the weights stay put and the raw gradient
@@ -339,20 +339,34 @@ def run_batched(name, agent, topo, seed, n_step, K=4):
     (no update); replicas 0, 1 end their episode there and start the main batch fresh (done = True, zero state,
     uniform fingerprints -- the reference's env.reset(); model.reset()), replicas 2.. continue (done = False, states
     and fingerprints carried over, states_bw <- states_fw as in policies.py:115, 211).  Replica 1's episode ends with
-    the last step of the main batch (R = 0, utils.py:189-190), the others bootstrap (utils.py:192-196)."""
-    cp = cacc_config(agent=agent, n_step=n_step, reward_norm=50.0, coop_gamma=-1)
+    the last step of the main batch (R = 0, utils.py:189-190), the others bootstrap (utils.py:192-196).
+
+    topo 'ragged': the reference's heterogeneous nets (identical=False) on ragged_graph(), with run_ragged's conventions
+    (n_s_ls of the IA2C family, X zero past each agent's own width, ACT[..., i] < n_a_ls[i], uniform fingerprints
+    1 / n_a_i, PI zero padded to the widest action set).  coop_gamma >= 0: spatial returns from per-agent rewards
+    REW [K,2,T,N], handed to add_transition as run_scripted does."""
+    cp = cacc_config(agent=agent, n_step=n_step, reward_norm=50.0, coop_gamma=coop_gamma)
     mc = cp['MODEL_CONFIG']
-    if topo == 'line':
+    ragged = topo == 'ragged'
+    if ragged:
+        nb, dist, n_own, n_a_ls = ragged_graph()
+        N, n_feat, A = len(n_own), max(n_own), max(n_a_ls)
+    elif topo == 'line':
         N, n_feat, A = 8, 5, 4
         nb, dist = line_masks(N)
     else:
         N, n_feat, A = 25, 12, 5
         nb, dist = grid_masks(5)
+    if not ragged:
+        n_own, n_a_ls = [n_feat] * N, [A] * N
+    spatial = coop_gamma >= 0
     is_ma = agent.startswith('ma2c')
     nbr = [np.where(nb[i] == 1)[0] for i in range(N)]
-    n_s_ls = [n_feat if is_ma else n_feat * (1 + len(nbr[i])) for i in range(N)]
+    # IA2C_FP adds the neighbours' fingerprint widths itself (models.py:176-187)
+    n_s_ls = list(n_own) if is_ma else [n_own[i] + sum(n_own[j] for j in nbr[i]) for i in range(N)]
     np.random.seed(seed)
-    model = CLS[agent](n_s_ls, [A] * N, nb, dist, -1, 10 ** 9, mc, seed=seed)
+    model = CLS[agent](n_s_ls, list(n_a_ls), nb, dist, coop_gamma, 10 ** 9, mc, seed=seed)
+    assert model.identical_agent == (not ragged)
     variables = tf.global_variables()
     by_name = {v.full_name: v for v in variables}
     policies = model.policy if isinstance(model.policy, list) else [model.policy]
@@ -378,38 +392,64 @@ def run_batched(name, agent, topo, seed, n_step, K=4):
     T = n_step
     rng = np.random.RandomState(seed + 2000)
     X = rng.normal(0, 0.7, size=(K, 2, T + 1, N, n_feat))
-    ACT = rng.randint(0, A, size=(K, 2, T + 1, N))
-    REW = rng.normal(-30, 20, size=(K, 2, T))
+    if ragged:
+        for i in range(N):
+            X[..., i, n_own[i]:] = 0.0
+        ACT = np.stack([rng.randint(0, n_a_ls[i], size=(K, 2, T + 1)) for i in range(N)], axis=-1)
+    else:
+        ACT = rng.randint(0, A, size=(K, 2, T + 1, N))
+    REW = rng.normal(-30, 20, size=(K, 2, T, N) if spatial else (K, 2, T))
     PI = np.zeros((K, 2, T + 1, N, A))
     V = np.zeros((K, 2, T + 1, N))
     RB = np.zeros((K, N))
     STATES = np.zeros((K, N, 2 * int(mc['num_lstm'])))
     state = {'fp': None}
 
+    def uniform():                                            # a fresh episode's fingerprints: uniform over the agent's OWN actions
+        return [np.ones(n_a_ls[i]) / n_a_ls[i] for i in range(N)] if ragged else np.ones((N, A)) / A
+
+    def copy_fp(fp):
+        return [np.asarray(p, dtype=np.float64).reshape(-1).copy() for p in fp] if ragged else fp.copy()
+
+    def pad(pi):
+        if not ragged:
+            return pi
+        o = np.zeros((N, A))
+        for i in range(N):
+            o[i, :n_a_ls[i]] = pi[i]
+        return o
+
     def make_ob(x):
         ob = []
         for i in range(N):
-            cur = [x[i]]
+            cur = [x[i, :n_own[i]]]
             if not is_ma:
-                cur += [x[j] for j in nbr[i]]
+                cur += [x[j, :n_own[j]] for j in nbr[i]]
             if agent == 'ia2c_fp':
                 cur += [state['fp'][j] for j in nbr[i]]
             ob.append(np.concatenate(cur))
         return ob
 
+    def outputs(res, vector):                                 # identical nets: one array; heterogeneous: ragged lists (policies.py:301, 387)
+        if not ragged:
+            return np.array(res)
+        if vector:
+            return [np.asarray(p, dtype=np.float64).reshape(-1) for p in res]
+        return np.array(res, dtype=np.float64).reshape(N)
+
     def decide(x, done, a, update_fp=True):
         ob = make_ob(x)
-        ps = state['fp'].copy()
+        ps = copy_fp(state['fp'])
         if is_ma:
-            pi = np.array(model.forward(ob, done, ps))
-            v = np.array(model.forward(ob, done, ps, np.array(a), 'v'))
+            pi = outputs(model.forward(ob, done, ps), True)
+            v = outputs(model.forward(ob, done, ps, np.array(a), 'v'), False)
             extra = ps
         else:
-            pi = np.array(model.forward(ob, done))
+            pi = outputs(model.forward(ob, done), True)
             extra = [a[nb[i] == 1] for i in range(N)]
-            v = np.array(model.forward(ob, done, extra, 'v'))
+            v = outputs(model.forward(ob, done, extra, 'v'), False)
         if update_fp:
-            state['fp'] = pi.copy()                           # env.update_fingerprint (utils.py:173), not at the bootstrap
+            state['fp'] = copy_fp(pi)                         # env.update_fingerprint (utils.py:173), not at the bootstrap
         return ob, extra, pi, v
 
     def batch(k, ph, done, last_done):
@@ -417,20 +457,20 @@ def run_batched(name, agent, topo, seed, n_step, K=4):
             a = ACT[k, ph, t]
             ob, extra, pi, v = decide(X[k, ph, t], done, a)
             done = bool(last_done and t == T - 1)
-            model.add_transition(ob, extra, a, float(REW[k, ph, t]), v, done)
-            PI[k, ph, t], V[k, ph, t] = pi, v
+            model.add_transition(ob, extra, a, REW[k, ph, t] if spatial else float(REW[k, ph, t]), v, done)
+            PI[k, ph, t], V[k, ph, t] = pad(pi), v
         if done:
             R = np.zeros(N)
         else:
             _, _, pi, R = decide(X[k, ph, T], done, ACT[k, ph, T], update_fp=False)
-            PI[k, ph, T], V[k, ph, T] = pi, R
+            PI[k, ph, T], V[k, ph, T] = pad(pi), R
         model.backward(R, 0)                                  # intercepted: gradients recorded, states_bw <- states_fw
         return R
 
     per_replica = []
     for k in range(K):
         model.reset()
-        state['fp'] = np.ones((N, A)) / A
+        state['fp'] = uniform()
         if k >= 2:                                            # continuing replicas: a prefix batch, discarded
             batch(k, 0, True, False)
             grad_log.clear()
@@ -461,7 +501,8 @@ def run_batched(name, agent, topo, seed, n_step, K=4):
             mean_g[nm] = g / scale
     if agent == 'ma2c_cu':
         # the consensus update that follows the optimiser step (policies.py:351-364, 403-426): every agent's LSTM variables
-        # <- mean over itself and its neighbours, all sources read before any target is written (the shim's tf.group)
+        # <- mean over itself and its neighbours, all sources read before any target is written (the shim's tf.group).  Both
+        # branches of ConsensusPolicy._build_net name these scopes lstm_<i>a (policies.py:380, 409); only the heads differ
         stepped = dict(new_w)
         for i in range(N):
             for var in ('wx', 'wh', 'b'):
@@ -471,7 +512,9 @@ def run_batched(name, agent, topo, seed, n_step, K=4):
                X=X, ACT=ACT, REW=REW, PI=PI, V=V, RB=RB, STATES=STATES, LOSSK=LOSSK, LOSS=LOSSK.mean(0), GN=GN,
                STATS=var_stats([new_w[v.full_name] for v in variables]),
                GSTATS=var_stats([mean_g.get(v.full_name, np.zeros(tuple(v.value.shape))) for v in variables]),
-               nb=nb, dist=dist, agent=agent, topo=topo, seed=seed, n_step=n_step, K=K, coop_gamma=-1, reward_norm=50.0)
+               nb=nb, dist=dist, agent=agent, topo=topo, seed=seed, n_step=n_step, K=K, coop_gamma=coop_gamma, reward_norm=50.0)
+    if ragged:
+        out.update(n_own=np.array(n_own), n_a_ls=np.array(n_a_ls), n_s_ls=np.array(n_s_ls))
     np.savez_compressed(os.path.join(OUT, 'nnb_%s.npz' % name), **out)
     print('%-22s K=%d T=%d loss=%s gnorm=%s' % ('nnb_' + name, K, T, np.round(out['LOSS'], 5)[:3], np.round(GN, 4)[:3]))
 
@@ -482,6 +525,12 @@ BATCHED = [('ia2c_fp_line', 'ia2c_fp', 'line', 40, 60), ('ma2c_nc_line', 'ma2c_n
            # 64 x 4 = 256 wide: the product's separate-launch message path, not the step kernel's pre-phase)
            ('ia2c_line', 'ia2c', 'line', 43, 60), ('ma2c_cu_line', 'ma2c_cu', 'line', 44, 60),
            ('ma2c_dial_line', 'ma2c_dial', 'line', 45, 60), ('ma2c_nc_grid', 'ma2c_nc', 'grid', 46, 30)]
+# heterogeneous agents on ragged_graph() through the batched engine (n_step 12: not a multiple of the n-step return kernel's
+# 10-step chunk, short enough for the float64 shim), and NeurComm with spatial returns from per-agent rewards (coop_gamma 0.9,
+# what the Monaco configuration runs)
+BATCHED_RAGGED = [('ia2c_ragged', 'ia2c', 50, -1), ('ia2c_fp_ragged', 'ia2c_fp', 51, -1), ('ma2c_nc_ragged', 'ma2c_nc', 52, -1),
+                  ('ma2c_ic3_ragged', 'ma2c_ic3', 53, -1), ('ma2c_cu_ragged', 'ma2c_cu', 54, -1),
+                  ('ma2c_dial_ragged', 'ma2c_dial', 55, -1), ('ma2c_nc_ragged_spatial', 'ma2c_nc', 56, 0.9)]
 
 
 def run_ortho():
@@ -519,6 +568,10 @@ def main(argv):
         if want('nnb_' + nm):
             tf.reset_default_graph()
             run_batched(nm, ag, topo, sd, ns)
+    for nm, ag, sd, cg in BATCHED_RAGGED:
+        if want('nnb_' + nm):
+            tf.reset_default_graph()
+            run_batched(nm, ag, 'ragged', sd, 12, coop_gamma=cg)
 
 
 SCRIPTED = [('ia2c_line', 'ia2c', 'line', 12, 6, -1), ('ia2c_fp_line', 'ia2c_fp', 'line', 13, 6, -1),

@@ -238,14 +238,19 @@ def build_product_batched(z, device):
     cls = {'ia2c': models.IA2C, 'ia2c_fp': models.IA2C_FP, 'ma2c_nc': models.MA2C_NC, 'ma2c_ic3': models.MA2C_IC3,
            'ma2c_cu': models.IA2C_CU, 'ma2c_dial': models.MA2C_DIAL}[agent]
     n_step, seed, K = int(z['n_step']), int(z['seed']), int(z['K'])
-    cp = cacc_config(agent=agent, n_step=n_step, reward_norm=float(z['reward_norm']), coop_gamma=-1)
+    coop_gamma = float(z['coop_gamma']) if 'coop_gamma' in z else -1          # (files without the key: global rewards)
+    coop_gamma = -1 if coop_gamma < 0 else coop_gamma
+    cp = cacc_config(agent=agent, n_step=n_step, reward_norm=float(z['reward_norm']), coop_gamma=coop_gamma)
     nb, dist = z['nb'], z['dist']
     N = nb.shape[0]
+    np.random.seed(seed)
+    if topo == 'ragged':        # heterogeneous agents, like build_product_model: widths / action counts recorded by run_batched
+        return cls([int(x) for x in z['n_s_ls']], [int(x) for x in z['n_a_ls']], nb, dist, coop_gamma, 10 ** 9,
+                   cp['MODEL_CONFIG'], seed=seed, num_envs=K, device=device, n_feat_ls=[int(x) for x in z['n_own']])
     n_feat, A = (5, 4) if topo == 'line' else (12, 5)
     is_ma = agent.startswith('ma2c')
     n_s_ls = [n_feat if is_ma else n_feat * (1 + int(nb[i].sum())) for i in range(N)]
-    np.random.seed(seed)
-    return cls(n_s_ls, [A] * N, nb, dist, -1, 10 ** 9, cp['MODEL_CONFIG'], seed=seed, num_envs=K, device=device)
+    return cls(n_s_ls, [A] * N, nb, dist, coop_gamma, 10 ** 9, cp['MODEL_CONFIG'], seed=seed, num_envs=K, device=device)
 
 
 def drive_batched(model, z, saved=False, compact=False):
@@ -258,7 +263,13 @@ def drive_batched(model, z, saved=False, compact=False):
     lock-stepped replicas, the calls BatchedTrainer makes): a prefix batch without update, the episode boundary
     (replicas 0, 1 restart: reset_states(mask), done_pre = 1), the main batch, ONE update.  Observations are written
     into buf_x; the scripted actions are forced through the kernels' own draw with uniforms placed in the middle of the
-    golden CDF interval of the wanted action (mode SAMPLE_UNIFORM), so the fused policy/value kernels run unchanged."""
+    golden CDF interval of the wanted action (mode SAMPLE_UNIFORM), so the fused policy/value kernels run unchanged.
+
+    Heterogeneous nets (topo 'ragged'): X is zero past each agent's own width and the golden PI is zero past its action
+    count, so the slab below is the padded-slot layout of the product's own `_obs_to_slab` (asserted on step 0 against the
+    reference's tightly concatenated observation vectors) and the forced draw uses the padded golden CDF (flat over the
+    padding: the wanted action's interval never touches it).  Spatial fixtures (coop_gamma >= 0) carry per-agent rewards
+    REW [K,2,T,N]."""
     import torch
     from deeprl_network_amd import ops
     X, ACT, REW, PIg = z['X'], z['ACT'], z['REW'], z['PI']
@@ -266,6 +277,8 @@ def drive_batched(model, z, saved=False, compact=False):
     N, A, dev = model.n_agent, model.n_a, model.device
     F = X.shape[-1]
     nbrs = model.policy.nbrs
+    ragged = str(z['topo']) == 'ragged'
+    assert not (ragged and compact), 'enable_compact_obs refuses heterogeneous nets'
     model.masked_steps = (0,)
     if saved:
         assert model.enable_saved_activations(), 'this policy cannot save its rollout activations'
@@ -289,10 +302,28 @@ def drive_batched(model, z, saved=False, compact=False):
         u = np.where(live[:, None], 0.5 * (lo + hi), 0.5)
         return torch.from_numpy(u.astype(np.float32)).to(dev)
 
+    if not compact:
+        # step 0 of the main batch, every replica: the slab == what the product's reference-compatible API builds from the
+        # reference's observation vectors (own features, then each neighbour's, tightly concatenated; IA2C-FP: + fingerprints)
+        n_own = [int(v) for v in z['n_own']] if ragged else [F] * N
+        is_ma = str(z['agent']).startswith('ma2c')
+        mine = slab(X[:, 1, 0])
+        for k in range(K):
+            ob = []
+            for i in range(N):
+                cur = [X[k, 1, 0, i, :n_own[i]]]
+                if not is_ma:
+                    cur += [X[k, 1, 0, j, :n_own[j]] for j in nbrs[i]]
+                if model.uses_fingerprint_obs():
+                    cur += [np.ones(model.n_a_ls[j]) / model.n_a_ls[j] for j in nbrs[i]]
+                ob.append(np.concatenate(cur))
+            assert torch.equal(model._obs_to_slab(ob)[0][0], mine[k]), 'observation slab layout (replica %d)' % k
+
     zero = torch.zeros(K, dtype=torch.float32, device=dev)
     scratch = torch.zeros(K, N, dtype=torch.uint8, device=dev)
     PI = np.zeros_like(PIg)
     V = np.zeros_like(z['V'])
+    DRAWN = np.zeros(ACT.shape, dtype=np.int64)             # every action the kernels drew, forced or not
     model.reset_states()
     done_pre = torch.ones(K, dtype=torch.float32, device=dev)
     live = {0: np.arange(K) >= 2, 1: np.ones(K, bool)}      # replicas 0, 1 have no golden prefix (restarted afterwards)
@@ -305,6 +336,7 @@ def drive_batched(model, z, saved=False, compact=False):
             model.act(d, mode=ops.SAMPLE_UNIFORM, u=uniforms(PIg[:, ph, t], ACT[:, ph, t], live[ph]), done_is_zero=(t > 0))
             got = model.buf_act[t].cpu().numpy()
             assert np.array_equal(got[live[ph]], ACT[:, ph, t][live[ph]]), 'forced action draw failed at step %d' % t
+            DRAWN[:, ph, t] = got
             PI[:, ph, t] = model.buf_fp[t + 1].permute(1, 0, 2).cpu().numpy()
             if not saved:
                 V[:, ph, t] = model.buf_v[t].t().cpu().numpy()
@@ -313,6 +345,7 @@ def drive_batched(model, z, saved=False, compact=False):
         v = model.bootstrap(zero, scratch, mode=ops.SAMPLE_UNIFORM, u=uniforms(PIg[:, ph, T], ACT[:, ph, T], live[ph]),
                             done_is_zero=True)
         PI[:, ph, T] = model._pi_boot.permute(1, 0, 2).cpu().numpy()
+        DRAWN[:, ph, T] = scratch.cpu().numpy()
         V[:, ph, T] = v.t().cpu().numpy()
         if ph == 0:
             # batch boundary WITHOUT an update: what update() does to the rollout state (models.py: states_bw <-
@@ -327,17 +360,66 @@ def drive_batched(model, z, saved=False, compact=False):
     last_done = torch.tensor([0, 1] + [0] * (K - 2), dtype=torch.uint8, device=dev)
     model.buf_done_post.zero_()
     model.buf_done_post[T - 1].copy_(last_done)
-    model.load_rewards(torch.from_numpy(REW[:, 1].T.astype(np.float32)).to(dev).contiguous())
+    rew = REW[:, 1].transpose(1, 0, 2) if REW.ndim == 4 else REW[:, 1].T         # [T,E,N] per-agent (spatial) or [T,E]
+    model.load_rewards(torch.from_numpy(np.ascontiguousarray(rew, dtype=np.float32)).to(dev))
     R_end = (v * (1.0 - last_done.to(torch.float32)).view(1, -1)).contiguous()
     states = np.concatenate([model.c_fw.permute(1, 0, 2).cpu().numpy(), model.h_fw.permute(1, 0, 2).cpu().numpy()], axis=2)
+    # which loss path the update takes (models._loss_backward_fused: True = ops.heads_loss, False = heads + ops.a2c_loss),
+    # and the whole parameter buffer before the step (padding must come out of it untouched)
+    fused, inner, flat0 = [], model._loss_backward_fused, model.policy.params.flat.detach().clone()
+    model._loss_backward_fused = lambda Hs: fused.append(bool(inner(Hs))) or fused[-1]
     model.update(R_end)
+    del model._loss_backward_fused
     if saved:       # the values are complete (critic's neighbour-action term added) only after update()
         V[:, 1, :T] = model.buf_v.permute(2, 0, 1).cpu().numpy()
     tot = model.last_loss[3].cpu().numpy().astype(np.float64)
     gn = model.grad_norm.cpu().numpy().astype(np.float64)
     loss, gnorm = (tot, gn) if model.per_agent_optimizer else (np.array([tot.sum()]), gn[:1])
+    # (kept apart from the record: callers compare the records of two runs key by key)
+    model.drive_extras = dict(DRAWN=DRAWN, fused=fused, flat0=flat0)
     return dict(PI=PI, V=V, RB=R_end.t().cpu().numpy(), STATES=states, LOSS=loss, GN=gnorm, saved=saved,
                 STATS=var_stats_from_named(model.policy.params.ref_variables()))
+
+
+def check_ragged_batched(model, z, out):
+    """What the padded arrangement of a heterogeneous net (policies.BatchedPolicy) must keep through a batched rollout and
+    update, beyond the reference's numbers: no action outside an agent's own set is ever drawn (forced draws or not), the
+    padded policy columns are exactly 0, the padding of every parameter -- the -1e30 logit bias included -- and variables the
+    reference does not create come out of the update bit for bit as they went in, with an exactly zero gradient; and the
+    engine took the path these nets are meant to take."""
+    import torch
+    K = int(z['K'])
+    n_a_ls = [int(v) for v in z['n_a_ls']]
+    ps, ex = model.policy.params, model.drive_extras
+    assert model.policy.hetero and not model.identical_agent
+    for i, n in enumerate(n_a_ls):
+        assert (ex['DRAWN'][..., i] < n).all(), 'agent %d drew an action it does not have' % i
+        assert (out['PI'][..., i, n:] == 0).all(), 'agent %d: probability in a padded column' % i
+        pb = ps['pi_b'].detach()
+        assert bool((pb[i, n:] == -1e30).all()), 'agent %d: padded logit bias moved' % i
+        assert bool((ps['pi_w'].detach()[i, :, n:] == 0).all()), 'agent %d: padded actor weight column moved' % i
+    # entries of the flat buffers that belong to no reference variable: the padding inside existing variables and whole variables
+    # the reference does not create (agent 4 has no neighbours).  Only where the latter exist does the store carry an update
+    # mask; elsewhere the kernels' raw gradient itself must be exactly 0 on the padding
+    own = np.zeros((model.n_agent, ps.P), dtype=bool)
+    for i, key, o, size, shape, lay in ps._entries():
+        if lay.exists:
+            blk = np.zeros(shape, dtype=bool)
+            ps._region(blk, lay)[...] = True
+            own[i, o:o + size] = blk.ravel()
+    off = torch.from_numpy(~own).to(ps.flat.device)
+    if ps.mask is not None:
+        assert torch.equal(ps.mask == 0, off)
+    assert bool((ps.grad[off] == 0).all()), 'gradient on an entry the reference does not have'
+    assert torch.equal(ps.flat.detach()[off], ex['flat0'][off]), 'the update moved a padded entry'
+    # one optimiser over heterogeneous agents (MA2C family, ConseNet included: ConsensusPolicy is an NCMultiAgentPolicy,
+    # policies.py:339): quirk Q6 needs the autograd heads + ops.a2c_loss; one optimiser per agent: ops.heads_loss
+    # (the one-pass kernel has no restatement on the CPU emulation: there every net takes the autograd heads)
+    assert ex['fused'] == [bool(model.per_agent_optimizer) and model.device.type == 'cuda'], ex['fused']
+    assert model.per_agent_optimizer == (str(z['agent']) in ('ia2c', 'ia2c_fp'))
+    if str(z['agent']) == 'ma2c_nc':                        # message input 64 x 3 neighbours > MSG_MAX_K: launch-per-step forms
+        from deeprl_network_amd import ops
+        assert model.policy.n_h * model.policy.m_max > ops.MSG_MAX_K and not model.policy.pv_one_launch(K)
 
 
 def compare_batched(out, z, rtol_fw=1e-4, rtol_w=1e-3):

@@ -5,7 +5,7 @@ Where /root/reference exists (the authoring container; never on the GPU box) the
 directory and every array is compared for exact equality (dtype, shape, bytes) with the committed file.  The full set
 takes ~25 CPU-minutes (the reference's graphs run on the float64 fake-TF shim), so by default a representative
 subset is regenerated -- all 15 environment trajectories, the orthogonal-init draws, one scripted run per model family
-and the E = 4, n_step = 60 batched-update case; NMARL_REGEN_ALL=1 regenerates every fixture (round 2: the 36 fixtures
+the E = 4, n_step = 60 batched-update case and the heterogeneous NeurComm one (n_step 12); NMARL_REGEN_ALL=1 regenerates every fixture (round 2: the 36 fixtures
 of round 1 -- 15 cacc, ortho, 18 nn, 2 e2e -- were regenerated and found identical array by array)."""
 import glob
 import os
@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, 'golden')
 pytestmark = pytest.mark.skipif(not os.path.isdir('/root/reference/agents'), reason='needs the reference checkout')
 
-FAST_NN = 'ortho_init,nn_ia2c_fp_line,nn_ma2c_nc_line,nn_ma2c_ic3_ragged,nnb_ia2c_fp_line,nnb_ma2c_cu_line'
+FAST_NN = 'ortho_init,nn_ia2c_fp_line,nn_ma2c_nc_line,nn_ma2c_ic3_ragged,nnb_ia2c_fp_line,nnb_ma2c_cu_line,nnb_ma2c_nc_ragged'
 
 
 def _same(out_dir, expect_at_least):

@@ -33,13 +33,16 @@ def test_batched_update_matches_reference_replicas_on_gpu(path, saved):
     (policies.py:20-48, 232-273; agents/utils.py:763-775, 837-855; tests/golden/make_golden_nn.py run_batched).
     Forward rtol 1e-4, post-update weights rtol 1e-3.  saved_acts: the rollout's step kernel hands gates /
     states / LSTM inputs to the update (no forward pass there) -- what BatchedTrainer does for uncoupled nets."""
-    from helpers import build_product_batched, compare_batched, drive_batched
+    from helpers import build_product_batched, check_ragged_batched, compare_batched, drive_batched
     z = load_npz(path)
     model = build_product_batched(z, 'cuda')
     if saved and not model.policy.can_save_acts:
         pytest.skip('coupled net: the update recomputes its forward pass')
     np.testing.assert_allclose(var_stats_from_named(model.policy.params.ref_variables()), z['stats0'], rtol=1e-6, atol=1e-7)
-    compare_batched(drive_batched(model, z, saved=saved), z)
+    out = drive_batched(model, z, saved=saved)
+    if str(z['topo']) == 'ragged':           # heterogeneous nets (n_step 12; one with spatial returns): the padding's invariants and the path taken
+        check_ragged_batched(model, z, out)
+    compare_batched(out, z)
 
 
 @pytest.mark.parametrize('agent', ['ia2c_fp', 'ia2c', 'ma2c_cu'])

@@ -73,8 +73,9 @@ BATCHED = sorted(glob.glob(os.path.join(GOLDEN, 'nnb_*.npz')))
 @pytest.mark.parametrize('path', BATCHED, ids=[os.path.basename(c)[4:-4] for c in BATCHED])
 def test_batched_update_equals_mean_of_reference_replica_gradients(path, saved):
     """E = K = 4 replicas, n_step 60 / 120: the product's batched update == mean over K independent reference models'
-    gradients -> clip -> one RMSProp step (tests/golden/make_golden_nn.py run_batched), host logic on CPU emulation."""
-    from helpers import build_product_batched, compare_batched, drive_batched
+    gradients -> clip -> one RMSProp step (tests/golden/make_golden_nn.py run_batched), host logic on CPU emulation.
+    *_ragged: the reference's heterogeneous nets (n_step 12; one with spatial returns) + helpers.check_ragged_batched."""
+    from helpers import build_product_batched, check_ragged_batched, compare_batched, drive_batched
     z = load_npz(path)
     with cpu_ops():
         model = build_product_batched(z, 'cpu')
@@ -82,6 +83,8 @@ def test_batched_update_equals_mean_of_reference_replica_gradients(path, saved):
             pytest.skip('coupled net: the update recomputes its forward pass')
         np.testing.assert_allclose(var_stats_from_named(model.policy.params.ref_variables()), z['stats0'], rtol=1e-6, atol=1e-7)
         out = drive_batched(model, z, saved=saved)
+        if str(z['topo']) == 'ragged':
+            check_ragged_batched(model, z, out)
     compare_batched(out, z)
 
 
