@@ -590,6 +590,8 @@ def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, ad
 def rmsprop_tf_clip(w, g, ms, scratch, lr, rho, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False):
     """tf.clip_by_global_norm + ApplyRMSProp (policies.py:32-39), per row (= optimiser) of [G,P]."""
     with torch.no_grad():
+        if lr_dev is not None:
+            lr = lr_dev.reshape(-1)[0]            # the device scalar overrides the host value, read per call
         gs = g * grad_scale
         norm = gs.pow(2).sum(dim=1, keepdim=True).sqrt()
         if max_norm > 0:
