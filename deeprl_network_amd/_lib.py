@@ -214,6 +214,7 @@ SIGNATURES = {
     'nmarl_atsc_traffic_begin': [_i64, _i32, _i32, _p, _p, _p, _p, _p],
     'nmarl_atsc_traffic_step': [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_atsc_greedy': [_i64, _i32, _i32, _p, _p, _p, _i64, _p, _p],
+    'nmarl_atsc_maxpressure': [_i64, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p, _p],
     'nmarl_nbr_gather_fwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],
     'nmarl_nbr_gather_bwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],
     'nmarl_nbr_mean_fwd': [_i64, _i32, _i32, _i32, _p, _p, _p, _p],

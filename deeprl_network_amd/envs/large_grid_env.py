@@ -20,6 +20,7 @@ from .. import _lib
 N_NODE, N_FEAT, N_OBS, N_PHASE = 25, 12, 60, 5
 N_NODE_MAX = 32                   # one replica per 32-lane half wave, lane = intersection (csrc/grid_tile.h)
 OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
+RULE_AGENTS = ('greedy', 'maxpressure')      # rule-based controllers: own-row observations, the global reward
 
 
 def grid_shape_from_config(config):
@@ -280,7 +281,7 @@ class LargeGridBatchEnv:
 
 class LargeGridEnv:
     """Reference duck-type (atsc_env.py:77-524 / large_grid_env.py:48-137) for ONE replica.
-    Observation lists: `ma2c*` / `greedy` 12 wave features; `ia2c*` own + neighbours' in the reference's `neighbor_map` list
+    Observation lists: `ma2c*` / `greedy` / `maxpressure` 12 wave features; `ia2c*` own + neighbours' in the reference's `neighbor_map` list
     order (north, east, south, west: atsc_env.py:263-269, `neighbor_order`) (+ the neighbours' fingerprints in the same order
     for ia2c_fp); neighbour actions in mask order (ascending, atsc_env.py:132-136)."""
 
@@ -368,7 +369,7 @@ class LargeGridEnv:
             self.record.step()                                         # one launch behind the step, nothing read back here
         global_reward = float(g.item())
         done = bool(done.item())
-        if self.agent == 'greedy' or self.coop_gamma < 0:                           # atsc_env.py:205-206
+        if self.agent in RULE_AGENTS or self.coop_gamma < 0:                        # atsc_env.py:205-206
             reward = global_reward
         else:
             reward = reward[0].cpu().numpy().astype(np.float64)

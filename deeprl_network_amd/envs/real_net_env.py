@@ -65,6 +65,7 @@ PHASE_SETS = {
 }
 N_GROUP = 4
 OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
+RULE_AGENTS = ('greedy', 'maxpressure')      # rule-based controllers: own-row observations, the global reward
 
 
 class RealNetController:
@@ -247,7 +248,7 @@ class RealNetBatchEnv:
         self.n_agent, self.n_a, self.n_a_ls = tp.N, tp.A, list(tp.n_a_ls)
         self.n_feat, self.n_feat_ls = tp.L, list(tp.n_s_ls)               # own observation widths (heterogeneous)
         self.neighbor_mask, self.distance_mask = tp.neighbor_mask, tp.distance_mask
-        if self.agent.startswith('ma2c') or self.agent == 'greedy':      # (greedy: atsc_env.py:256-257)
+        if self.agent.startswith('ma2c') or self.agent in RULE_AGENTS:   # (greedy: atsc_env.py:256-257)
             self.n_s_ls = list(tp.n_s_ls)
         else:                                                            # own + listed neighbours' (atsc_env.py:263-269)
             self.n_s_ls = [tp.n_s_ls[i] + sum(tp.n_s_ls[j] for j in tp.nbrs[i]) for i in range(tp.N)]
@@ -315,7 +316,7 @@ class RealNetBatchEnv:
 
 class RealNetEnv:
     """Reference duck-type (atsc_env.py:77-524 / real_net_env.py:145-198) for ONE replica: ragged observation lists
-    (`ma2c*` / `greedy`: the node's own links; `ia2c*`: own + listed neighbours' in ascending node index, + their fingerprints
+    (`ma2c*` / `greedy` / `maxpressure`: the node's own links; `ia2c*`: own + listed neighbours' in ascending node index, + their fingerprints
     for ia2c_fp), ragged fingerprints, per-agent rewards."""
 
     def __init__(self, config, port=0, device='cuda', **_):
@@ -402,7 +403,7 @@ class RealNetEnv:
             self.record.step()                                         # one launch behind the step, nothing read back here
         global_reward = float(g.item())
         done = bool(done.item())
-        if self.agent == 'greedy' or (self.coop_gamma < 0 and self.train_mode):     # atsc_env.py:205-206
+        if self.agent in RULE_AGENTS or (self.coop_gamma < 0 and self.train_mode):  # atsc_env.py:205-206
             reward = global_reward
         else:
             reward = reward[0].cpu().numpy().astype(np.float64) if self.coop_gamma >= 0 else global_reward

@@ -11,6 +11,7 @@ from .agents.models import IA2C, IA2C_CU, IA2C_FP, MA2C_DIAL, MA2C_IC3, MA2C_NC
 from .envs import init_env, make_batch_env
 from .envs.greedy import GreedyBatchController
 from .envs.large_grid_env import LargeGridController
+from .envs.maxpressure import MaxPressureBatchController, MaxPressureController
 from .envs.real_net_env import RealNetController
 from .utils import (BatchedEvaluator, BatchedTrainer, Counter, Evaluator, SummaryWriter, Trainer, check_dir, copy_file, find_file,
                     init_dir, init_log)
@@ -52,6 +53,8 @@ def init_agent(env, config, total_step, seed, **kw):
         if env.name.endswith('large_grid'):
             return LargeGridController(getattr(env, 'node_names', None))
         return RealNetController(env.node_names) if env.name.endswith('real_net') else None
+    if env.agent == 'maxpressure':             # the max-pressure baseline of the same scenarios (envs/maxpressure.py)
+        return MaxPressureController.for_env(env) if env.name.endswith(('large_grid', 'real_net')) else None
     cls = AGENTS.get(env.agent)
     if cls is None:
         return None
@@ -88,6 +91,12 @@ def train(args):
     elif args.lstm_precision is not None:
         config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
     env_cfg = config['ENV_CONFIG']
+    if env_cfg.get('agent') in ('greedy', 'maxpressure'):
+        # the rule-based ATSC baselines have nothing to train (no add_transition / backward / save): say so instead of dying on an
+        # AttributeError after the first env step with a half-initialised run directory -- `main.py evaluate` is their mode
+        # (asked before TRAIN_CONFIG is read: their inis have neither that section nor MODEL_CONFIG)
+        logging.error('Training: agent "%s" is a rule-based controller; run `main.py evaluate` on it' % env_cfg.get('agent'))
+        return
     total_step = int(config.getfloat('TRAIN_CONFIG', 'total_step'))
     test_step = int(config.getfloat('TRAIN_CONFIG', 'test_interval'))
     log_step = int(config.getfloat('TRAIN_CONFIG', 'log_interval'))
@@ -96,11 +105,6 @@ def train(args):
     num_envs = args.num_envs if args.num_envs is not None else env_cfg.getint('num_envs', fallback=1)
     device = torch.device('cuda', local)
     writer = SummaryWriter(dirs['log']) if rank == 0 else None
-    if env_cfg.get('agent') == 'greedy':
-        # the rule-based ATSC baseline has nothing to train (no add_transition / backward / save): say so instead of dying on an
-        # AttributeError after the first env step with a half-initialised run directory -- `main.py evaluate` is its mode
-        logging.error('Training: agent "greedy" is a rule-based controller; run `main.py evaluate` on it')
-        return
     if num_envs <= 1 and world == 1:
         env = init_env(env_cfg, device=device)                       # seeds np.random (cacc_env.py:22)
         logging.info('Training: a dim %r, agent dim: %d' % (env.n_a_ls, env.n_agent))
@@ -137,7 +141,7 @@ def _open_run(run_dir):
 
 
 def model_config(cfg):
-    """The run's MODEL_CONFIG section; None where the ini has none (config_greedy.ini: the rule-based agent reads no model keys)."""
+    """The run's MODEL_CONFIG section; None where the ini has none (config_greedy.ini, config_maxpressure*.ini: a rule-based agent reads no model keys)."""
     return cfg['MODEL_CONFIG'] if cfg.has_section('MODEL_CONFIG') else None
 
 
@@ -164,7 +168,7 @@ def evaluate(args):
 
 def evaluate_batched(cfg, seeds, run_dir, output_path):
     """`main.py evaluate --batched`: the seeds are the replicas of one batch env, the policy is built for that many replicas (or
-    is the batched greedy controller), and BatchedEvaluator writes the CSVs the loop above writes.  A scenario / agent pair the
+    is the batched greedy / max-pressure controller), and BatchedEvaluator writes the CSVs the loop above writes.  A scenario / agent pair the
     batch engine cannot build raises the engine's own error."""
     E = len(seeds)
     if E < 1:
@@ -174,6 +178,8 @@ def evaluate_batched(cfg, seeds, run_dir, output_path):
     env = make_batch_env(env_cfg, num_envs=E)
     if env.agent == 'greedy':
         model = GreedyBatchController(env)
+    elif env.agent == 'maxpressure':
+        model = MaxPressureBatchController(env)
     else:
         model = init_agent(env, model_config(cfg), 0, 0, num_envs=E)
     if model is None or not model.load(os.path.join(run_dir, 'model') + '/'):

@@ -1748,6 +1748,27 @@ def atsc_greedy(n_a, mask, obs, out, a_max=8):
     return out
 
 
+def atsc_maxpressure(n_a, mask, gptr, gpair, tgrp, tw, obs, out, n_feat, a_max=8):
+    """nmarl_atsc_maxpressure: the max-pressure ATSC agent for every (replica, node) in one launch.  n_a [N] i32 and mask [N,8] i32
+    are the greedy agent's table; gptr [G+1] i32, gpair [P,2] i16 the downstream groups in CSR form; tgrp [N,24,3] i16 and
+    tw [N,24,3] f32 the terms of every (node, feature) (envs/maxpressure.py grid_pressure_table, net_pressure_table; the rule is
+    DESIGN.md 6).  obs [E,N,obs_row] f32 is an env's observation buffer as it is, whose rows lead with the node's own wave vector
+    of at most n_feat features; out [E,N] u8 receives the actions; a_max: an upper bound of n_a."""
+    N = obs.shape[1] if obs.dim() == 3 else -1
+    if obs.dim() != 3 or tuple(out.shape) != tuple(obs.shape[:2]) or tuple(mask.shape) != (N, 8) or tuple(n_a.shape) != (N,) or \
+            gptr.dim() != 1 or gptr.numel() < 1 or gpair.dim() != 2 or gpair.shape[1] != 2 or \
+            tuple(tgrp.shape) != (N, 24, 3) or tuple(tw.shape) != (N, 24, 3):
+        raise _lib.NmarlError('atsc_maxpressure: obs [E,N,row], out [E,N], n_a [N], mask [N,8], gptr [G+1], gpair [P,2], '
+                              'tgrp / tw [N,24,3] (got %s, %s, %s, %s, %s, %s, %s, %s)'
+                              % tuple(tuple(t.shape) for t in (obs, out, n_a, mask, gptr, gpair, tgrp, tw)))
+    E, _, row = obs.shape
+    check(lib.nmarl_atsc_maxpressure(E, N, int(a_max), int(n_feat), ptr(n_a, torch.int32), ptr(mask, torch.int32),
+                                     gptr.numel() - 1, gpair.shape[0], ptr(gptr, torch.int32), ptr(gpair, torch.int16),
+                                     ptr(tgrp, torch.int16), ptr(tw, F32), ptr(obs, F32), row, ptr(out, torch.uint8), stream()),
+          'nmarl_atsc_maxpressure')
+    return out
+
+
 A2C_LOSS_MAX_A = 8
 
 

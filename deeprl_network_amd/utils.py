@@ -136,7 +136,7 @@ class Trainer:
     LSTM from the state the policy forward just wrote -- Q1) and `_walk` (a generator that advances an episode cursor one
     env step at a time); `explore`, the bootstrap and `perform` are thin consumers of them.  It drives any env with the
     reference duck-type (envs.cacc_env.CACCEnv is the GPU E = 1 adapter); models without a policy (`agent == 'greedy'`,
-    large_grid_env.py:30-45) decide through `model.forward(ob)` alone."""
+    large_grid_env.py:30-45, and `agent == 'maxpressure'`) decide through `model.forward(ob)` alone."""
 
     def __init__(self, env, model, global_counter, summary_writer, output_path=None):
         assert env.T % model.n_step == 0
@@ -156,7 +156,7 @@ class Trainer:
         """-> _Decision.  Call order on the model: forward(.., 'p') then forward(.., 'v') (the second advances nothing the
         first did not: it re-steps a scratch copy, Q1)."""
         env, model = self.env, self.model
-        if self.agent == 'greedy':                               # rule-based controller: actions straight from the observation
+        if self.agent in ('greedy', 'maxpressure'):              # rule-based controller: actions straight from the observation
             return _Decision(None, np.asarray(model.forward(ob)))
         fps = env.get_fingerprint() if self._stacked else None
         pi = model.forward(ob, done, fps) if self._stacked else model.forward(ob, done)
@@ -857,8 +857,8 @@ class _PolicyLockSteps:
 
 
 class _GreedyLockSteps:
-    """The same T lock-steps under the rule-based controller: one nmarl_atsc_greedy launch on the env's observation buffer,
-    then the env step."""
+    """The same T lock-steps under a rule-based controller (`forward_batch`): one nmarl_atsc_greedy / nmarl_atsc_maxpressure
+    launch on the env's observation buffer, then the env step."""
 
     def __init__(self, env, controller):
         self.env, self.controller = env, controller
@@ -954,10 +954,11 @@ class BatchedEvaluator:
         uploaded once) -- a stream of its own, comparable to the one-replica path's unseeded host np.random.choice in
         distribution only; `agent = greedy`: nmarl_atsc_greedy on the env's observation buffer (the grid) or on the
         own vectors staged from it (the network, whose rows are no multiple of 16 bytes: GreedyBatchController);
+        `agent = maxpressure`: nmarl_atsc_maxpressure on the env's observation buffer as it is (MaxPressureBatchController);
       * per lock-step: policy step (or greedy launch), env step without auto-reset writing D[t] / G[t], on ATSC the traffic
         recorder's launch, on CACC one copy of (h, v, u) into hist[t + 1];
       * afterwards: one copy of each buffer to the host; a replica's rows stop with its first done.
-    env: make_batch_env(..., num_envs=len(seeds)); model: a policy built with num_envs=len(seeds), or GreedyBatchController.
+    env: make_batch_env(..., num_envs=len(seeds)); model: a policy built with num_envs=len(seeds), GreedyBatchController or MaxPressureBatchController.
     use_graph: the T lock-steps as one captured hipGraph (launches of this library only inside, plus the network controller's
     staging copy, a torch kernel node); eager is the default and, as measured, no slower (profiles/r15_batched_evaluate.txt)."""
 

@@ -335,6 +335,32 @@ int nmarl_atsc_greedy(int64_t E, int32_t N, int32_t A_max, const int32_t* n_a, c
                       int64_t obs_row, uint8_t* action, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* The rule-based `maxpressure` agent of the ATSC scenarios for E replicas    */
+/* (Varaiya 2013); kernel and mapping in csrc/maxpressure.hip, rule and the   */
+/* tables of both scenarios in DESIGN 6                                       */
+/* ------------------------------------------------------------------------- */
+/* Node j of replica e has its OWN wave vector at obs + (e * N + j) * obs_row floats, F features wide (F = the widest own vector:
+ * 12 on the grid, 22 on the network).  Any row pitch obs_row >= F is read as it is, with 4-byte loads: the compact grid
+ * observation [E,N,12], the grid slab [E,N,60], the network's [E,N,22] and its env buffer [E,N,110] (no multiple of 16 bytes).
+ * Static tables (device), validated by the host (envs/maxpressure.py check_pressure_table):
+ *   n_a [N] i32, mask [N][8] u32     the greedy agent's: bit k of mask[i][a] set = feature k counts for phase a (k < F);
+ *   gptr [G+1] i32, gpair [P][2] i16 downstream groups in CSR form: group g is the pairs gptr[g] .. gptr[g+1]-1, each a
+ *                                    (node < N, feature < F); every group has n_g >= 1 pairs;
+ *   tgrp [N][24][3] i16, tw [N][24][3] f32   up to three terms per (node, feature): group (-1 = none, left packed) and share.
+ * Rule, float64 on the float32 observation, x[j][f] = (double) obs[e, j, f], every operation as written, no contraction:
+ *     occ_g      = (sum over the pairs p of group g, ascending from 0.0, of x[node_p][feat_p]) / (double) n_g
+ *     press(i,k) = x[i][k];  for r = 0, 1, 2 while tgrp[i][k][r] >= 0:  press = press - (double) tw[i][k][r] * occ[tgrp[i][k][r]]
+ *     score_a    = sum over the set bits k < F of mask[i][a], k ascending from 0.0, of press(i,k),     a < n_a[i]
+ *     action[e,i]= the smallest a with the largest score_a                                            -> action [E,N] u8
+ * (n_a outside 1..A_max is clamped, not reported).  One launch for any E, no host synchronisation, no atomics, independent of E
+ * and of the launch grid.
+ * NMARL_EINVAL without a launch: E < 1, N outside 1..32, A_max outside 1..8, F outside 1..24, G outside 0..128, P outside
+ * 0..768, obs_row < F, a NULL array, obs not 4-byte aligned. */
+int nmarl_atsc_maxpressure(int64_t E, int32_t N, int32_t A_max, int32_t F, const int32_t* n_a, const uint32_t* mask, int32_t G,
+                           int32_t P, const int32_t* gptr, const int16_t* gpair, const int16_t* tgrp, const float* tw,
+                           const float* obs, int64_t obs_row, uint8_t* action, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Neighbourhood aggregation over the fixed adjacency (agent-major [N,E,F])   */
 /* ------------------------------------------------------------------------- */
 /*
