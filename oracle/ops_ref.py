@@ -186,17 +186,50 @@ def lstm_msg_wimage(w_msg, out=None):
     return torch.zeros(w_msg.shape[0], 1) if out is None else out
 
 
-def lstm_wimage(wx, wh, out=None):
+PRECISIONS = ('fp32', 'bf16x3')
+
+
+def check_precision(precision, what='precision'):
+    if precision not in PRECISIONS:
+        raise ValueError('%s: %r is not one of %s' % (what, precision, ', '.join(PRECISIONS)))
+    return precision
+
+
+def lstm_wimage(wx, wh, out=None, precision='fp32'):
     """The product's chunked LDS image of [wx; wh] is a kernel-side layout; the restatement multiplies by wx / wh
     directly, so the 'image' is just a token."""
+    check_precision(precision, 'lstm_wimage')
     return torch.zeros(wh.shape[0], 1) if out is None else out
 
 
-def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=None):
+def bf16_split(a):
+    """a -> (hi, lo) in a's dtype: hi = bf16_rne(a), lo = bf16_rne(a - hi), what the product's bf16x3 forms multiply
+    (csrc/lstm_mfma.hip chunk_bf16x3, lstm_wimage_bf16x3_kernel)."""
+    a32 = a.float()
+    hi = a32.to(torch.bfloat16).float()
+    lo = (a32 - hi).to(torch.bfloat16).float()
+    return hi.to(a.dtype), lo.to(a.dtype)
+
+
+def step_product(a, w, precision='fp32'):
+    """a [N,E,K] @ w [N,K,4H] of the lock-step: exact, or ('bf16x3') the three split products hi_a hi_b + hi_a lo_b + lo_a hi_b
+    summed in the operands' dtype."""
+    if precision == 'fp32':
+        return torch.bmm(a, w)
+    ah, al = bf16_split(a)
+    wh, wl = bf16_split(w)
+    return torch.bmm(ah, wh) + torch.bmm(ah, wl) + torch.bmm(al, wh)
+
+
+def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=None, precision='fp32'):
     """agents/utils.py:102-113 with z = zadd1 (+ zadd2) + (h*(1-done)) @ wh; with xs = (x, wx, image) the x-side
-    product x @ wx is part of the step (z = x @ wx + (h*(1-done)) @ wh (+ zadd1) (+ zadd2))."""
+    product x @ wx is part of the step (z = x @ wx + (h*(1-done)) @ wh (+ zadd1) (+ zadd2)).  precision 'bf16x3': both
+    products as the split product of `step_product` (the uncoupled nets' forms: no message term)."""
+    check_precision(precision, 'lstm_step_fused')
+    if precision != 'fp32' and xs is not None and len(xs) > 4 and xs[4] is not None:
+        raise ValueError('lstm_step_fused: bf16x3 exists for the forms without a message term only')
     keep = (1.0 - done).view(1, -1, 1)
-    z = torch.bmm(h * keep, wh)
+    z = step_product(h * keep, wh, precision)
     if xs is not None:
         x = xs[0]
         if len(xs) > 3 and xs[3] is not None:          # [x | x2]: the last columns of the LSTM input from a second tensor
@@ -239,7 +272,7 @@ def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out
                 m['out'].copy_(t)
             x = t if x is None else torch.cat([x, t], dim=-1)
         if x is not None:
-            z = z + torch.bmm(x, xs[1])
+            z = z + step_product(x, xs[1], precision)
     if zadd1 is not None:
         z = z + zadd1
     if zadd2 is not None:
@@ -255,9 +288,9 @@ def lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out
 
 
 def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w, pi_b, pi_out, act_out, mode,
-                     u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, gates=None):
+                     u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, gates=None, precision='fp32'):
     """forward('p') (policies.py:119-123, 50-57) + the action draw (utils.py:135-141) after one LSTM step."""
-    lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=xs)
+    lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, gates, c_out, h_out, xs=xs, precision=precision)
     nxt = xs[4].get('next') if xs is not None and len(xs) > 4 and xs[4] is not None else None
     if nxt is not None:                                # lstm_dial: the sender layer on the new h (agents/utils.py:566-569)
         nxt['out'].copy_(torch.relu(torch.bmm(h_out, nxt['w']) + nxt['b'].unsqueeze(1)))
@@ -266,9 +299,10 @@ def lstm_step_policy(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, pi_w
     return pi_out, act_out
 
 
-def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, v_b, action, nbr_idx, n_a, v_out, xs=None):
+def lstm_step_value(h, wh, bias, zadd1, zadd2, c_prev, done, c_out, h_out, v_w, v_b, action, nbr_idx, n_a, v_out, xs=None,
+                    precision='fp32'):
     """forward('v') (policies.py:124-133, 59-77): v = [h', one_hot(neighbour actions)] @ w + b."""
-    lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, None, c_out, h_out, xs=xs)
+    lstm_step_fused(h, wh, bias, zadd1, zadd2, c_prev, done, None, c_out, h_out, xs=xs, precision=precision)
     na = nbr_onehot(action, nbr_idx, n_a)
     v_out.copy_((torch.bmm(torch.cat([h_out, na], dim=-1), v_w) + v_b.unsqueeze(1)).squeeze(-1))
     return v_out
@@ -405,7 +439,7 @@ def step_enc_forward(d):
 
 def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_out, act_out, v_w, v_b, nbr_idx, n_a,
                            v_out, mode, u=None, seed=0, env_id_base=0, step=0, step_dev=None, xs=None, h_out=None,
-                           c_out=None, gates=None, defer_action_term=False):
+                           c_out=None, gates=None, defer_action_term=False, precision='fp32'):
     """Trainer._get_policy + _get_value of one lock-step (utils.py:129-149): forward('p') advances the state, forward('v')
     re-steps a COPY of it (policies.py:119-133, quirk Q1)."""
     h_out, c_out = (h if h_out is None else h_out), (c if c_out is None else c_out)
@@ -426,19 +460,19 @@ def lstm_step_policy_value(h, wh, bias, zadd1, zadd2, c, done, pi_w, pi_b, pi_ou
         xs_g = xs
         if xs_p is not xs:                   # (the gates are the POLICY step's: its message term, without its outputs)
             xs_g = tuple(xs[:4]) + (dict(xs[4], _carry_role='policy'),)
-        lstm_step_fused(h, wh, bias, zadd1, zadd2, c, done, gates, torch.empty_like(c), torch.empty_like(h), xs=xs_g)
+        lstm_step_fused(h, wh, bias, zadd1, zadd2, c, done, gates, torch.empty_like(c), torch.empty_like(h), xs=xs_g, precision=precision)
         if xs_p is not xs:                   # the step below writes (h_out, c_out); the message term needs the OLD h of all agents
             assert h_out.data_ptr() != h.data_ptr()
     lstm_step_policy(h, wh, bias, zadd1, zadd2, c, done, c_out, h_out, pi_w, pi_b, pi_out, act_out, mode, u=u, seed=seed,
-                     env_id_base=env_id_base, step=step, step_dev=step_dev, xs=xs_p)
+                     env_id_base=env_id_base, step=step, step_dev=step_dev, xs=xs_p, precision=precision)
     if defer_action_term:      # only the h part of the critic: v = h'' @ w[:H] + b
         H = h.shape[-1]
         hv, cv = torch.empty_like(h), torch.empty_like(c)
-        lstm_step_fused(h_out, wh, bias, zadd1, zadd2, c_out, done, None, cv, hv, xs=xs)
+        lstm_step_fused(h_out, wh, bias, zadd1, zadd2, c_out, done, None, cv, hv, xs=xs, precision=precision)
         v_out.copy_((torch.bmm(hv, v_w[:, :H]) + v_b.unsqueeze(1)).squeeze(-1))
     else:
         lstm_step_value(h_out, wh, bias, zadd1, zadd2, c_out, done, torch.empty_like(c), torch.empty_like(h), v_w, v_b,
-                        act_out, nbr_idx, n_a, v_out, xs=xs)
+                        act_out, nbr_idx, n_a, v_out, xs=xs, precision=precision)
     return pi_out, act_out, v_out
 
 

@@ -11,24 +11,11 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
 
 from helpers import cacc_config  # noqa: E402
+from step_edge_checks import _cell, _check, _emul, _split  # noqa: E402,F401  (the split emulation and its bounds live with the edge checks)
 
 pytestmark = pytest.mark.gpu
 
 H, CH, PITCH, CHUNK = 64, 32, 132, 10240
-
-
-def _split(a):
-    """fp32 tensor -> (hi, lo) float64, hi = bf16_rne(a), lo = bf16_rne(a - hi): what the kernels multiply."""
-    hi = a.float().to(torch.bfloat16)
-    lo = (a.float() - hi.float()).to(torch.bfloat16)
-    return hi.double(), lo.double()
-
-
-def _emul(A, W):
-    """float64 sum of the three bf16 products hi_a hi_b + hi_a lo_b + lo_a hi_b of A [N,E,K] @ W [N,K,4H], and sum |a||b|."""
-    ah, al = _split(A)
-    wh, wl = _split(W)
-    return torch.bmm(ah, wh) + torch.bmm(ah, wl) + torch.bmm(al, wh), torch.bmm(A.double().abs(), W.double().abs())
 
 
 def _image_ref(w):
@@ -72,25 +59,6 @@ def _case(N, E, KX, seed):
     return dict(x=torch.relu(r(N, E, KX)), h=torch.tanh(r(N, E, H)), c=r(N, E, H), done=(torch.rand(E, generator=g) < 0.2).float(),
                 wx=r(N, KX, 4 * H) * 0.15, wh=r(N, H, 4 * H) * 0.2, b=r(N, 4 * H) * 0.1, pi_w=r(N, H, 4) * 0.5, pi_b=r(N, 4) * 0.3,
                 v_w=r(N, H + 2 * 4, 1), v_b=r(N, 1))
-
-
-def _cell(z, c, keep):
-    i, f, o, u = torch.sigmoid(z[..., :H]), torch.sigmoid(z[..., H:2 * H]), torch.sigmoid(z[..., 2 * H:3 * H]), torch.tanh(z[..., 3 * H:])
-    cn = f * c * keep + i * u
-    return torch.cat([i, f, o, u], dim=-1), cn, o * torch.tanh(cn)
-
-
-def _check(G, C, Hn, z, c, keep, bound, what):
-    """Kernel gates / c' / h' against the cell applied to the pre-activation z whose error is at most `bound` (elementwise; the
-    activations' slopes are <= 1, c' and h' take the propagated bound), plus the fp32 epilogue's own rounding."""
-    tol = 2e-6
-    g, cn, hn = _cell(z, c, keep)
-    eg = bound + tol
-    ec = (c * keep).abs() * eg[..., H:2 * H] + g[..., 3 * H:].abs() * eg[..., :H] + g[..., :H].abs() * eg[..., 3 * H:] + tol
-    eh = torch.tanh(cn).abs() * eg[..., 2 * H:3 * H] + g[..., 2 * H:3 * H].abs() * ec + tol
-    for got, want, err, name in ((G, g, eg, 'gates'), (C, cn, ec, "c'"), (Hn, hn, eh, "h'")):
-        d = (got.cpu().double() - want).abs()
-        assert bool((d <= err).all()), '%s: %s off by %.3g (bound %.3g there)' % (what, name, float(d.max()), float(err.view(-1)[d.argmax()]))
 
 
 @pytest.mark.parametrize('E', [77, 1000, 4096])
