@@ -1,31 +1,19 @@
 """The rule-based `greedy` ATSC agent for a batch of replicas: csrc/greedy.hip behind the duck-type of the host controllers."""
 import torch
 
-from .. import _lib, ops
+from .. import ops
+from .atsc import RuleController, described
 
 
-class GreedyBatchController:
+class GreedyBatchController(RuleController):
     """`LargeGridController` / `RealNetController` for E lock-stepped replicas.  `forward_batch(obs, out)` decides every
-    (replica, node) with one launch of nmarl_atsc_greedy on the env's observation buffer -- nothing is read back --; `forward`,
-    `reset` and `load` are the host controller's, so the object also drives the one-replica loops.  The scenario is the table
-    (n_a, mask) its env module builds; the rule is DESIGN.md 6."""
+    (replica, node) with one launch of nmarl_atsc_greedy on the env's observation buffer -- nothing is read back --; `forward`
+    is the host controller's, so the object also drives the one-replica loops.  The scenario is the table (n_a, mask) its env
+    hands over (`greedy_rule`); the rule is DESIGN.md 6."""
     name = 'greedy'
-    n_step = 1
 
     def __init__(self, batch_env):
-        from .large_grid_env import LargeGridBatchEnv, LargeGridController, grid_greedy_table
-        from .real_net_env import RealNetBatchEnv, RealNetController, net_greedy_table
-        if isinstance(batch_env, LargeGridBatchEnv):
-            self.host = LargeGridController()
-            self.n_own = 12
-            n_a, mask = grid_greedy_table(batch_env.rows, batch_env.cols)
-        elif isinstance(batch_env, RealNetBatchEnv):
-            self.host = RealNetController(batch_env.topo.node_names)
-            self.n_own = int(batch_env.topo.L)
-            n_a, mask = net_greedy_table(batch_env.topo.node_names)
-        else:
-            raise _lib.NmarlError('the greedy agent is defined for the ATSC grid and network envs, not for %s'
-                                  % type(batch_env).__name__)
+        self.host, self.n_own, n_a, mask = described(batch_env, 'greedy_rule', 'greedy agent')
         self.node_names = self.host.node_names
         self.n_a_host, self.mask_host, self.a_max = n_a, mask, int(n_a.max())
         dev = torch.device(batch_env.device)
@@ -51,9 +39,3 @@ class GreedyBatchController:
 
     def forward(self, obs):
         return self.host.forward(obs)
-
-    def reset(self):
-        return
-
-    def load(self, model_dir, checkpoint=None):
-        return True

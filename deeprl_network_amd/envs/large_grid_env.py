@@ -16,11 +16,11 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .atsc import N_GROUP, OBJECTIVES, RULE_AGENTS, AtscBatchEnv, AtscEnv, RuleController, atsc_params_from_config  # noqa: F401
+from .traffic_record import grid_demand, grid_mult
 
 N_NODE, N_FEAT, N_OBS, N_PHASE = 25, 12, 60, 5
 N_NODE_MAX = 32                   # one replica per 32-lane half wave, lane = intersection (csrc/grid_tile.h)
-OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
-RULE_AGENTS = ('greedy', 'maxpressure')      # rule-based controllers: own-row observations, the global reward
 
 
 def grid_shape_from_config(config):
@@ -74,13 +74,12 @@ def grid_entries(rows=5, cols=5):
 _LANE_FIRST_LINK = (0, 3, 5, 6, 9, 11)
 
 
-class LargeGridController:
+class LargeGridController(RuleController):
     """The reference's rule-based `greedy` agent (large_grid_env.py:30-45): per node the phase whose served lanes hold the
     most vehicles.  The reference indexes a 6-lane observation [N, E lane 0, E lane 1, S, W lane 0, W lane 1]; this env's
     wave vector has one entry per signal LINK (12, duplicated lanes), so the six lanes are read at their first links.
-    Same `forward(obs) -> actions` duck-type; `reset` / `load` exist so that Trainer.perform / main.py evaluate drive it."""
+    Same `forward(obs) -> actions` duck-type."""
     name = 'greedy'
-    n_step = 1
 
     def __init__(self, node_names=None):
         self.node_names = node_names
@@ -97,12 +96,6 @@ class LargeGridController:
 
     def forward(self, obs):
         return [self.greedy(ob) for ob in obs]
-
-    def reset(self):
-        return
-
-    def load(self, model_dir, checkpoint=None):
-        return True
 
 
 # the five phases of LargeGridController.greedy as sets of lanes [N, E lane 0, E lane 1, S, W lane 0, W lane 1] (large_grid_env.py:25-26)
@@ -122,46 +115,23 @@ def grid_greedy_table(rows=5, cols=5):
 
 def grid_params_from_config(config):
     """ENV_CONFIG section -> nmarl_grid_params_t; keys of atsc_env.py:79-99 + large_grid_env.py:50-52."""
-    if config.getint('control_interval_sec') != 5 or config.getint('yellow_interval_sec') != 2:
-        raise _lib.NmarlError('the synthetic grid is specified for control 5 s / yellow 2 s')
-    p = _lib.GridParams()
-    obj = config.get('objective', fallback='queue')
-    if obj not in OBJECTIVES:
-        raise _lib.NmarlError('objective must be one of queue, wait, hybrid (atsc_env.py:87, 411-416), got %r' % obj)
-    p.objective = OBJECTIVES[obj]
-    p.coef_wait = config.getfloat('coef_wait', fallback=0.0)
-    p.norm_wave = config.getfloat('norm_wave')
-    p.clip_wave = config.getfloat('clip_wave')
+    p = atsc_params_from_config(config, _lib.GridParams(), 'grid', config.get('objective', fallback='queue'), _lib.NmarlError)
     p.peak1 = config.getfloat('peak_flow1')
     p.peak2 = config.getfloat('peak_flow2')
-    p.T = int(np.ceil(config.getint('episode_length_sec') / config.getint('control_interval_sec')))
-    p.per_agent_reward = 0 if config.getfloat('coop_gamma') < 0 else 1
     return p
 
 
-class LargeGridBatchEnv:
+class LargeGridBatchEnv(AtscBatchEnv):
     rows, cols = 5, 5                 # the reference's lattice unless ENV_CONFIG's grid_rows / grid_cols say otherwise
 
     @property
     def entries(self):
         return grid_entries(self.rows, self.cols)
 
-    def __init__(self, config, num_envs=1, device='cuda', env_id_base=0, seed=None):
-        self.config = config
-        self.E = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise _lib.NmarlError('LargeGridBatchEnv needs a HIP device; there is no CPU path')
-        self.name = config.get('scenario')
+    def _scenario(self, config):
         if self.name == 'large_grid':        # (config_greedy.ini's spelling): ONE name for the scenario -- Trainer / perform branch on 'atsc*'
             self.name = 'atsc_large_grid'
-        self.agent = config.get('agent')
-        self.coop_gamma = config.getfloat('coop_gamma')
-        self.seed = config.getint('seed') if seed is None else int(seed)
-        self.env_id_base = int(env_id_base)
-        p = grid_params_from_config(config)
-        self.params = p
-        self.T = p.T
+        self.params = grid_params_from_config(config)
         self.rows, self.cols = grid_shape_from_config(config)
         self.fixed_shape = (self.rows, self.cols) == (5, 5)       # the 5x5 kernels; any other shape: the `_rc` entries
         N = self.rows * self.cols
@@ -171,28 +141,20 @@ class LargeGridBatchEnv:
         self.neighbor_mask, self.distance_mask = grid_masks(self.rows, self.cols)
         self.neighbor_order = grid_neighbor_order(self.rows, self.cols)
         self.n_s_ls = grid_n_s_ls(self.agent, self.neighbor_mask)
-        self.train_mode = True
-        E, d = self.E, self.device
-        f32 = dict(dtype=torch.float32, device=d)
-        self.q = torch.zeros(E, N, 6, **f32)
-        self.transit = torch.zeros(E, N, 6, **f32)
-        self.prev_action = torch.zeros(E, N, dtype=torch.uint8, device=d)
-        self.t = torch.zeros(E, dtype=torch.int32, device=d)
-        self.xi = torch.ones(E, 4, **f32)
-        # `wait` / `hybrid` objectives: the front vehicle's standing time per lane (oracle/grid_ref.py step 6)
-        self.head_wait = torch.zeros(E, N, 6, **f32) if p.objective else None
-        if self.head_wait is not None:
-            p.head_wait = self.head_wait.data_ptr()
-        self.obs = torch.zeros(E, N, N_OBS, **f32)
-        self.reward = torch.zeros((E, N) if p.per_agent_reward else (E,), **f32)
-        self.done = torch.zeros(E, dtype=torch.uint8, device=d)
-        self.global_reward = torch.zeros(E, **f32)
-        self.episode = torch.zeros(E, dtype=torch.int32, device=d)
-        self.batch_size = None     # episodes end at T only; any n_step dividing T works
+        return 6, N_OBS
 
-    def state_tensors(self):
-        return [self.q, self.transit, self.prev_action, self.t, self.xi, self.obs, self.episode, self.done] + \
-            ([self.head_wait] if self.head_wait is not None else [])
+    def traffic_model(self):
+        """(mult [N,6] i32, demand [4,12] f64) of the traffic record (envs/traffic_record.py)."""
+        n_entry = [sum(1 for e in self.entries if e[2] == g) for g in range(N_GROUP)]
+        return grid_mult(self.n_agent), grid_demand(float(self.params.peak1), float(self.params.peak2), n_entry)
+
+    def greedy_rule(self):
+        """(host controller, own observation width, n_a, mask) of the batched greedy agent (envs/greedy.py)."""
+        return (LargeGridController(), N_FEAT) + grid_greedy_table(self.rows, self.cols)
+
+    def pressure_table(self):
+        from .maxpressure import grid_pressure_table
+        return grid_pressure_table(self.rows, self.cols)
 
     compact_obs = False
 
@@ -205,33 +167,19 @@ class LargeGridBatchEnv:
         self.obs = torch.zeros(self.E, self.n_agent, N_FEAT if flag else N_OBS, dtype=torch.float32, device=self.device)
         return True
 
-    def reset(self, mask=None, u0=None):
-        P = _lib.ptr
-        args = (ctypes.byref(self.params), self.E, P(mask, torch.uint8), P(u0, torch.float32), self.seed, self.env_id_base,
-                P(self.episode), P(self.q), P(self.transit), P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
+    def _reset_call(self, params, args):
         if self.fixed_shape:
-            rc = _lib.lib.nmarl_grid_reset(*args)
+            rc = _lib.lib.nmarl_grid_reset(ctypes.byref(params), *args)
         else:
-            rc = _lib.lib.nmarl_grid_reset_rc(*args, self.rows, self.cols)
+            rc = _lib.lib.nmarl_grid_reset_rc(ctypes.byref(params), *args, self.rows, self.cols)
         _lib.check(rc, 'nmarl_grid_reset')
-        return self.obs
 
-    def reset_replica(self, e, seed):
-        """Replica e alone, to the state the one-replica env takes for this seed (`LargeGridEnv.reset`: Philox key = seed, env id
-        0, episode 0): the reset entry point on the replica's contiguous slices, E = 1.  A batch whose replicas are the test
-        seeds of an evaluation starts every one of them where the E = 1 path starts it, whatever its position in the batch."""
-        P, s = _lib.ptr, slice(e, e + 1)
-        p = _lib.GridParams.from_buffer_copy(self.params)
-        if self.head_wait is not None:
-            p.head_wait = self.head_wait[s].data_ptr()
-        self.episode[s].zero_()
-        args = (ctypes.byref(p), 1, None, None, int(seed), 0, P(self.episode[s]), P(self.q[s]), P(self.transit[s]),
-                P(self.prev_action[s]), P(self.t[s]), P(self.xi[s]), P(self.obs[s]), _lib.stream())
+    def _step_call(self, args):
         if self.fixed_shape:
-            rc = _lib.lib.nmarl_grid_reset(*args)
+            rc = _lib.lib.nmarl_grid_step(ctypes.byref(self.params), *args)
         else:
-            rc = _lib.lib.nmarl_grid_reset_rc(*args, self.rows, self.cols)
-        _lib.check(rc, 'nmarl_grid_reset')
+            rc = _lib.lib.nmarl_grid_step_rc(ctypes.byref(self.params), *args, self.rows, self.cols)
+        _lib.check(rc, 'nmarl_grid_step')
 
     _words = None
 
@@ -251,10 +199,9 @@ class LargeGridBatchEnv:
                                   'the 5x5 lattice')
         if self._words is None:          # hand-off words of the launch ([E][2] u64): zeroed once, every launch leaves them zero
             self._words = torch.zeros(_lib.lib.nmarl_lstm_step_grid_words(self.E), dtype=torch.int64, device=self.device)
+        obs, reward, done, greward = self._outputs(obs_out, reward_out, done_out, greward_out)
         return dict(params=self.params, q=self.q, transit=self.transit, prev_action=self.prev_action, t=self.t, xi=self.xi,
-                    obs_out=self.obs if obs_out is None else obs_out, reward=self.reward if reward_out is None else reward_out,
-                    done=self.done if done_out is None else done_out,
-                    global_reward=self.global_reward if greward_out is None else greward_out, auto_reset=bool(auto_reset),
+                    obs_out=obs, reward=reward, done=done, global_reward=greward, auto_reset=bool(auto_reset),
                     seed=self.seed, env_id_base=self.env_id_base, episode=self.episode, words=self._words)
 
     def clear_inkernel_words(self):
@@ -262,81 +209,19 @@ class LargeGridBatchEnv:
         if self._words is not None:
             self._words.zero_()
 
-    def step(self, action, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
-        P = _lib.ptr
-        obs = self.obs if obs_out is None else obs_out
-        reward = self.reward if reward_out is None else reward_out
-        done = self.done if done_out is None else done_out
-        greward = self.global_reward if greward_out is None else greward_out
-        args = (ctypes.byref(self.params), self.E, P(action, torch.uint8), P(self.q), P(self.transit), P(self.prev_action),
-                P(self.t), P(self.xi), P(obs, torch.float32), P(reward, torch.float32), P(done, torch.uint8),
-                P(greward, torch.float32), 1 if auto_reset else 0, self.seed, self.env_id_base, P(self.episode), _lib.stream())
-        if self.fixed_shape:
-            rc = _lib.lib.nmarl_grid_step(*args)
-        else:
-            rc = _lib.lib.nmarl_grid_step_rc(*args, self.rows, self.cols)
-        _lib.check(rc, 'nmarl_grid_step')
-        return obs, reward, done, greward
 
-
-class LargeGridEnv:
+class LargeGridEnv(AtscEnv):
     """Reference duck-type (atsc_env.py:77-524 / large_grid_env.py:48-137) for ONE replica.
     Observation lists: `ma2c*` / `greedy` / `maxpressure` 12 wave features; `ia2c*` own + neighbours' in the reference's `neighbor_map` list
     order (north, east, south, west: atsc_env.py:263-269, `neighbor_order`) (+ the neighbours' fingerprints in the same order
     for ia2c_fp); neighbour actions in mask order (ascending, atsc_env.py:132-136)."""
+    batch_class = LargeGridBatchEnv
 
     def __init__(self, config, port=0, device='cuda', **_):
-        self.batch = LargeGridBatchEnv(config, num_envs=1, device=device)
-        b = self.batch
-        self.rows, self.cols = b.rows, b.cols
-        self.name, self.agent, self.coop_gamma, self.T = b.name, b.agent, b.coop_gamma, b.T
-        self.n_agent, self.n_a, self.n_a_ls, self.n_s_ls = b.n_agent, b.n_a, b.n_a_ls, b.n_s_ls
-        self.neighbor_mask, self.distance_mask = b.neighbor_mask, b.distance_mask
-        self.neighbor_order = b.neighbor_order
+        super().__init__(config, port, device)
+        self.rows, self.cols, self.neighbor_order = self.batch.rows, self.batch.cols, self.batch.neighbor_order
         self.node_names = ['nt%d' % (i + 1) for i in range(self.n_agent)]
-        self.seed = config.getint('seed')
-        self.control_interval_sec = config.getint('control_interval_sec')
-        self.init_test_seeds([int(s) for s in config.get('test_seeds').split(',')])
-        self.cur_episode = 0
-        self.train_mode = True
-        self.is_record = False
-        self.record = None           # the traffic / trip tables of an evaluation (envs/traffic_record.py): init_data(is_record=True)
         self._nbr = [np.where(self.neighbor_mask[i] == 1)[0] for i in range(self.n_agent)]
-
-    def init_data(self, is_record, record_stats, output_path):
-        self.is_record, self.output_path = is_record, output_path
-        if is_record:                                                    # atsc_env.py:142-145
-            from .traffic_record import EpisodeRecord
-            self.control_data, self.traffic_data, self.trip_data = [], [], []
-            self.record = EpisodeRecord(self)
-        else:
-            self.record = None
-
-    def init_test_seeds(self, test_seeds):
-        self.test_num, self.test_seeds = len(test_seeds), test_seeds
-
-    def get_neighbor_action(self, action):
-        action = np.asarray(action)
-        return [action[self.neighbor_mask[i] == 1] for i in range(self.n_agent)]
-
-    def get_fingerprint(self):
-        return self.fp
-
-    def update_fingerprint(self, policy):
-        self.fp = policy
-
-    def terminate(self):
-        return
-
-    def collect_tripinfo(self):
-        """The finished episode's rows of `_traffic.csv` and its row of `_trip.csv` (atsc_env.py:107-124, 464-499)."""
-        if self.record is not None:
-            self.record.collect(self.traffic_data, self.trip_data)
-
-    def output_data(self):
-        if self.is_record:
-            from .traffic_record import write_tables
-            write_tables(self)
 
     def _state_list(self):
         own = self.batch.obs[0, :, :N_FEAT].cpu().numpy().astype(np.float64)      # every node's own wave vector leads its row
@@ -349,33 +234,3 @@ class LargeGridEnv:
                 cur += [np.asarray(self.fp[j]) for j in self.neighbor_order[i]]
             out.append(np.concatenate(cur))
         return out
-
-    def reset(self, gui=False, test_ind=0):
-        seed = self.seed if self.train_mode else self.test_seeds[test_ind]      # atsc_env.py:167-170
-        self.batch.seed = seed
-        self.batch.episode.zero_()
-        self.batch.reset()
-        if self.record is not None:
-            self.record.begin()
-        self.cur_episode += 1
-        self.fp = [np.ones(self.n_a) / self.n_a for _ in range(self.n_agent)]
-        self.seed += 1
-        return self._state_list()
-
-    def step(self, action):
-        a = torch.as_tensor(np.asarray(action, dtype=np.uint8).reshape(1, -1), device=self.batch.device)
-        _, reward, done, g = self.batch.step(a)
-        if self.record is not None:
-            self.record.step()                                         # one launch behind the step, nothing read back here
-        global_reward = float(g.item())
-        done = bool(done.item())
-        if self.agent in RULE_AGENTS or self.coop_gamma < 0:                        # atsc_env.py:205-206
-            reward = global_reward
-        else:
-            reward = reward[0].cpu().numpy().astype(np.float64)
-        if self.is_record:
-            sec = int(self.batch.t.item()) * self.control_interval_sec
-            self.control_data.append({'episode': self.cur_episode, 'time_sec': sec,
-                                      'step': sec / self.control_interval_sec,
-                                      'action': ','.join('%d' % x for x in action), 'reward': global_reward})
-        return self._state_list(), reward, done, global_reward

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
+from .atsc import RuleController, described
 
 N_MAX, A_MAX, F_MAX, T_MAX, G_MAX, P_MAX = 32, 8, 24, 3, 128, 768       # the limits of nmarl_atsc_maxpressure
 
@@ -99,24 +100,10 @@ def net_pressure_table(topo):
     return _pack(n_a, mask, groups, terms, topo.L)
 
 
-def _table_of(env):
-    """The scenario's table for a batch env or a one-replica env (which wraps one)."""
-    from .large_grid_env import LargeGridBatchEnv
-    from .real_net_env import RealNetBatchEnv
-    b = getattr(env, 'batch', env)
-    if isinstance(b, LargeGridBatchEnv):
-        return grid_pressure_table(b.rows, b.cols)
-    if isinstance(b, RealNetBatchEnv):
-        return net_pressure_table(b.topo)
-    raise _lib.NmarlError('the maxpressure agent is defined for the ATSC grid and network envs, not for %s' % type(b).__name__)
-
-
-class MaxPressureController:
+class MaxPressureController(RuleController):
     """The rule on the host for ONE replica, in float64 on the list of the nodes' own wave vectors (Python floats: every sum and
-    product in the order DESIGN.md 6 writes it).  Same `forward(obs) -> actions` duck-type as the greedy controllers; `reset` /
-    `load` exist so that Trainer.perform / main.py evaluate drive it."""
+    product in the order DESIGN.md 6 writes it).  Same `forward(obs) -> actions` duck-type as the greedy controllers."""
     name = 'maxpressure'
-    n_step = 1
 
     def __init__(self, table, node_names=None):
         self.table = t = check_pressure_table(table)
@@ -136,7 +123,8 @@ class MaxPressureController:
 
     @classmethod
     def for_env(cls, env):
-        return cls(_table_of(env), getattr(env, 'node_names', None))
+        """For a batch env or a one-replica env (which wraps one): the scenario's table is the batch env's `pressure_table`."""
+        return cls(described(getattr(env, 'batch', env), 'pressure_table', 'maxpressure agent'), getattr(env, 'node_names', None))
 
     def scores(self, obs):
         """-> per node the list of its phases' scores."""
@@ -164,19 +152,12 @@ class MaxPressureController:
     def forward(self, obs):
         return [int(np.argmax(np.array(s))) for s in self.scores(obs)]          # the first maximum
 
-    def reset(self):
-        return
 
-    def load(self, model_dir, checkpoint=None):
-        return True
-
-
-class MaxPressureBatchController:
+class MaxPressureBatchController(RuleController):
     """`MaxPressureController` for E lock-stepped replicas.  `forward_batch(obs, out)` decides every (replica, node) with one
-    launch of nmarl_atsc_maxpressure on the env's observation buffer as it is -- no staging copy, nothing read back --; `forward`,
-    `reset` and `load` are the host controller's, so the object also drives the one-replica loops."""
+    launch of nmarl_atsc_maxpressure on the env's observation buffer as it is -- no staging copy, nothing read back --; `forward`
+    is the host controller's, so the object also drives the one-replica loops."""
     name = 'maxpressure'
-    n_step = 1
 
     def __init__(self, batch_env):
         self.host = MaxPressureController.for_env(batch_env)
@@ -196,9 +177,3 @@ class MaxPressureBatchController:
 
     def forward(self, obs):
         return self.host.forward(obs)
-
-    def reset(self):
-        return
-
-    def load(self, model_dir, checkpoint=None):
-        return True

@@ -17,6 +17,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .atsc import N_GROUP, OBJECTIVES, RULE_AGENTS, AtscBatchEnv, AtscEnv, RuleController, atsc_params_from_config  # noqa: F401
+from .traffic_record import net_demand, net_mult
 
 # (node, phase-set key, listed neighbours): real_net_env.py:21-49
 NODE_DEFS = (
@@ -63,19 +65,15 @@ PHASE_SETS = {
     '6.1': ('GGgrrGGGrrrGGGgrrrGGGg', 'rrGrrrrrrrrrrrGrrrrrrG', 'GGGrrrrrGGgrrrrGGgrrrr', 'GGGrrrrrrrGrrrrrrGrrrr',
             'rrrGGGrrrrrrrrrrrrGGGG', 'rrrGGGrrrrrGGGgrrrGGGg'),
 }
-N_GROUP = 4
-OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2}
-RULE_AGENTS = ('greedy', 'maxpressure')      # rule-based controllers: own-row observations, the global reward
 
 
-class RealNetController:
+class RealNetController(RuleController):
     """The reference's rule-based `greedy` agent (real_net_env.py:112-145): per node the phase whose green links hold the most
     vehicles.  A link counts for a phase where its signal is the capital 'G' (the reference tests `signal == 'G'`: a permitted
     'g' does not count); the reference adds every incoming lane once per phase, and in the synthetic network every link is its
     own lane, so nothing is de-duplicated.  `ob` is the node's own wave vector, one entry per link.  Same `forward(obs) ->
-    actions` duck-type as LargeGridController; `reset` / `load` exist so that Trainer.perform / main.py evaluate drive it."""
+    actions` duck-type as LargeGridController."""
     name = 'greedy'
-    n_step = 1
 
     def __init__(self, node_names):
         self.node_names = list(node_names)
@@ -87,12 +85,6 @@ class RealNetController:
 
     def forward(self, obs):
         return [self.greedy(ob, node_name) for ob, node_name in zip(obs, self.node_names)]
-
-    def reset(self):
-        return
-
-    def load(self, model_dir, checkpoint=None):
-        return True
 
 
 def net_greedy_table(node_names):
@@ -214,36 +206,14 @@ class NetTopology:
 
 def net_params_from_config(config):
     """ENV_CONFIG section -> nmarl_net_params_t; keys of atsc_env.py:79-99 + real_net_env.py:147."""
-    if config.getint('control_interval_sec') != 5 or config.getint('yellow_interval_sec') != 2:
-        raise _lib.NmarlError('the synthetic network is specified for control 5 s / yellow 2 s')
-    obj = config.get('objective')
-    if obj not in OBJECTIVES:
-        raise ValueError('objective must be one of queue, wait, hybrid (atsc_env.py:87, 411-416), got %r' % obj)
-    p = _lib.NetParams()
-    p.objective = OBJECTIVES[obj]
-    p.coef_wait = config.getfloat('coef_wait', fallback=0.0)
-    p.norm_wave = config.getfloat('norm_wave')
-    p.clip_wave = config.getfloat('clip_wave')
+    p = atsc_params_from_config(config, _lib.NetParams(), 'network', config.get('objective'), ValueError)
     p.flow_rate = config.getfloat('flow_rate')
-    p.T = int(np.ceil(config.getint('episode_length_sec') / config.getint('control_interval_sec')))
-    p.per_agent_reward = 0 if config.getfloat('coop_gamma') < 0 else 1
     return p
 
 
-class RealNetBatchEnv:
-    def __init__(self, config, num_envs=1, device='cuda', env_id_base=0, seed=None):
-        self.config = config
-        self.E = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise _lib.NmarlError('RealNetBatchEnv needs a HIP device; there is no CPU path')
-        self.name = config.get('scenario')
-        self.agent = config.get('agent')
-        self.coop_gamma = config.getfloat('coop_gamma')
-        self.seed = config.getint('seed') if seed is None else int(seed)
-        self.env_id_base = int(env_id_base)
+class RealNetBatchEnv(AtscBatchEnv):
+    def _scenario(self, config):
         self.params = net_params_from_config(config)
-        self.T = self.params.T
         tp = self.topo = NetTopology(self.device)
         self.n_agent, self.n_a, self.n_a_ls = tp.N, tp.A, list(tp.n_a_ls)
         self.n_feat, self.n_feat_ls = tp.L, list(tp.n_s_ls)               # own observation widths (heterogeneous)
@@ -252,124 +222,43 @@ class RealNetBatchEnv:
             self.n_s_ls = list(tp.n_s_ls)
         else:                                                            # own + listed neighbours' (atsc_env.py:263-269)
             self.n_s_ls = [tp.n_s_ls[i] + sum(tp.n_s_ls[j] for j in tp.nbrs[i]) for i in range(tp.N)]
-        self.train_mode = True
-        E, d, N, L = self.E, self.device, tp.N, tp.L
-        f32 = dict(dtype=torch.float32, device=d)
-        self.q = torch.zeros(E, N, L, **f32)
-        self.transit = torch.zeros(E, N, L, **f32)
-        self.prev_action = torch.zeros(E, N, dtype=torch.uint8, device=d)
-        self.t = torch.zeros(E, dtype=torch.int32, device=d)
-        self.xi = torch.ones(E, N_GROUP, **f32)
-        # `wait` / `hybrid` objectives: the front vehicle's standing time per link (csrc/realnet.hip header)
-        self.head_wait = torch.zeros(E, N, L, **f32) if self.params.objective else None
-        if self.head_wait is not None:
-            self.params.head_wait = self.head_wait.data_ptr()
-        self.obs = torch.zeros(E, N, L * (1 + tp.m_max), **f32)
-        self.reward = torch.zeros((E, N) if self.params.per_agent_reward else (E,), **f32)
-        self.done = torch.zeros(E, dtype=torch.uint8, device=d)
-        self.global_reward = torch.zeros(E, **f32)
-        self.episode = torch.zeros(E, dtype=torch.int32, device=d)
-        self.batch_size = None     # episodes end at T only; any n_step dividing T works
+        return tp.L, tp.L * (1 + tp.m_max)
 
-    def state_tensors(self):
-        return [self.q, self.transit, self.prev_action, self.t, self.xi, self.obs, self.episode, self.done] + \
-            ([self.head_wait] if self.head_wait is not None else [])
+    def traffic_model(self):
+        """(mult [N,L] i32, demand [4,12] f64) of the traffic record (envs/traffic_record.py)."""
+        return net_mult(self.topo.n_s_ls, self.topo.L), net_demand(float(self.params.flow_rate))
 
-    def reset(self, mask=None, u0=None):
-        P = _lib.ptr
-        args = (ctypes.byref(self.topo.c), self.E, P(mask, torch.uint8), P(u0, torch.float32), self.seed, self.env_id_base,
-                P(self.episode), P(self.q), P(self.transit), P(self.prev_action), P(self.t), P(self.xi), P(self.obs), _lib.stream())
+    def greedy_rule(self):
+        """(host controller, own observation width, n_a, mask) of the batched greedy agent (envs/greedy.py)."""
+        names = self.topo.node_names
+        return (RealNetController(names), int(self.topo.L)) + net_greedy_table(names)
+
+    def pressure_table(self):
+        from .maxpressure import net_pressure_table
+        return net_pressure_table(self.topo)
+
+    def _reset_call(self, params, args):
+        topo = ctypes.byref(self.topo.c)
         if self.head_wait is None:
-            _lib.check(_lib.lib.nmarl_net_reset(*args), 'nmarl_net_reset')
+            _lib.check(_lib.lib.nmarl_net_reset(topo, *args), 'nmarl_net_reset')
         else:                                                            # the same reset, which also clears head_wait
-            _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(self.params), *args), 'nmarl_net_reset_obj')
-        return self.obs
+            _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(params), topo, *args), 'nmarl_net_reset_obj')
 
-    def reset_replica(self, e, seed):
-        """Replica e alone, to the state the one-replica env takes for this seed (`RealNetEnv.reset`: Philox key = seed, env id 0,
-        episode 0): the reset entry point on the replica's contiguous slices, E = 1."""
-        P, s = _lib.ptr, slice(e, e + 1)
-        self.episode[s].zero_()
-        args = (ctypes.byref(self.topo.c), 1, None, None, int(seed), 0, P(self.episode[s]), P(self.q[s]), P(self.transit[s]),
-                P(self.prev_action[s]), P(self.t[s]), P(self.xi[s]), P(self.obs[s]), _lib.stream())
-        if self.head_wait is None:
-            _lib.check(_lib.lib.nmarl_net_reset(*args), 'nmarl_net_reset')
-        else:
-            p = _lib.NetParams.from_buffer_copy(self.params)
-            p.head_wait = self.head_wait[s].data_ptr()
-            _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(p), *args), 'nmarl_net_reset_obj')
-
-    def step(self, action, auto_reset=False, obs_out=None, reward_out=None, done_out=None, greward_out=None):
-        P = _lib.ptr
-        obs = self.obs if obs_out is None else obs_out
-        reward = self.reward if reward_out is None else reward_out
-        done = self.done if done_out is None else done_out
-        greward = self.global_reward if greward_out is None else greward_out
-        rc = _lib.lib.nmarl_net_step(ctypes.byref(self.params), ctypes.byref(self.topo.c), self.E, P(action, torch.uint8),
-                                     P(self.q), P(self.transit), P(self.prev_action), P(self.t), P(self.xi),
-                                     P(obs, torch.float32), P(reward, torch.float32), P(done, torch.uint8),
-                                     P(greward, torch.float32), 1 if auto_reset else 0, self.seed, self.env_id_base,
-                                     P(self.episode), _lib.stream())
-        _lib.check(rc, 'nmarl_net_step')
-        return obs, reward, done, greward
+    def _step_call(self, args):
+        _lib.check(_lib.lib.nmarl_net_step(ctypes.byref(self.params), ctypes.byref(self.topo.c), *args), 'nmarl_net_step')
 
 
-class RealNetEnv:
+class RealNetEnv(AtscEnv):
     """Reference duck-type (atsc_env.py:77-524 / real_net_env.py:145-198) for ONE replica: ragged observation lists
     (`ma2c*` / `greedy` / `maxpressure`: the node's own links; `ia2c*`: own + listed neighbours' in ascending node index, + their fingerprints
     for ia2c_fp), ragged fingerprints, per-agent rewards."""
+    batch_class = RealNetBatchEnv
 
     def __init__(self, config, port=0, device='cuda', **_):
-        self.batch = RealNetBatchEnv(config, num_envs=1, device=device)
-        b = self.batch
-        self.name, self.agent, self.coop_gamma, self.T = b.name, b.agent, b.coop_gamma, b.T
-        self.n_agent, self.n_a, self.n_a_ls, self.n_s_ls = b.n_agent, b.n_a, b.n_a_ls, b.n_s_ls
-        self.n_feat_ls = b.n_feat_ls
-        self.node_names = b.topo.node_names
-        self.neighbor_mask, self.distance_mask = b.neighbor_mask, b.distance_mask
-        self.seed = config.getint('seed')
-        self.control_interval_sec = config.getint('control_interval_sec')
-        self.init_test_seeds([int(s) for s in config.get('test_seeds').split(',')])
-        self.cur_episode = 0
-        self.train_mode = True
-        self.is_record = False
-        self.record = None           # the traffic / trip tables of an evaluation (envs/traffic_record.py): init_data(is_record=True)
-        self._nbr = b.topo.nbrs
-
-    def init_data(self, is_record, record_stats, output_path):
-        self.is_record, self.output_path = is_record, output_path
-        if is_record:                                                    # atsc_env.py:142-145
-            from .traffic_record import EpisodeRecord
-            self.control_data, self.traffic_data, self.trip_data = [], [], []
-            self.record = EpisodeRecord(self)
-        else:
-            self.record = None
-
-    def init_test_seeds(self, test_seeds):
-        self.test_num, self.test_seeds = len(test_seeds), test_seeds
-
-    def get_neighbor_action(self, action):
-        action = np.asarray(action)
-        return [action[self.neighbor_mask[i] == 1] for i in range(self.n_agent)]
-
-    def get_fingerprint(self):
-        return self.fp
-
-    def update_fingerprint(self, policy):
-        self.fp = policy
-
-    def terminate(self):
-        return
-
-    def collect_tripinfo(self):
-        """The finished episode's rows of `_traffic.csv` and its row of `_trip.csv` (atsc_env.py:107-124, 464-499)."""
-        if self.record is not None:
-            self.record.collect(self.traffic_data, self.trip_data)
-
-    def output_data(self):
-        if self.is_record:
-            from .traffic_record import write_tables
-            write_tables(self)
+        super().__init__(config, port, device)
+        self.n_feat_ls = self.batch.n_feat_ls
+        self.node_names = self.batch.topo.node_names
+        self._nbr = self.batch.topo.nbrs
 
     def _state_list(self):
         L = self.batch.n_feat
@@ -383,33 +272,3 @@ class RealNetEnv:
                 cur += [np.asarray(self.fp[j]) for j in self._nbr[i]]
             out.append(np.concatenate(cur))
         return out
-
-    def reset(self, gui=False, test_ind=0):
-        seed = self.seed if self.train_mode else self.test_seeds[test_ind]      # atsc_env.py:167-170
-        self.batch.seed = seed
-        self.batch.episode.zero_()
-        self.batch.reset()
-        if self.record is not None:
-            self.record.begin()
-        self.cur_episode += 1
-        self.fp = [np.ones(a) / a for a in self.n_a_ls]                  # atsc_env.py:498-499
-        self.seed += 1
-        return self._state_list()
-
-    def step(self, action):
-        a = torch.as_tensor(np.asarray(action, dtype=np.uint8).reshape(1, -1), device=self.batch.device)
-        _, reward, done, g = self.batch.step(a)
-        if self.record is not None:
-            self.record.step()                                         # one launch behind the step, nothing read back here
-        global_reward = float(g.item())
-        done = bool(done.item())
-        if self.agent in RULE_AGENTS or (self.coop_gamma < 0 and self.train_mode):  # atsc_env.py:205-206
-            reward = global_reward
-        else:
-            reward = reward[0].cpu().numpy().astype(np.float64) if self.coop_gamma >= 0 else global_reward
-        if self.is_record:
-            sec = int(self.batch.t.item()) * self.control_interval_sec
-            self.control_data.append({'episode': self.cur_episode, 'time_sec': sec,
-                                      'step': sec / self.control_interval_sec,
-                                      'action': ','.join('%d' % x for x in action), 'reward': global_reward})
-        return self._state_list(), reward, done, global_reward

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .atsc import described
 
 TRAFFIC_COLUMNS = ('number_total_car', 'number_departed_car', 'number_arrived_car', 'avg_wait_sec', 'avg_speed_mps', 'std_queue',
                    'avg_queue', 'time_sec')                       # the 8 floats of a row, in the kernel's order
@@ -56,21 +57,11 @@ def net_demand(flow_rate):
 
 
 class TrafficRecorder:
-    """Recorder state + the record rec[max_steps][E][8] of a LargeGridBatchEnv or RealNetBatchEnv, all on the env's device."""
+    """Recorder state + the record rec[max_steps][E][8] of an ATSC batch env (envs/atsc.py AtscBatchEnv, which says what its lanes
+    or links count for and what its demand is: `traffic_model`), all on the env's device."""
 
     def __init__(self, batch_env, max_steps):
-        from .large_grid_env import LargeGridBatchEnv
-        from .real_net_env import RealNetBatchEnv
-        if isinstance(batch_env, LargeGridBatchEnv):
-            mult = grid_mult(batch_env.n_agent)
-            n_entry = [sum(1 for e in batch_env.entries if e[2] == g) for g in range(N_GROUP)]
-            demand = grid_demand(float(batch_env.params.peak1), float(batch_env.params.peak2), n_entry)
-        elif isinstance(batch_env, RealNetBatchEnv):
-            mult = net_mult(batch_env.topo.n_s_ls, batch_env.topo.L)
-            demand = net_demand(float(batch_env.params.flow_rate))
-        else:
-            raise _lib.NmarlError('the traffic record is defined for the ATSC grid and network envs, not for %s'
-                                  % type(batch_env).__name__)
+        mult, demand = described(batch_env, 'traffic_model', 'traffic record')
         dev = torch.device(batch_env.device)
         if dev.type != 'cuda':
             raise _lib.NmarlError('TrafficRecorder needs a HIP device; there is no CPU path')
@@ -139,7 +130,7 @@ def trip_row(trip, e, episode):
 
 
 class EpisodeRecord:
-    """What LargeGridEnv / RealNetEnv (one replica) share: the recorder next to `control_data`, and the two tables."""
+    """The one-replica env's (envs/atsc.py AtscEnv) recorder next to `control_data`, and the two tables."""
 
     def __init__(self, env):
         self.env = env

@@ -9,10 +9,9 @@ import torch
 
 from .agents.models import IA2C, IA2C_CU, IA2C_FP, MA2C_DIAL, MA2C_IC3, MA2C_NC
 from .envs import init_env, make_batch_env
+from .envs.atsc import RULE_AGENTS
 from .envs.greedy import GreedyBatchController
-from .envs.large_grid_env import LargeGridController
-from .envs.maxpressure import MaxPressureBatchController, MaxPressureController
-from .envs.real_net_env import RealNetController
+from .envs.maxpressure import MaxPressureBatchController
 from .utils import (BatchedEvaluator, BatchedTrainer, Counter, Evaluator, SummaryWriter, Trainer, check_dir, copy_file, find_file,
                     init_dir, init_log)
 
@@ -49,12 +48,9 @@ def parse_args(argv=None):
 
 
 def init_agent(env, config, total_step, seed, **kw):
-    if env.agent == 'greedy':                  # rule-based baseline of the ATSC scenarios (large_grid_env.py:30-45, real_net_env.py:112-145)
-        if env.name.endswith('large_grid'):
-            return LargeGridController(getattr(env, 'node_names', None))
-        return RealNetController(env.node_names) if env.name.endswith('real_net') else None
-    if env.agent == 'maxpressure':             # the max-pressure baseline of the same scenarios (envs/maxpressure.py)
-        return MaxPressureController.for_env(env) if env.name.endswith(('large_grid', 'real_net')) else None
+    if env.agent in RULE_AGENTS:               # the rule-based baselines: the ATSC envs know theirs (envs/atsc.py), no other env has one
+        host_controller = getattr(env, 'host_controller', None)
+        return host_controller() if host_controller is not None else None
     cls = AGENTS.get(env.agent)
     if cls is None:
         return None
@@ -91,7 +87,7 @@ def train(args):
     elif args.lstm_precision is not None:
         config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
     env_cfg = config['ENV_CONFIG']
-    if env_cfg.get('agent') in ('greedy', 'maxpressure'):
+    if env_cfg.get('agent') in RULE_AGENTS:
         # the rule-based ATSC baselines have nothing to train (no add_transition / backward / save): say so instead of dying on an
         # AttributeError after the first env step with a half-initialised run directory -- `main.py evaluate` is their mode
         # (asked before TRAIN_CONFIG is read: their inis have neither that section nor MODEL_CONFIG)

@@ -906,7 +906,7 @@ def eval_row_counts(D):
 
 def eval_control_rows(acts, G, rows, atsc, dt):
     """The rows of `_control.csv` from the per-step buffers acts [T,E,N], G [T,E], in the one-replica writers' form
-    (LargeGridEnv / RealNetEnv / CACCEnv.step): episode e + 1; after lock-step k the env's clock stands at k + 1 steps -- ATSC:
+    (envs/atsc.py AtscEnv.step / CACCEnv.step): episode e + 1; after lock-step k the env's clock stands at k + 1 steps -- ATSC:
     time_sec = 5 (k + 1) as int, step = time_sec / 5; CACC: time_sec = (k + 1) dt, step = k + 1."""
     out = []
     for e, n in enumerate(rows):
