@@ -709,6 +709,28 @@ def bptt_coupled(kind, rev, m_max, G, Call, done, dHs, ws, wm, mask, dZ, D1, mod
     return dZ.sum(dim=(1, 2)), D1.sum(dim=(1, 2))
 
 
+def bptt_dial(rev, m_max, G, Call, done, dHs, ws, wm, img_f, hm, msg, dZ, DS, D1, D2, mode=0, head_dy=None, want_state_grad=False):
+    """Restatement of nmarl_lstm_bptt_dial, per reverse step: bptt_step (cell backward, [ds | dh] = dz [wx; wh]^T, dh * keep), then
+    dial_msg_adjoint (both relu masks, gather adjoint, dh + d2 mfc_w^T) -- the loop of agents/sequence.py.  ws = (wx, wh, .),
+    wm = (w_msg, .), img_f = mfc_w (lstm_bptt_msg_wimage hands the weight through).  -> (db, dbmsg, dbmfc, dh0, dc0 or None)."""
+    N, T, E, H4 = G.shape
+    H = H4 // 4
+    if head_dy is not None:
+        dy8, hw = head_dy
+        dHs = torch.bmm(dy8[:, :, :hw.shape[2]].to(hw.dtype), hw.transpose(1, 2)).view(N, T, E, -1)
+    z = lambda: torch.zeros(N, E, H, dtype=G.dtype)                                     # noqa: E731
+    dc, dc_next, dh_rec = z(), z(), None
+    for t in range(T - 1, -1, -1):
+        dhd = z()
+        bptt_step(G[:, t], Call[:, t], Call[:, t + 1], done[t], dHs[:, t], dh_rec, dc, (ws[0], ws[1], None), dZ[:, t], dc_next, dhd, True,
+                  dx=DS[:, t])
+        dc, dc_next = dc_next, dc
+        dh_rec = z()
+        dial_msg_adjoint(DS[:, t], hm[:, t], msg[:, t], dhd, wm[0], img_f, rev['nbr_idx'], None, None, D1[:, t], D2[:, t], dh_rec)
+    dh0, dc0 = (dh_rec, dc) if want_state_grad else (None, None)
+    return dZ.sum(dim=(1, 2)), D1[:, :T].sum(dim=(1, 2)), D2[:, :T].sum(dim=(1, 2)), dh0, dc0
+
+
 def batch_epilogue(g, done, ep_sum, ep_sq, ep_len, fin, T_env, h_fw, c_fw, h_bw, c_bw, fp_T, fp_0, fp_uniform, x_T, x_0, done_pre,
                    skip_if=None):
     """Restatement of nmarl_batch_epilogue (csrc/a2c.hip): the elementwise host code the batched loop used to run."""

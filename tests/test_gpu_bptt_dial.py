@@ -63,24 +63,18 @@ def _inputs(N, T, E, topo, seed, O=None):
 
 def _reference(d):
     """float64, per reverse step: ops_ref.bptt_step (cell backward, [ds | dh] = dz [wx; wh]^T, dh * keep) then
-    ops_ref.dial_msg_adjoint (both relu masks, gather adjoint, dh + d2 mfc_w^T) -- the loop of agents/sequence.py."""
+    ops_ref.dial_msg_adjoint (both relu masks, gather adjoint, dh + d2 mfc_w^T) -- the loop of agents/sequence.py, composed in
+    oracle/ops_ref.py as bptt_dial."""
     from oracle import ops_ref
     f = lambda t: t.double()                                                            # noqa: E731
-    G, C, done, dhs = f(d['gates']), f(d['call']), f(d['done']), f(d['dhs'])
-    N, T, E, _ = G.shape
-    ws = (f(d['wx']), f(d['wh']), None)
+    N, T, E, _ = d['gates'].shape
     dZ = torch.zeros(N, T, E, 4 * H, dtype=torch.float64)
     DS, D1, D2 = (torch.zeros(N, T, E, H, dtype=torch.float64) for _ in range(3))
-    dc, dc_next = torch.zeros(N, E, H, dtype=torch.float64), torch.zeros(N, E, H, dtype=torch.float64)
-    dh_rec = None
-    for t in range(T - 1, -1, -1):
-        dhd = torch.zeros(N, E, H, dtype=torch.float64)
-        ops_ref.bptt_step(G[:, t], C[:, t], C[:, t + 1], done[t], dhs[:, t], dh_rec, dc, ws, dZ[:, t], dc_next, dhd, True, dx=DS[:, t])
-        dc, dc_next = dc_next, dc
-        dh_rec = torch.zeros(N, E, H, dtype=torch.float64)
-        ops_ref.dial_msg_adjoint(DS[:, t], f(d['hm'][:, t]), f(d['msg'][:, t]), dhd, f(d['w_msg']), f(d['mfc_w']), d['idx'], None, None,
-                                 D1[:, t], D2[:, t], dh_rec)
-    return dict(dZ=dZ, DS=DS, D1=D1, D2=D2, db=dZ.sum(dim=(1, 2)), dbm=D1.sum(dim=(1, 2)), dbf=D2.sum(dim=(1, 2)), dh0=dh_rec, dc0=dc)
+    db, dbm, dbf, dh0, dc0 = ops_ref.bptt_dial(ops_ref.reverse_neighbor_table(d['idx'], ops_ref.COUPLED_NC), d['m_max'], f(d['gates']),
+                                               f(d['call']), f(d['done']), f(d['dhs']), (f(d['wx']), f(d['wh']), None),
+                                               (f(d['w_msg']), None), f(d['mfc_w']), f(d['hm']), f(d['msg']), dZ, DS, D1, D2,
+                                               want_state_grad=True)
+    return dict(dZ=dZ, DS=DS, D1=D1, D2=D2, db=db, dbm=dbm, dbf=dbf, dh0=dh0, dc0=dc0)
 
 
 def _run(d, mode, head_dy=False):
