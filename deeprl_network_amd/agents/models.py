@@ -14,7 +14,7 @@ Engine (per n_step batch, E replicas, N agents):
             from the state `forward('p')` just wrote);
   buffers   [T,...] device tensors replacing OnPolicyBuffer's Python lists
             (agents/utils.py:722-761, 819-835);
-  update    nmarl_nstep_return -> autograd unroll -> A2C loss (policies.py:20-30,
+  update    nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) -> autograd unroll -> A2C loss (policies.py:20-30,
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
             nmarl_rmsprop_tf_clip (policies.py:32-39).
 """
@@ -72,6 +72,11 @@ class IA2C:
         # optional (absent: 'fp32', so every reference ini runs unchanged): the rollout's LSTM product arithmetic, see
         # BatchedPolicy -- 'bf16x3' is opt-in and exists for the x-side uncoupled nets only
         self.lstm_precision = ops.check_precision(model_config.get('lstm_precision', fallback='fp32').strip(), 'lstm_precision')
+        # optional (absent: 1.0 = the reference's plain n-step advantage, ops.nstep_return): lambda of GAE -- any other value in
+        # [0, 1] sends the update's return scan through ops.gae_return (R becomes the lambda-return)
+        self.gae_lambda = model_config.getfloat('gae_lambda', fallback=1.0)
+        if not 0.0 <= self.gae_lambda <= 1.0:                # (nan fails both comparisons)
+            raise ValueError('gae_lambda = %r: must lie in [0, 1]' % self.gae_lambda)
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -552,8 +557,12 @@ class IA2C:
                 ops.nbr_action_value(self.buf_act.view(T * self.E, self.n_agent), self.policy.nbr_idx,
                                      self.policy.params['v_w'][:, self.n_lstm:], self.n_a, out=vn, accumulate=True)
                 self.buf_v.copy_(self.buf_vn.permute(1, 0, 2))
-        ops.nstep_return(self.buf_r, self.buf_v, self.buf_done_post, R_end.contiguous(), self.gamma, alpha,
-                         self.dist_dev, self.R, self.Adv)
+        if self.gae_lambda == 1.0:
+            ops.nstep_return(self.buf_r, self.buf_v, self.buf_done_post, R_end.contiguous(), self.gamma, alpha,
+                             self.dist_dev, self.R, self.Adv)
+        else:           # opt-in GAE(lambda): Adv = the lambda-weighted TD errors, R = Adv + v (the critic's target)
+            ops.gae_return(self.buf_r, self.buf_v, self.buf_done_post, R_end.contiguous(), self.gamma, self.gae_lambda, alpha,
+                           self.dist_dev, self.R, self.Adv)
         ps = self.policy.params
         ps.begin_backward()
         FP = self.buf_fp[:T].permute(1, 0, 2, 3).reshape(self.n_agent, T * self.E, self.n_a)

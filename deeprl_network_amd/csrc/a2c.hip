@@ -237,6 +237,96 @@ __global__ __launch_bounds__(256) void nstep_kernel(
     }
 }
 
+// GAE(lambda) advantage and lambda-return (opt-in, MODEL_CONFIG gae_lambda; the reference has no lambda).  Layouts of nstep_kernel.
+//   rho[t] = r[t,e] (alpha < 0)  |  sum_j alpha^dist(n,j) r[t,e,j] (alpha >= 0, j ascending);  next = R_end, A = 0;  t = T-1 .. 0:
+//   delta = rho[t] + (gamma next) keep - v[t];  A = delta + ((gamma lambda) A) keep;  Adv = A;  R = A + v[t];  next = v[t]
+// Only A is a dependent chain: ten steps' done / r / v are requested together as in nstep_kernel, v[t] is loaded once and serves as
+// the subtrahend at t and, from its register, as `next` at t - 1 (the bytes nstep_kernel moves).  Spatial path: the ten steps'
+// weighted sums run side by side (ten independent loads and accumulators per j, each sum over j ascending).  One instantiation
+// per path: a run-time `spatial` inside the unrolled loads made the compiler wait for each of them on its own.
+template <bool SPATIAL>
+__global__ __launch_bounds__(256) void gae_kernel(
+    const int64_t E, const int N, const int T, const float* __restrict__ r, const float* __restrict__ v,
+    const uint8_t* __restrict__ done_post, const float* __restrict__ R_end, const double gamma, const double lambda,
+    const double alpha, const int32_t* __restrict__ dist, float* __restrict__ R_out, float* __restrict__ adv_out) {
+    __shared__ double s_w[SPATIAL ? 64 * 64 : 1];  // alpha^dist(i,j), N <= 64
+    if (SPATIAL) {
+        for (int p = threadIdx.x; p < N * N; p += blockDim.x) s_w[p] = dist[p] < 0 ? 0.0 : pow(alpha, (double)dist[p]);
+        __syncthreads();
+    }
+    const double gl = gamma * lambda;
+    const int64_t total = (int64_t)N * E;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int n = (int)(idx / E);
+        const int64_t e = idx - (int64_t)n * E;
+        double next = (double)R_end[idx], A = 0.0;
+        constexpr int U = 10;
+        for (int t0 = T - 1; t0 >= 0; t0 -= U) {
+            float vv[U], rr[U];
+            uint8_t dd[U];
+            double rho[U];
+#pragma unroll
+            for (int k = 0; k < U; ++k) {
+                const int t = t0 - k >= 0 ? t0 - k : 0;                  // (clamped: unconditional loads)
+                dd[k] = done_post[(int64_t)t * E + e];
+                vv[k] = v[((int64_t)t * N + n) * E + e];
+                if (!SPATIAL) rr[k] = r[(int64_t)t * E + e];
+            }
+            if (SPATIAL) {
+                const float* rk[U];
+#pragma unroll
+                for (int k = 0; k < U; ++k) {
+                    rk[k] = r + ((int64_t)(t0 - k >= 0 ? t0 - k : 0) * E + e) * N;
+                    rho[k] = 0.0;
+                }
+                const double* w = s_w + n * N;
+                // four neighbouring j per step at a time: a replica's row of N rewards is contiguous, so the four loads share a cache
+                // line, where ten steps' single loads per j brought ten lines per thread back for every j (more than the L1 holds).
+                // Each step's sum still runs over j ascending
+                constexpr int JB = 4;
+                int j = 0;
+                for (; j + JB <= N; j += JB) {
+                    float x[U][JB];
+#pragma unroll
+                    for (int k = 0; k < U; ++k)
+#pragma unroll
+                        for (int b = 0; b < JB; ++b) x[k][b] = rk[k][j + b];
+#pragma unroll
+                    for (int b = 0; b < JB; ++b) {
+                        const double wj = w[j + b];
+#pragma unroll
+                        for (int k = 0; k < U; ++k) rho[k] += wj * (double)x[k][b];
+                    }
+                }
+                for (; j < N; ++j) {                                     // the last N % 4: ten loads in flight per j
+                    const double wj = w[j];
+#pragma unroll
+                    for (int k = 0; k < U; ++k) rr[k] = rk[k][j];
+#pragma unroll
+                    for (int k = 0; k < U; ++k) rho[k] += wj * (double)rr[k];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < U; ++k) rho[k] = (double)rr[k];
+            }
+            // straight-line over the ten steps; behind t = 0 (last chunk only) the clamped operands are scanned and not stored
+#pragma unroll
+            for (int k = 0; k < U; ++k) {
+                const int t = t0 - k;
+                const double keep = 1.0 - (double)dd[k], vt = (double)vv[k];
+                const double delta = rho[k] + (gamma * next) * keep - vt;
+                A = delta + (gl * A) * keep;
+                if (t >= 0) {
+                    const int64_t o = ((int64_t)n * T + t) * E + e;
+                    adv_out[o] = (float)A;
+                    R_out[o] = (float)(A + vt);
+                }
+                next = vt;
+            }
+        }
+    }
+}
+
 // ---- clip_by_global_norm + RMSProp over flat [G, P] (G groups = optimisers) ----
 // ---------------------------------------------------------------------------------------------------------------------
 // What the batched loop does between two n_step batches, in two launches instead of ~45 elementwise ones:
@@ -561,6 +651,23 @@ extern "C" int nmarl_nstep_return(int64_t E, int32_t N, int32_t T, const float* 
     if (E == 0) return NMARL_OK;
     hipLaunchKernelGGL(nstep_kernel, dim3(grid_x((int64_t)N * E)), dim3(256), 0, static_cast<hipStream_t>(stream), E, N,
                        T, r, v, done_post, R_end, gamma, alpha, dist, R_out, adv_out);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_gae_return(int64_t E, int32_t N, int32_t T, const float* r, const float* v, const uint8_t* done_post,
+                                const float* R_end, double gamma, double lambda, double alpha, const int32_t* dist,
+                                float* R_out, float* adv_out, void* stream) {
+    if (E < 0 || N <= 0 || N > 64 || T <= 0 || (E > 0 && (!r || !v || !done_post || !R_end || !R_out || !adv_out)))
+        return NMARL_EINVAL;
+    if (alpha >= 0.0 && !dist) return NMARL_EINVAL;
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return NMARL_EINVAL;          // (NaN included)
+    if (E == 0) return NMARL_OK;
+    if (alpha >= 0.0)
+        hipLaunchKernelGGL(gae_kernel<true>, dim3(grid_x((int64_t)N * E)), dim3(256), 0, static_cast<hipStream_t>(stream), E,
+                           N, T, r, v, done_post, R_end, gamma, lambda, alpha, dist, R_out, adv_out);
+    else
+        hipLaunchKernelGGL(gae_kernel<false>, dim3(grid_x((int64_t)N * E)), dim3(256), 0, static_cast<hipStream_t>(stream), E,
+                           N, T, r, v, done_post, R_end, gamma, lambda, alpha, dist, R_out, adv_out);
     return nmarl_check_launch();
 }
 

@@ -33,6 +33,9 @@ def parse_args(argv=None):
     sp.add_argument('--lstm-precision', choices=('fp32', 'bf16x3'), default=None,
                     help='arithmetic of the rollout\'s LSTM products (overrides MODEL_CONFIG lstm_precision; default fp32). '
                          'bf16x3: opt-in split-bf16 form, IA2C / IA2C-FP / ConseNet only; the update stays fp32')
+    sp.add_argument('--gae-lambda', type=float, default=None,
+                    help='lambda of generalised advantage estimation in [0, 1] (overrides MODEL_CONFIG gae_lambda; default 1 = the '
+                         'reference\'s n-step advantage).  Below 1 the critic\'s target is the lambda-return')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -71,6 +74,20 @@ def _dist():
     return world, rank, local, group
 
 
+def apply_overrides(config, args, run_ini=None):
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda), set on every rank; run_ini (rank 0): the
+    run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
+    given = {'lstm_precision': args.lstm_precision,
+             'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda)}
+    given = {k: v for k, v in given.items() if v is not None}
+    for k, v in given.items():
+        config.set('MODEL_CONFIG', k, v)
+    if given and run_ini is not None:
+        with open(run_ini, 'w') as f:
+            config.write(f)
+    return bool(given)
+
+
 def train(args):
     world, rank, local, group = _dist()
     dirs = init_dir(args.base_dir)
@@ -79,13 +96,7 @@ def train(args):
     config.read(args.config_dir)
     if rank == 0:
         copy_file(args.config_dir, dirs['data'])
-        if args.lstm_precision is not None:
-            # the override goes into the run's copy of the ini: `evaluate` rebuilds the policy from that file
-            config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
-            with open(os.path.join(dirs['data'], os.path.basename(args.config_dir)), 'w') as f:
-                config.write(f)
-    elif args.lstm_precision is not None:
-        config.set('MODEL_CONFIG', 'lstm_precision', args.lstm_precision)
+    apply_overrides(config, args, os.path.join(dirs['data'], os.path.basename(args.config_dir)) if rank == 0 else None)
     env_cfg = config['ENV_CONFIG']
     if env_cfg.get('agent') in RULE_AGENTS:
         # the rule-based ATSC baselines have nothing to train (no add_transition / backward / save): say so instead of dying on an

@@ -1829,6 +1829,19 @@ def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, ad
     return R_out, adv_out
 
 
+def gae_return(r, v, done_post, R_end, gamma, lam, alpha, dist=None, R_out=None, adv_out=None):
+    """GAE(lam) on the layouts of nstep_return -> lambda-return R, advantage Adv [N,T,E] (lam = 1: the n-step return)."""
+    T, N, E = v.shape
+    if R_out is None:
+        R_out = torch.empty(N, T, E, dtype=F32, device=v.device)
+    if adv_out is None:
+        adv_out = torch.empty(N, T, E, dtype=F32, device=v.device)
+    check(lib.nmarl_gae_return(E, N, T, ptr(r, F32), ptr(v, F32), ptr(done_post, torch.uint8), ptr(R_end, F32),
+                               float(gamma), float(lam), float(alpha), ptr(dist, torch.int32), ptr(R_out), ptr(adv_out),
+                               stream()), 'nmarl_gae_return')
+    return R_out, adv_out
+
+
 def rmsprop_tf_clip(w, g, ms, scratch, lr, rho, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False):
     """In-place clip_by_global_norm + TF RMSProp on flat [G,P] buffers.  guard: the caller's model launches in-launch
     hand-off kernels -- the step then consults the device's hand-off status word and changes nothing while it is set (a

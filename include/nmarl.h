@@ -959,6 +959,17 @@ int nmarl_nstep_return(int64_t E, int32_t N, int32_t T, const float* r, const fl
                        const uint8_t* done_post, const float* R_end, double gamma, double alpha,
                        const int32_t* dist, float* R_out, float* adv_out, void* stream);
 /*
+ * GAE(lambda) advantage and lambda-return (opt-in: MODEL_CONFIG gae_lambda; the reference has no lambda).  Layouts and
+ * return codes of nmarl_nstep_return; lambda in [0,1] (outside or NaN: NMARL_EINVAL).  Per (n, e), float64 scan:
+ *   rho[t] = r[t,e]  |  sum_j alpha^dist(n,j) r[t,e,j] (dist < 0: weight 0);  next = R_end[n,e];  A = 0;  t = T-1 .. 0:
+ *   delta = rho[t] + gamma next (1-d[t,e]) - v[t,n,e];  A = delta + gamma lambda A (1-d[t,e]);
+ *   Adv[n,t,e] = A;  R[n,t,e] = A + v[t,n,e];  next = v[t,n,e]
+ * lambda = 1: the n-step return; lambda = 0: the one-step TD error.
+ */
+int nmarl_gae_return(int64_t E, int32_t N, int32_t T, const float* r, const float* v, const uint8_t* done_post,
+                     const float* R_end, double gamma, double lambda, double alpha, const int32_t* dist,
+                     float* R_out, float* adv_out, void* stream);
+/*
  * tf.clip_by_global_norm + tf.train.RMSPropOptimizer.apply_gradients
  * (policies.py:32-39, 257-264; TF-1.12 ApplyRMSProp, ms0 = 1, momentum 0) on a
  * flat [G,P] parameter buffer; G = number of independent optimisers (IA2C: one
