@@ -16,7 +16,7 @@ Engine (per n_step batch, E replicas, N agents):
             (agents/utils.py:722-761, 819-835);
   update    nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) -> autograd unroll -> A2C loss (policies.py:20-30,
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
-            nmarl_rmsprop_tf_clip (policies.py:32-39).
+            nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip).
 """
 import logging
 import os
@@ -77,6 +77,19 @@ class IA2C:
         self.gae_lambda = model_config.getfloat('gae_lambda', fallback=1.0)
         if not 0.0 <= self.gae_lambda <= 1.0:                # (nan fails both comparisons)
             raise ValueError('gae_lambda = %r: must lie in [0, 1]' % self.gae_lambda)
+        # optional (absent: 'rmsprop' = the reference's clip + TF-1.12 RMSProp, ops.rmsprop_tf_clip): 'adam' sends the optimiser
+        # step through ops.adam_clip (the same clip, then bias-corrected Adam); rmsp_alpha / rmsp_epsilon are unused then
+        self.optimizer = model_config.get('optimizer', fallback='rmsprop').strip().lower()
+        if self.optimizer not in ('rmsprop', 'adam'):
+            raise ValueError('optimizer = %r: must be rmsprop or adam' % self.optimizer)
+        self.adam_beta1 = model_config.getfloat('adam_beta1', fallback=0.9)
+        self.adam_beta2 = model_config.getfloat('adam_beta2', fallback=0.999)
+        self.adam_epsilon = model_config.getfloat('adam_epsilon', fallback=1e-8)
+        for key in ('adam_beta1', 'adam_beta2'):
+            if not 0.0 <= getattr(self, key) < 1.0:          # (nan fails both comparisons)
+                raise ValueError('%s = %r: must lie in [0, 1)' % (key, getattr(self, key)))
+        if not self.adam_epsilon > 0.0:
+            raise ValueError('adam_epsilon = %r: must be positive' % self.adam_epsilon)
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -94,6 +107,8 @@ class IA2C:
                                       n_h=self.n_lstm, device=self.device, n_feat_ls=self.n_feat_ls,
                                       n_a_ls=None if self.identical_agent else self.n_a_ls,
                                       obs_order=None if self._is_ma2c() else obs_order, precision=self.lstm_precision)
+        if self.optimizer == 'adam':
+            self.policy.params.enable_adam()
         self.policy.params.init_reference_order()       # consumes np.random like the reference's ortho_init
         self.n_s = self.n_s_ls[0]
         N, E, H, T = self.n_agent, self.E, self.n_lstm, self.n_step
@@ -541,7 +556,7 @@ class IA2C:
     @property
     def handoff_guarded(self):
         """This model launches in-launch hand-off kernels (one-launch coupled lock-step / BPTT): its optimiser step consults
-        the device's hand-off status word and refuses a batch a timed-out wave contributed to (ops.rmsprop_tf_clip)."""
+        the device's hand-off status word and refuses a batch a timed-out wave contributed to (ops.rmsprop_tf_clip, ops.adam_clip)."""
         return bool(self.policy.coupled) and self.device.type == 'cuda'
 
     def update_grads(self, R_end):
@@ -600,15 +615,20 @@ class IA2C:
         self.allreduce_calls = getattr(self, 'allreduce_calls', 0) + 1
 
     def update_apply(self, lr, rotate=True, lr_dev=None):
-        """clip_by_global_norm + RMSProp on the flat buffers (policies.py:32-39, 257-264); lr_dev: device scalar that
-        overrides `lr` (captured updates: the host refreshes it when the schedule moves)."""
+        """clip_by_global_norm + RMSProp on the flat buffers (policies.py:32-39, 257-264) -- under the opt-in optimizer = adam the same
+        clip + Adam; lr_dev: device scalar that overrides `lr` (captured updates: the host refreshes it when the schedule moves)."""
         ps = self.policy.params
         scale = 1.0 / self.world_size
         guard = self.handoff_guarded
         if self._status_on_wire:             # some rank timed out (summed tail != 0): this rank's status word is raised as well
             st = ops.handoff_status(self.device)[:1]
             torch.maximum(st, (ps.grad_tail != 0).to(torch.int32), out=st)
-        if self.per_agent_optimizer:
+        if self.optimizer == 'adam':         # opt-in: the same [G,P] views, clip, scale, guard and lr; Adam's slots and device counter
+            shape = (self.n_agent, ps.P) if self.per_agent_optimizer else (1, self.n_agent * ps.P)
+            ops.adam_clip(ps.flat.view(shape), ps.grad.view(shape), ps.adam_m.view(shape), ps.adam_v.view(shape), ps.scratch,
+                          ps.adam_t, lr, self.adam_beta1, self.adam_beta2, self.adam_epsilon, self.max_grad_norm, scale,
+                          self.grad_norm, lr_dev=lr_dev, guard=guard)
+        elif self.per_agent_optimizer:
             ops.rmsprop_tf_clip(ps.flat, ps.grad, ps.ms, ps.scratch, lr, self.rmsp_alpha, self.rmsp_epsilon,
                                 self.max_grad_norm, scale, self.grad_norm, lr_dev=lr_dev, guard=guard)
         else:
@@ -733,12 +753,17 @@ class IA2C:
         """`checkpoint-<step>.pt` (the reference writes TF Saver files `checkpoint-<step>.*`, models.py:53-58; the two
         formats are not interchangeable): a dict of plain tensors / numbers only, so it loads with
         torch.load(weights_only=True) -- variables under the reference's names and ragged shapes, the RMSProp slots,
-        the lr schedule position."""
+        the lr schedule position.  'optimizer' names the slots that follow: 'rmsprop_ms', or under adam 'adam_m' / 'adam_v' and the
+        step count 'adam_t' (a blob without the key is an RMSProp checkpoint of an earlier version)."""
         path = model_dir + 'checkpoint-%d.pt' % int(global_step)
         ps = self.policy.params
         sched = getattr(self, 'lr_scheduler', None)
+        if self.optimizer == 'adam':
+            slots = {'adam_m': ps.adam_m.detach().cpu(), 'adam_v': ps.adam_v.detach().cpu(), 'adam_t': ps.adam_t.detach().cpu()}
+        else:
+            slots = {'rmsprop_ms': ps.ms.detach().cpu()}
         torch.save({'variables': {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in ps.ref_variables()},
-                    'rmsprop_ms': ps.ms.detach().cpu(), 'name': self.name, 'global_step': int(global_step),
+                    'optimizer': self.optimizer, **slots, 'name': self.name, 'global_step': int(global_step),
                     'lr_n': float(sched.n) if sched is not None else -1.0}, path)
         # keep the 5 newest, like tf.train.Saver(max_to_keep=5)
         found = sorted(self._list_checkpoints(model_dir))
@@ -768,8 +793,18 @@ class IA2C:
         if save_file is not None and os.path.isfile(os.path.join(model_dir, save_file)):
             blob = torch.load(os.path.join(model_dir, save_file), weights_only=True, map_location='cpu')
             self.policy.params.load_ref_variables({k: v.numpy() for k, v in blob['variables'].items()})
-            if 'rmsprop_ms' in blob:
-                self.policy.params.ms.copy_(blob['rmsprop_ms'])
+            ps = self.policy.params
+            saved_opt = blob.get('optimizer', 'rmsprop')
+            if saved_opt != self.optimizer:
+                # the variables are all `evaluate` needs; a run that trains on starts the other optimiser from fresh slots
+                logging.warning('Checkpoint %s was written under optimizer = %s, this model uses %s: variables loaded, optimiser '
+                                'slots left fresh' % (save_file, saved_opt, self.optimizer))
+            elif self.optimizer == 'adam':
+                ps.adam_m.copy_(blob['adam_m'])
+                ps.adam_v.copy_(blob['adam_v'])
+                ps.adam_t.copy_(blob['adam_t'])
+            elif 'rmsprop_ms' in blob:
+                ps.ms.copy_(blob['rmsprop_ms'])
             if blob.get('lr_n', -1.0) >= 0 and getattr(self, 'lr_scheduler', None) is not None:
                 self.lr_scheduler.n = blob['lr_n']       # resume the lr decay where it stopped
             logging.info('Checkpoint loaded: %s' % save_file)

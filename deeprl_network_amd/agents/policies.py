@@ -91,6 +91,7 @@ class ParamStore:
         self.grad_tail = self.grad_wire[n_agent * self.P:]
         self.ms = torch.ones_like(self.flat)            # TF RMSProp slot starts at 1
         self.scratch = torch.zeros(n_agent, 64, dtype=F32, device=device)
+        self.adam_m = self.adam_v = self.adam_t = None  # the opt-in Adam state: allocated by `enable_adam` only
         self.views = {}
         for key, (o, size, shape, _, _) in self.index.items():
             w = self.flat[:, o:o + size].view(n_agent, *shape)
@@ -111,6 +112,19 @@ class ParamStore:
 
     def __getitem__(self, key):
         return self.views[key]
+
+    # ---- MODEL_CONFIG optimizer = adam (models._init_algo): first and second moment shaped like `flat`, both from 0, and ONE
+    # device-resident int32 step count (ops.adam_clip advances it on the device, so a replayed update graph counts too)
+    def enable_adam(self):
+        if self.adam_m is None:
+            self.adam_m, self.adam_v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+            self.adam_t = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def reset_adam(self):
+        if self.adam_m is not None:
+            self.adam_m.zero_()
+            self.adam_v.zero_()
+            self.adam_t.zero_()
 
     # ---- gradients of one update without an accumulation launch per parameter
     def begin_backward(self):
@@ -183,6 +197,7 @@ class ParamStore:
         with torch.no_grad():
             self.flat.copy_(torch.from_numpy(host))
         self.ms.fill_(1.0)
+        self.reset_adam()
         self.grad.zero_()
 
     # ---- reference-named export / import (checkpoint + parity tests)

@@ -427,12 +427,15 @@ __global__ __launch_bounds__(256) void epilogue_state_kernel(const EpilogueArgs 
 
 constexpr int SUMSQ_BLOCKS = 64;   // partial sums per group
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const int64_t P, const float* __restrict__ g,
-                                                    float* __restrict__ partial /*[G, SUMSQ_BLOCKS]*/) {
+// One block's partial sum of squares of its group's gradient (block x of SUMSQ_BLOCKS, group y): shared by both optimiser entries,
+// so that the norm they report for the same g has the same bits.  block_dim / grid_dim: the kernel's blockDim.x / gridDim.x, read in
+// the kernel (where the compiler knows the blocks to be uniform: sumsq_kernel keeps the instructions it had with the body in place).
+__device__ __forceinline__ void sumsq_block(const int64_t P, const float* __restrict__ g, float* __restrict__ partial,
+                                            const unsigned block_dim, const unsigned grid_dim) {
     const int grp = blockIdx.y;
     const float* gp = g + (int64_t)grp * P;
     float s = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = (int64_t)blockIdx.x * block_dim + threadIdx.x; i < P; i += (int64_t)grid_dim * block_dim) {
         const float x = gp[i];
         s += x * x;
     }
@@ -442,6 +445,11 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const int64_t P, const float
     if (lane == 0) sw[w] = s;
     __syncthreads();
     if (threadIdx.x == 0) partial[grp * SUMSQ_BLOCKS + blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+
+__global__ __launch_bounds__(256) void sumsq_kernel(const int64_t P, const float* __restrict__ g,
+                                                    float* __restrict__ partial /*[G, SUMSQ_BLOCKS]*/) {
+    sumsq_block(P, g, partial, blockDim.x, gridDim.x);
 }
 
 __global__ __launch_bounds__(256) void rmsprop_kernel(
@@ -470,6 +478,55 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(
         m = m + (gc * gc - m) * (1.0f - rho);                 // ApplyRMSProp
         ms[base + i] = m;
         w[base + i] = w[base + i] - lr * gc / sqrtf(m + eps);
+    }
+}
+
+// Opt-in Adam (Kingma & Ba) behind the same clip, nmarl_adam_clip[_guarded].  Two launches like RMSProp.  The step counter lives on
+// the device (a replayed graph re-sends the host's arguments): the FIRST launch advances it, from one thread and only when the guard
+// lets the step through; the SECOND only reads it -- no launch reads it for the bias correction and writes it.
+__global__ __launch_bounds__(256) void adam_sumsq_kernel(const int64_t P, const float* __restrict__ g, float* __restrict__ partial,
+                                                         int32_t* __restrict__ step, const int32_t* status) {
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 &&
+        !(status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+        step[0] = step[0] + 1;                         // a refused batch keeps t (the host re-runs it)
+    sumsq_block(P, g, partial, blockDim.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(
+    const int64_t P, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m1, float* __restrict__ m2,
+    const float* __restrict__ partial, const int32_t* __restrict__ step, const float* __restrict__ lr_ptr, const float lr_host,
+    const float beta1, const float beta2, const float eps, const float max_norm, const float grad_scale,
+    float* __restrict__ norm_out, int32_t* status) {
+    const int grp = blockIdx.y;
+    // fail closed, exactly as rmsprop_kernel: w, m, v keep their bits (and adam_sumsq_kernel left the counter alone)
+    if (status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(status + 1, 1);
+        return;
+    }
+    // bias corrections 1 - beta^t, once per block in float64 (t = the counter the first launch advanced), then broadcast
+    __shared__ float bc[2];
+    if (threadIdx.x == 0) {
+        const double t = (double)step[0];
+        const double lr = (double)(lr_ptr ? *lr_ptr : lr_host);
+        bc[0] = (float)(lr / (1.0 - pow((double)beta1, t)));                 // lr / (1 - beta1^t)
+        bc[1] = (float)(1.0 / sqrt(1.0 - pow((double)beta2, t)));            // 1 / sqrt(1 - beta2^t)
+    }
+    __syncthreads();
+    const float step_size = bc[0], rs_bc2 = bc[1];
+    const float tot = nmarl_ordered_sum(partial + grp * SUMSQ_BLOCKS, 1, SUMSQ_BLOCKS);
+    const float norm = sqrtf(tot) * fabsf(grad_scale);
+    float scale = grad_scale;
+    if (max_norm > 0.0f) scale = grad_scale * (max_norm * fminf(1.0f / norm, 1.0f / max_norm));
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[grp] = norm;
+    const float c1 = 1.0f - beta1, c2 = 1.0f - beta2;
+    const int64_t base = (int64_t)grp * P;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
+        const float gc = g[base + i] * scale;
+        const float m = beta1 * m1[base + i] + c1 * gc;
+        const float v = beta2 * m2[base + i] + c2 * (gc * gc);
+        m1[base + i] = m;
+        m2[base + i] = v;
+        w[base + i] = w[base + i] - step_size * m / (sqrtf(v) * rs_bc2 + eps);   // eps OUTSIDE the root
     }
 }
 
@@ -687,6 +744,27 @@ extern "C" int nmarl_rmsprop_tf_clip(int32_t G, int64_t P, float* w, const float
                                      float grad_scale, float* grad_norm_out, void* stream) {
     return nmarl_rmsprop_tf_clip_guarded(G, P, w, g, ms, scratch, lr_dev, lr, rho, eps, max_norm, grad_scale, grad_norm_out,
                                          nullptr, stream);
+}
+
+extern "C" int nmarl_adam_clip_guarded(int32_t G, int64_t P, float* w, const float* g, float* m, float* v, float* scratch,
+                                       int32_t* step, const float* lr_dev, float lr, float beta1, float beta2, float eps,
+                                       float max_norm, float grad_scale, float* grad_norm_out, int32_t* status, void* stream) {
+    if (G <= 0 || P < 0 || !w || !g || !m || !v || !scratch || !step || ((uintptr_t)step % 4) || ((uintptr_t)status % 4))
+        return NMARL_EINVAL;
+    if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps > 0.0f)) return NMARL_EINVAL;   // (NaN included)
+    if (P == 0) return NMARL_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(adam_sumsq_kernel, dim3(SUMSQ_BLOCKS, G), dim3(256), 0, s, P, g, scratch, step, (const int32_t*)status);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_x(P, 1024), G), dim3(256), 0, s, P, w, g, m, v, scratch, (const int32_t*)step, lr_dev,
+                       lr, beta1, beta2, eps, max_norm, grad_scale, grad_norm_out, status);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_adam_clip(int32_t G, int64_t P, float* w, const float* g, float* m, float* v, float* scratch, int32_t* step,
+                               const float* lr_dev, float lr, float beta1, float beta2, float eps, float max_norm,
+                               float grad_scale, float* grad_norm_out, void* stream) {
+    return nmarl_adam_clip_guarded(G, P, w, g, m, v, scratch, step, lr_dev, lr, beta1, beta2, eps, max_norm, grad_scale,
+                                   grad_norm_out, nullptr, stream);
 }
 
 static int loss_chunks(int64_t rows, int N) {

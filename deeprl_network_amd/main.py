@@ -36,6 +36,9 @@ def parse_args(argv=None):
     sp.add_argument('--gae-lambda', type=float, default=None,
                     help='lambda of generalised advantage estimation in [0, 1] (overrides MODEL_CONFIG gae_lambda; default 1 = the '
                          'reference\'s n-step advantage).  Below 1 the critic\'s target is the lambda-return')
+    sp.add_argument('--optimizer', choices=('rmsprop', 'adam'), default=None,
+                    help='optimiser behind the gradient clip (overrides MODEL_CONFIG optimizer; default rmsprop = the reference\'s '
+                         'TF-1.12 RMSProp).  adam: opt-in bias-corrected Adam (MODEL_CONFIG adam_beta1 / adam_beta2 / adam_epsilon)')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -75,10 +78,11 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda), set on every rank; run_ini (rank 0): the
-    run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer), set on every rank; run_ini
+    (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
     given = {'lstm_precision': args.lstm_precision,
-             'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda)}
+             'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
+             'optimizer': args.optimizer}
     given = {k: v for k, v in given.items() if v is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)

@@ -1855,6 +1855,18 @@ def rmsprop_tf_clip(w, g, ms, scratch, lr, rho, eps, max_norm, grad_scale=1.0, n
           'nmarl_rmsprop_tf_clip')
 
 
+def adam_clip(w, g, m, v, scratch, step, lr, beta1, beta2, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False):
+    """In-place clip_by_global_norm + bias-corrected Adam on flat [G,P] buffers (the opt-in second optimiser).  m, v: fp32 slots
+    that start at 0; step: one device int32, the steps applied so far, advanced by the call.  guard as in `rmsprop_tf_clip`: a
+    refused step changes neither w, m, v nor step."""
+    G, P = w.shape
+    check(lib.nmarl_adam_clip_guarded(G, P, ptr(w, F32), ptr(g, F32), ptr(m, F32), ptr(v, F32), ptr(scratch, F32),
+                                      ptr(step, torch.int32), ptr(lr_dev, F32), float(lr), float(beta1), float(beta2), float(eps),
+                                      float(max_norm), float(grad_scale), ptr(norm_out, F32),
+                                      ptr(handoff_status(w.device), torch.int32) if (guard and w.is_cuda) else None, stream()),
+          'nmarl_adam_clip')
+
+
 _epilogue_scratch = {}
 
 

@@ -1005,6 +1005,29 @@ int nmarl_rmsprop_tf_clip(int32_t G, int64_t P, float* w, const float* g, float*
                           float grad_scale, float* grad_norm_out, void* stream);
 
 /*
+ * Opt-in second optimiser (MODEL_CONFIG optimizer = adam; the reference has RMSProp only): the same clip_by_global_norm, then Adam
+ * (Kingma & Ba 2015) with bias correction, on the same flat [G,P] buffers.  Per group, with t = step[0] + 1:
+ *     norm = ||g_grp|| * |grad_scale|                  (the partial sums and the fixed order of nmarl_rmsprop_tf_clip: same bits)
+ *     gc   = g * grad_scale * (max_norm * min(1 / norm, 1 / max_norm))        (max_norm > 0; else gc = g * grad_scale)
+ *     m    = beta1 m + (1 - beta1) gc          v = beta2 v + (1 - beta2) gc^2
+ *     w   -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)   (eps OUTSIDE the root)
+ *     step[0] = t
+ * m, v: fp32 slots, both start at 0.  step: ONE device-resident int32 shared by all groups, the number of steps applied so far
+ * (device-side because a replayed graph re-sends the host's arguments); the first of the two launches advances it, the second reads
+ * it.  1 - beta^t is formed in float64 once per block.  lr_dev: NULL, or a device scalar that overrides lr.  scratch: [G,64] floats.
+ * status (guarded form; NULL = unguarded): while status[0] != 0 NOTHING changes -- w, m, v and step keep their bits -- and status[1]
+ * counts the refused step, as nmarl_rmsprop_tf_clip_guarded does.  No float atomics: two runs give the same bits.
+ * NMARL_EINVAL (nothing written, nothing launched): a null w / g / m / v / scratch / step, G <= 0, P < 0, beta1 or beta2 outside
+ * [0, 1), eps <= 0, or a NaN in one of them.  P == 0: NMARL_OK without a launch.
+ */
+int nmarl_adam_clip_guarded(int32_t G, int64_t P, float* w, const float* g, float* m, float* v, float* scratch, int32_t* step,
+                            const float* lr_dev, float lr, float beta1, float beta2, float eps, float max_norm,
+                            float grad_scale, float* grad_norm_out, int32_t* status, void* stream);
+int nmarl_adam_clip(int32_t G, int64_t P, float* w, const float* g, float* m, float* v, float* scratch, int32_t* step,
+                    const float* lr_dev, float lr, float beta1, float beta2, float eps, float max_norm, float grad_scale,
+                    float* grad_norm_out, void* stream);
+
+/*
  * Between two n_step batches of the batched loop (two launches instead of ~45 elementwise ones):
  *  - episode statistics as Trainer.run keeps them (utils.py:228-229: mean / std of an episode's global rewards): g [T][E]
  *    the batch's global rewards, done [E] u8 the flags of its last lock-step; per replica running ep_sum / ep_sq / ep_len
