@@ -14,7 +14,8 @@ Engine (per n_step batch, E replicas, N agents):
             from the state `forward('p')` just wrote);
   buffers   [T,...] device tensors replacing OnPolicyBuffer's Python lists
             (agents/utils.py:722-761, 819-835);
-  update    nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) -> autograd unroll -> A2C loss (policies.py:20-30,
+  update    nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) [-> opt-in adv_norm: nmarl_standardize, the policy term's
+            advantage per agent / over all agents to zero mean and unit std] -> autograd unroll -> A2C loss (policies.py:20-30,
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
             nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip).
 """
@@ -90,6 +91,15 @@ class IA2C:
                 raise ValueError('%s = %r: must lie in [0, 1)' % (key, getattr(self, key)))
         if not self.adam_epsilon > 0.0:
             raise ValueError('adam_epsilon = %r: must be positive' % self.adam_epsilon)
+        # optional (absent: 'none' = the raw advantage in the policy-gradient term, as before): 'agent' standardises every agent's
+        # T*E advantages of a batch to zero mean and unit std (each agent has its own critic), 'all' the N*T*E of all agents together
+        # -- ops.standardize behind the return scan; the critic's target R is left alone
+        self.adv_norm = model_config.get('adv_norm', fallback='none').strip().lower()
+        if self.adv_norm not in ('none', 'agent', 'all'):
+            raise ValueError('adv_norm = %r: must be none, agent or all' % self.adv_norm)
+        self.adv_norm_epsilon = model_config.getfloat('adv_norm_epsilon', fallback=1e-8)
+        if not self.adv_norm_epsilon >= 0.0:                 # (nan fails the comparison)
+            raise ValueError('adv_norm_epsilon = %r: must be >= 0' % self.adv_norm_epsilon)
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -199,6 +209,13 @@ class IA2C:
         self.buf_r = torch.zeros((T, E, N) if spatial else (T, E), dtype=F32, device=d)
         self.R = torch.zeros(N, T, E, dtype=F32, device=d)
         self.Adv = torch.zeros(N, T, E, dtype=F32, device=d)
+        if self.adv_norm != 'none':
+            # opt-in: the standardised advantage the policy-gradient term reads (Adv itself stays raw for every other reader), the
+            # kernel's per-chunk moments and the (mean, std) of every group of the last update
+            G = N if self.adv_norm == 'agent' else 1
+            self.Adv_n = torch.zeros(N, T, E, dtype=F32, device=d)
+            self._adv_partial = torch.zeros(G, ops.standardize_chunks(N * T * E // G, G), 3, dtype=torch.float64, device=d)
+            self.adv_moments = torch.zeros(G, 2, dtype=torch.float64, device=d)
         self.dist_dev = torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
@@ -471,6 +488,10 @@ class IA2C:
         return p.step_value(enc, self.h_fw, self.c_fw, done, self._h2, self._c2, action_scratch, self._v_boot,
                             done_is_zero)
 
+    def _policy_adv(self):
+        """The advantage of the policy-gradient term [N,T,E]: Adv, or under the opt-in adv_norm its standardised copy."""
+        return self.Adv if self.adv_norm == 'none' else self.Adv_n
+
     def _loss_backward_fused(self, Hs):
         """`_loss(Hs).backward()` with the heads, the loss and the heads' backward as ONE pass over the h sequence
         (ops.heads_loss): this call is the root of the update's backward -- the head parameters receive their gradients here, the
@@ -485,7 +506,7 @@ class IA2C:
         # the one-launch BPTT kernels take the heads' dL/dh as dy8 (32 bytes per row) and expand it themselves: no [N,T*E,64] tensor
         as_dy = self.save_acts and p.bptt_takes_head_dy and os.environ.get('NMARL_BPTT_HEAD_DY', '1') != '0'
         r = ops.heads_loss(Hs.detach(), prm['pi_w'], prm['pi_b'], prm['v_w'], prm['v_b'], action, p.nbr_idx, self.n_a,
-                           self.Adv.view(N, T * E), self.R.view(N, T * E), self.v_coef, self.e_coef, want_dh=not as_dy)
+                           self._policy_adv().view(N, T * E), self.R.view(N, T * E), self.v_coef, self.e_coef, want_dh=not as_dy)
         terms = self._terms = r['terms']
         self.last_loss = (terms[:, 0], terms[:, 1], terms[:, 2], terms.sum(dim=1))
         for k in ('pi_w', 'pi_b', 'v_w', 'v_b'):
@@ -502,7 +523,7 @@ class IA2C:
         # the critic's neighbour one-hots (policies.py:66-68) are gathered from the action bytes inside the op
         action = self.buf_act.view(T * E, N)
         logits, v = p.heads(Hs, action)                                       # [N,T*E,A], [N,T*E]
-        adv = self.Adv.view(N, T * E)
+        adv = self._policy_adv().view(N, T * E)
         R = self.R.view(N, T * E)
         if not self.identical_agent and not self.per_agent_optimizer:
             # quirk Q6 (heterogeneous MA2C nets only, policies.py:241-254): the hetero branch builds prob_pi as
@@ -578,6 +599,10 @@ class IA2C:
         else:           # opt-in GAE(lambda): Adv = the lambda-weighted TD errors, R = Adv + v (the critic's target)
             ops.gae_return(self.buf_r, self.buf_v, self.buf_done_post, R_end.contiguous(), self.gamma, self.gae_lambda, alpha,
                            self.dist_dev, self.R, self.Adv)
+        if self.adv_norm != 'none':     # opt-in: Adv_n = (Adv - mean) / (std + eps) per agent / over all agents; Adv and R stay as they are
+            G = self.adv_moments.shape[0]
+            ops.standardize(self.Adv.view(G, -1), self.adv_norm_epsilon, out=self.Adv_n.view(G, -1), partial=self._adv_partial,
+                            moments=self.adv_moments)
         ps = self.policy.params
         ps.begin_backward()
         FP = self.buf_fp[:T].permute(1, 0, 2, 3).reshape(self.n_agent, T * self.E, self.n_a)

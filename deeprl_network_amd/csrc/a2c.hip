@@ -530,6 +530,139 @@ __global__ __launch_bounds__(256) void adam_kernel(
     }
 }
 
+// ---- per-batch advantage standardisation over [G, rows] (opt-in, MODEL_CONFIG adv_norm; the reference has none) ----
+//   mu = mean x;  sigma = sqrt(mean (x - mu)^2) (population);  y = (x - mu) / (sigma + eps), eps OUTSIDE the root
+// in float64 on the fp32 inputs, one rounding to fp32 on the store.  Two launches like sumsq_kernel / rmsprop_kernel, the caller's
+// `partial` [G, chunks, 3] between them; a group's rows are cut into `chunks` contiguous pieces of `per` = ceil(rows / chunks).
+//   (1) standardize_moments_kernel: block (chunk, group) -> the sum, the mean and M2 of its piece, two passes over the piece (the
+//       sums, then the squares of the centred values: never E[x^2] - mu^2); the second pass re-reads what the first just brought
+//       into the cache;
+//   (2) standardize_apply_kernel: every block adds its group's sums and merges its (count, mean, M2) by Chan's formula in one fixed
+//       tree, block 0 of a group writes (mu, sigma), each block writes y for its piece.
+// The means Chan's formula works on are kept RELATIVE TO THE GROUP'S FIRST ELEMENT K = x[g, 0]: x - K is exact in float64 for fp32
+// values of like magnitude, and the difference of two chunk means -- the term the formula squares -- then carries the rounding of
+// numbers of the size of the spread, not of the size of the offset (advantages at 3e4 +- 1e-2: with plain means the rounding of
+// each mean, 4e-12, against differences of ~1e-3 leaves sigma good to ~1e-11 at any chunking; relative to K it is good to ~1e-15).
+// The variance does not see the shift.  mu does not go through K (K + a mean relative to K cancels where the data are centred and
+// K is an outlying value): it is the plain sum over rows, the chunks' plain sums added in the same tree.  A triple in `partial` is
+// (sum, mean - K, M2): the count of a chunk follows from (rows, per, chunk), and only the first launch, which writes nothing to y,
+// reads K -- in place, x[g, 0] is overwritten by the second.
+// 4-byte accesses in (1): the order of every sum is a function of (rows, chunks) alone, not of where a group starts (a dense pitch
+// with odd rows puts group bases off 16 bytes); (2) has no order to keep and moves 16 bytes per lane between the peeled ends.
+constexpr int STD_MAX_CHUNKS = 512;                 // slots of the merge tree: 2 per thread of a 256-thread block
+
+// Sum over the block in a fixed order (lanes by shuffle, then the four waves), returned to every thread.  `sw`: 4 doubles of LDS
+// per call site (no barrier between two uses of the same words).
+__device__ __forceinline__ double std_block_sum(double s, double* sw) {
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+
+// rows of chunk c: per, fewer in the last chunk that has any, 0 behind it (rows < chunks happens)
+__device__ __forceinline__ int64_t std_chunk_rows(const int64_t rows, const int64_t per, const int64_t c) {
+    const int64_t left = rows - c * per;
+    return left < per ? (left > 0 ? left : 0) : per;
+}
+
+__global__ __launch_bounds__(256) void standardize_moments_kernel(const int64_t rows, const int64_t per, const float* __restrict__ x,
+                                                                  const int64_t x_sg, double* __restrict__ partial) {
+    const int64_t n = std_chunk_rows(rows, per, blockIdx.x);
+    const float* xg = x + (int64_t)blockIdx.y * x_sg;
+    const float* xp = xg + (int64_t)blockIdx.x * per;
+    const double K = (double)xg[0];
+    __shared__ double sw[3][4];
+    double s = 0.0, ps = 0.0;
+#pragma unroll 4
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const double v = (double)xp[i];
+        ps += v;
+        s += v - K;
+    }
+    const double sum = std_block_sum(ps, sw[2]);
+    const double tot = std_block_sum(s, sw[0]);
+    const double mean = n > 0 ? tot / (double)n : 0.0;                  // (of x - K)
+    double q = 0.0;
+#pragma unroll 4
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const double d = ((double)xp[i] - K) - mean;
+        q += d * d;
+    }
+    const double m2 = std_block_sum(q, sw[1]);
+    if (threadIdx.x == 0) {
+        double* p = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+        p[0] = sum; p[1] = mean; p[2] = m2;
+    }
+}
+
+struct StdMoments { double n, sum, mean, m2; };    // sum: of x;  mean: of x - K
+
+// Chan, Golub & LeVeque: the moments of A followed by B (and the plain sums added).  An empty side is a no-op (no 0 / 0).
+__device__ __forceinline__ StdMoments std_merge(const StdMoments a, const StdMoments b) {
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    const double n = a.n + b.n, delta = b.mean - a.mean;
+    return StdMoments{n, a.sum + b.sum, a.mean + delta * (b.n / n), (a.m2 + b.m2) + (delta * delta) * (a.n * (b.n / n))};
+}
+
+__global__ __launch_bounds__(256) void standardize_apply_kernel(const int64_t rows, const int64_t per, const float* x, const int64_t x_sg,
+                                                                float* y, const int64_t y_sg, const double eps,
+                                                                const double* __restrict__ partial, double* __restrict__ moments) {
+    const int grp = blockIdx.y, C = gridDim.x, tid = threadIdx.x;
+    const double* p = partial + (int64_t)grp * C * 3;
+    // the group's C triples in one fixed tree over STD_MAX_CHUNKS slots (slot c = chunk c, empty behind C): slot t with t + 256, then
+    // halving strides in LDS -- the same in every block of the group.  Every block of a group repeats the merge (up to 12 KB of
+    // triples read from the cache and nine merge levels per block, ~6 MB of cache reads per call at 512 blocks): block 0 alone
+    // could hand the result to the others only through a third launch, which costs more than the repeats
+    __shared__ StdMoments sm[256];
+    {
+        StdMoments a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
+        if (tid < C) a = StdMoments{(double)std_chunk_rows(rows, per, tid), p[tid * 3], p[tid * 3 + 1], p[tid * 3 + 2]};
+        if (tid + 256 < C)
+            b = StdMoments{(double)std_chunk_rows(rows, per, tid + 256), p[(tid + 256) * 3], p[(tid + 256) * 3 + 1], p[(tid + 256) * 3 + 2]};
+        sm[tid] = std_merge(a, b);
+    }
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) sm[tid] = std_merge(sm[tid], sm[tid + off]);
+        __syncthreads();
+    }
+    const double mu = sm[0].sum / (double)rows, sigma = sqrt(sm[0].m2 / (double)rows);
+    if (blockIdx.x == 0 && tid == 0 && moments) {
+        moments[grp * 2] = mu;
+        moments[grp * 2 + 1] = sigma;
+    }
+    // y = (x - mu) * (1 / (sigma + eps)) in float64: the quotient of the definition to one more float64 rounding, far inside
+    // the one fp32 rounding of the store; sigma = 0 with eps > 0 gives exact zeros, 0 * inf = NaN where the definition has 0 / 0
+    const double inv = 1.0 / (sigma + eps);
+#define NMARL_STD(v) (float)(((double)(v) - mu) * inv)
+    const int64_t n = std_chunk_rows(rows, per, blockIdx.x);
+    const float* xp = x + (int64_t)grp * x_sg + (int64_t)blockIdx.x * per;     // (no __restrict__: y == x is allowed; every element is
+    float* yp = y + (int64_t)grp * y_sg + (int64_t)blockIdx.x * per;           //  read, then written, by one thread)
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(xp), ya = reinterpret_cast<uintptr_t>(yp);
+    if (((xa ^ ya) & 15u) == 0) {
+        // the same peel aligns both: up to 3 floats in front, float4 in the middle, up to 3 behind
+        int64_t head = (int64_t)(((16u - (unsigned)(xa & 15u)) & 15u) >> 2);
+        head = head < n ? head : n;
+        const int64_t n4 = (n - head) >> 2;
+        if (tid < head) yp[tid] = NMARL_STD(xp[tid]);
+        const float4* x4 = reinterpret_cast<const float4*>(xp + head);
+        float4* y4 = reinterpret_cast<float4*>(yp + head);
+        for (int64_t i = tid; i < n4; i += 256) {
+            const float4 v = x4[i];
+            float4 o;
+            o.x = NMARL_STD(v.x); o.y = NMARL_STD(v.y); o.z = NMARL_STD(v.z); o.w = NMARL_STD(v.w);
+            y4[i] = o;
+        }
+        const int64_t done = head + (n4 << 2);
+        if (done + tid < n) yp[done + tid] = NMARL_STD(xp[done + tid]);
+    } else {
+        for (int64_t i = tid; i < n; i += 256) yp[i] = NMARL_STD(xp[i]);
+    }
+#undef NMARL_STD
+}
+
 // A2C loss of Policy.prepare_loss (policies.py:20-30; NCMultiAgentPolicy 232-255) for all agents and rows:
 //   pi = softmax(logits); log_pi = log(clip(pi, 1e-10, 1)); H = -sum pi log_pi
 //   policy = -mean(log_pi[a] ADV);  value = 0.5 v_coef mean((R - v)^2);  entropy = -e_coef mean(H)
@@ -765,6 +898,30 @@ extern "C" int nmarl_adam_clip(int32_t G, int64_t P, float* w, const float* g, f
                                float grad_scale, float* grad_norm_out, void* stream) {
     return nmarl_adam_clip_guarded(G, P, w, g, m, v, scratch, step, lr_dev, lr, beta1, beta2, eps, max_norm, grad_scale,
                                    grad_norm_out, nullptr, stream);
+}
+
+// Chunks per group of nmarl_standardize: G x chunks ~ 512 blocks, two per compute unit of a 256-CU device at G = 8 (64 chunks of
+// 3840 rows at rows = 245 760) and at G = 1 (512 chunks of 6000 rows at rows = 3 072 000).  A function of the arguments alone (never
+// of the device: two boxes cut and sum alike); it does not shrink for short groups -- chunks behind the last row are empty and merge
+// as no-ops, so the launch shape of a captured graph follows G only.
+extern "C" int nmarl_standardize_chunks(int64_t rows, int32_t G) {
+    (void)rows;
+    const int c = G > 0 ? (STD_MAX_CHUNKS + G - 1) / G : 1;
+    return c < 1 ? 1 : (c > STD_MAX_CHUNKS ? STD_MAX_CHUNKS : c);
+}
+
+extern "C" int nmarl_standardize(int32_t G, int64_t rows, const float* x, int64_t x_sg, float* y, int64_t y_sg, double eps,
+                                 double* partial, double* moments, void* stream) {
+    if (rows < 1 || G < 0 || G > 65535 || x_sg < rows || y_sg < rows || !(eps >= 0.0)) return NMARL_EINVAL;   // (NaN included)
+    if (G == 0) return NMARL_OK;
+    if (!x || !y || !partial) return NMARL_EINVAL;
+    const int C = nmarl_standardize_chunks(rows, G);
+    const int64_t per = (rows + C - 1) / C;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(standardize_moments_kernel, dim3(C, G), dim3(256), 0, s, rows, per, x, x_sg, partial);
+    hipLaunchKernelGGL(standardize_apply_kernel, dim3(C, G), dim3(256), 0, s, rows, per, x, x_sg, y, y_sg, eps,
+                       (const double*)partial, moments);
+    return nmarl_check_launch();
 }
 
 static int loss_chunks(int64_t rows, int N) {

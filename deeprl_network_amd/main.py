@@ -39,6 +39,10 @@ def parse_args(argv=None):
     sp.add_argument('--optimizer', choices=('rmsprop', 'adam'), default=None,
                     help='optimiser behind the gradient clip (overrides MODEL_CONFIG optimizer; default rmsprop = the reference\'s '
                          'TF-1.12 RMSProp).  adam: opt-in bias-corrected Adam (MODEL_CONFIG adam_beta1 / adam_beta2 / adam_epsilon)')
+    sp.add_argument('--adv-norm', choices=('none', 'agent', 'all'), default=None,
+                    help='per-batch standardisation of the advantage in the policy-gradient term (overrides MODEL_CONFIG adv_norm; '
+                         'default none).  agent: zero mean and unit std per agent; all: over all agents together.  The critic\'s '
+                         'target is not touched (MODEL_CONFIG adv_norm_epsilon, default 1e-8, is added to the std)')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -78,11 +82,12 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer), set on every rank; run_ini
-    (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm), set on every rank;
+    run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
     given = {'lstm_precision': args.lstm_precision,
              'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
-             'optimizer': args.optimizer}
+             'optimizer': args.optimizer,
+             'adv_norm': args.adv_norm}
     given = {k: v for k, v in given.items() if v is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)

@@ -1867,6 +1867,31 @@ def adam_clip(w, g, m, v, scratch, step, lr, beta1, beta2, eps, max_norm, grad_s
           'nmarl_adam_clip')
 
 
+def standardize_chunks(rows, G):
+    """Chunks per group of `standardize` (the middle extent of its `partial`): a function of the two numbers alone."""
+    return int(lib.nmarl_standardize_chunks(int(rows), int(G)))
+
+
+def standardize(x, eps, out=None, partial=None, moments=None):
+    """Per group g of x [G, rows] (fp32 views with unit column stride, any group pitch >= rows): out = (x - mean) / (std + eps) with
+    the population std, float64 arithmetic, one rounding (the opt-in advantage standardisation).  out may be x.
+    partial: float64 [G, standardize_chunks(rows, G), 3] scratch, moments: float64 [G, 2] receiving (mean, std); both optional."""
+    G, rows = x.shape
+    if out is None:
+        out = torch.empty(G, rows, dtype=F32, device=x.device)
+    if tuple(out.shape) != (G, rows) or (rows > 1 and (x.stride(1) != 1 or out.stride(1) != 1)):
+        raise ValueError('standardize: x and out must be [G, rows] views with unit column stride')
+    C = standardize_chunks(rows, G)
+    if partial is None:
+        partial = torch.empty(G, C, 3, dtype=torch.float64, device=x.device)
+    if partial.numel() < G * C * 3 or (moments is not None and moments.numel() < 2 * G):
+        raise ValueError('standardize: partial needs [G, %d, 3] and moments [G, 2] float64' % C)
+    pitch = lambda t: t.stride(0) if G > 1 else rows           # noqa: E731  (a single group has no pitch to speak of)
+    check(lib.nmarl_standardize(G, rows, ptr(x, F32, strided=True), pitch(x), ptr(out, F32, strided=True), pitch(out), float(eps),
+                                ptr(partial, torch.float64), ptr(moments, torch.float64), stream()), 'nmarl_standardize')
+    return out
+
+
 _epilogue_scratch = {}
 
 

@@ -1028,6 +1028,31 @@ int nmarl_adam_clip(int32_t G, int64_t P, float* w, const float* g, float* m, fl
                     float* grad_norm_out, void* stream);
 
 /*
+ * Opt-in per-batch advantage standardisation (MODEL_CONFIG adv_norm = agent | all; the reference has none).  x, y: G groups of
+ * `rows` fp32 values, group g at x + g x_sg / y + g y_sg (pitches in floats, >= rows; the floats of a pitch behind `rows` keep their
+ * bits).  Per group, in float64 on the fp32 inputs, one rounding to fp32 on the store:
+ *     mu    = (1 / rows) sum x
+ *     sigma = sqrt((1 / rows) sum (x - mu)^2)          (population variance, no rows - 1)
+ *     y     = (x - mu) / (sigma + eps)                 (eps OUTSIDE the root; the kernel multiplies by the float64 reciprocal)
+ * A constant group, or rows = 1, has sigma = 0 and (eps > 0) y = 0 exactly.  Non-finite inputs propagate inside their group only.
+ * y == x (in place) is allowed, any other overlap is not.  Two launches, kernel nodes only (no memset, no memcpy, no float atomics:
+ * two runs, and two boxes, give the same bits): the first forms per (group, chunk) the float64 moments (count, mean, M2) of a
+ * contiguous chunk of ceil(rows / chunks) rows -- M2 from the centred values, never E[x^2] - mu^2 -- and leaves them in the caller's
+ * partial [G, chunks, 3]; the second merges a group's moments by Chan's formula in one fixed tree (an empty chunk is a no-op),
+ * writes moments [G, 2] = (mu, sigma) if moments != NULL, and y.  The means Chan's formula works on are taken relative to the
+ * group's first element K = x[g, 0] (x - K is exact in float64 for fp32 values of like magnitude, so the difference of two chunk
+ * means keeps its digits when the data sit far from zero); mu is the plain sum over rows, the chunks' plain sums added in the same
+ * tree.  A triple in `partial` holds (sum, mean - K, M2); a chunk's count follows from rows and chunks.
+ * `partial` is scratch: its contents between and after the launches are not part of the interface.
+ * chunks = nmarl_standardize_chunks(rows, G) >= 1, at most 512, a function of its arguments alone (not of the device).
+ * NMARL_EINVAL (nothing written, nothing launched): rows < 1, G < 0 or G > 65535, a pitch below rows, eps < 0 or NaN, and with
+ * G > 0 a null x / y / partial.  G == 0: NMARL_OK without a launch.
+ */
+int nmarl_standardize_chunks(int64_t rows, int32_t G);
+int nmarl_standardize(int32_t G, int64_t rows, const float* x, int64_t x_sg, float* y, int64_t y_sg, double eps,
+                      double* partial /* [G, chunks, 3] */, double* moments /* [G, 2] = (mu, sigma), may be NULL */, void* stream);
+
+/*
  * Between two n_step batches of the batched loop (two launches instead of ~45 elementwise ones):
  *  - episode statistics as Trainer.run keeps them (utils.py:228-229: mean / std of an episode's global rewards): g [T][E]
  *    the batch's global rewards, done [E] u8 the flags of its last lock-step; per replica running ep_sum / ep_sq / ep_len
