@@ -272,6 +272,8 @@ SIGNATURES = {
     'nmarl_adam_clip_guarded': [_i32, _i64, _p, _p, _p, _p, _p, _p, _p, _f32, _f32, _f32, _f32, _f32, _f32, _p, _p, _p],
     'nmarl_standardize_chunks': [_i64, _i32],
     'nmarl_standardize': [_i32, _i64, _p, _i64, _p, _i64, C.c_double, _p, _p, _p],
+    'nmarl_reward_scale_chunks': [_i64],
+    'nmarl_reward_scale': [_i64, _i32, _i32, _p, _p, C.c_double, C.c_double, _f32, _p, _p, _p, _p, _p],
     'nmarl_handoff_capacity': [_i32, _i32],
     'nmarl_test_handoff_fault': [_i32],
     'nmarl_batch_epilogue': [C.POINTER(BatchEpilogue), _p],

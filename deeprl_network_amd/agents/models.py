@@ -14,7 +14,8 @@ Engine (per n_step batch, E replicas, N agents):
             from the state `forward('p')` just wrote);
   buffers   [T,...] device tensors replacing OnPolicyBuffer's Python lists
             (agents/utils.py:722-761, 819-835);
-  update    nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) [-> opt-in adv_norm: nmarl_standardize, the policy term's
+  update    rewards / reward_norm, clamped (opt-in reward_scale = return: nmarl_reward_scale, rewards over the running std of the
+            discounted return) -> nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) [-> opt-in adv_norm: nmarl_standardize, the policy term's
             advantage per agent / over all agents to zero mean and unit std] -> autograd unroll -> A2C loss (policies.py:20-30,
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
             nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip).
@@ -100,6 +101,17 @@ class IA2C:
         self.adv_norm_epsilon = model_config.getfloat('adv_norm_epsilon', fallback=1e-8)
         if not self.adv_norm_epsilon >= 0.0:                 # (nan fails the comparison)
             raise ValueError('adv_norm_epsilon = %r: must be >= 0' % self.adv_norm_epsilon)
+        # optional (absent: 'none' = raw / reward_norm, as before): 'return' divides the rewards of a batch by the running standard
+        # deviation of the discounted return over every sample seen so far (ops.reward_scale, in place of reward_norm)
+        self.reward_scale = model_config.get('reward_scale', fallback='none').strip().lower()
+        if self.reward_scale not in ('none', 'return'):
+            raise ValueError('reward_scale = %r: must be none or return' % self.reward_scale)
+        self.reward_scale_epsilon = model_config.getfloat('reward_scale_epsilon', fallback=1e-8)
+        if not self.reward_scale_epsilon >= 0.0:             # (nan fails the comparison)
+            raise ValueError('reward_scale_epsilon = %r: must be >= 0' % self.reward_scale_epsilon)
+        if self.reward_scale != 'none':
+            logging.info('reward_scale = %s: rewards are divided by the running std of the discounted return; reward_norm = %r '
+                         'is not applied' % (self.reward_scale, self.reward_norm))
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -216,6 +228,15 @@ class IA2C:
             self.Adv_n = torch.zeros(N, T, E, dtype=F32, device=d)
             self._adv_partial = torch.zeros(G, ops.standardize_chunks(N * T * E // G, G), 3, dtype=torch.float64, device=d)
             self.adv_moments = torch.zeros(G, 2, dtype=torch.float64, device=d)
+        if self.reward_scale != 'none':
+            # opt-in: the discounted return carried across batches per reward stream, the pooled running moments, the kernel's
+            # per-block moments, and the raw rewards of a batch of the one-replica path (`record` per step)
+            S = self.buf_r[0].numel()
+            self.rs_carry = torch.zeros(S, dtype=torch.float64, device=d)
+            self.rs_state = torch.zeros(ops.REWARD_SCALE_STATE, dtype=torch.float64, device=d)
+            self._rs_partial = torch.zeros(ops.reward_scale_chunks(S), 4, dtype=torch.float64, device=d)
+            self._rs_raw = torch.zeros_like(self.buf_r)
+            self._rs_pending = False
         self.dist_dev = torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
@@ -426,7 +447,11 @@ class IA2C:
     def record(self, reward, done_post):
         """model.add_transition's reward path (models.py:26-32) for slot t: normalise, clip, store."""
         t = self.t
-        self.buf_r[t].copy_(self._norm_reward(reward))
+        if self.reward_scale != 'none':      # opt-in: keep the raw reward; update_grads scales the whole batch in front of the return scan
+            self._rs_raw[t].copy_(reward)
+            self._rs_pending = True
+        else:
+            self.buf_r[t].copy_(self._norm_reward(reward))
         self.buf_done_post[t].copy_(done_post)
         self.t = t + 1
 
@@ -441,6 +466,10 @@ class IA2C:
         """Batched path: the env kernel wrote raw rewards for all T slots (and done flags straight
         into buf_done_post); normalise them in one pass and mark the batch complete."""
         # (written in place: `buf_r.copy_(temporary)` is a memcpy node inside the captured update)
+        if self.reward_scale != 'none':      # opt-in: the one native call in place of the division and the clamp
+            self._scale_rewards(raw_rewards)
+            self.t = self.n_step
+            return
         if self.reward_norm > 0:
             torch.div(raw_rewards, self.reward_norm, out=self.buf_r)
         else:
@@ -448,6 +477,18 @@ class IA2C:
         if self.reward_clip > 0:
             self.buf_r.clamp_(-self.reward_clip, self.reward_clip)
         self.t = self.n_step
+
+    def _scale_rewards(self, raw_rewards):
+        """Opt-in reward_scale = return: advance the carried discounted returns and the pooled running moments by this batch's raw
+        rewards and done flags, buf_r = raw / (running std + eps), clamped to reward_clip (reward_norm is not applied)."""
+        ops.reward_scale(raw_rewards, self.buf_done_post, self.gamma, self.reward_scale_epsilon, max(self.reward_clip, 0.0),
+                         self.rs_carry, self.rs_state, self._rs_partial, self.buf_r)
+        self._rs_pending = False
+
+    @property
+    def reward_scale_std(self):
+        """The running std of the discounted return the last update divided by (host read: synchronises); None with the key off."""
+        return None if self.reward_scale == 'none' else float(self.rs_state[6])
 
     def bootstrap(self, done, action_scratch, mode=ops.SAMPLE_PHILOX, u=None, seed=0, env_id_base=0,
                   step=0, step_dev=None, done_is_zero=False, pre_encoded=False):
@@ -585,6 +626,9 @@ class IA2C:
         synchronisation, static shapes and addresses: capturable)."""
         alpha = self.coop_gamma if self.coop_gamma >= 0 else -1.0
         T = self.n_step
+        if self.reward_scale != 'none' and self._rs_pending:
+            # the one-replica path (`record` per step kept the raw rewards): the same one call the batched path makes in load_rewards
+            self._scale_rewards(self._rs_raw)
         if self.save_acts and self.policy.pv_one_launch(self.E):
             # the critic's neighbour-action term of all T lock-steps in one launch (policies.py:59-77), then the values
             # in the [T,N,E] order the return scan reads
@@ -787,6 +831,10 @@ class IA2C:
             slots = {'adam_m': ps.adam_m.detach().cpu(), 'adam_v': ps.adam_v.detach().cpu(), 'adam_t': ps.adam_t.detach().cpu()}
         else:
             slots = {'rmsprop_ms': ps.ms.detach().cpu()}
+        if self.reward_scale != 'none' and hasattr(self, 'rs_state'):
+            # opt-in reward scaling: the setting, the pooled running moments and the carried discounted returns (absent otherwise)
+            slots.update({'reward_scale': self.reward_scale, 'reward_scale_state': self.rs_state.detach().cpu(),
+                          'reward_scale_carry': self.rs_carry.detach().cpu()})
         torch.save({'variables': {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in ps.ref_variables()},
                     'optimizer': self.optimizer, **slots, 'name': self.name, 'global_step': int(global_step),
                     'lr_n': float(sched.n) if sched is not None else -1.0}, path)
@@ -830,6 +878,18 @@ class IA2C:
                 ps.adam_t.copy_(blob['adam_t'])
             elif 'rmsprop_ms' in blob:
                 ps.ms.copy_(blob['rmsprop_ms'])
+            saved_rs = blob.get('reward_scale', 'none')
+            if saved_rs != self.reward_scale:
+                logging.warning('Checkpoint %s was written under reward_scale = %s, this model uses %s: variables loaded, the '
+                                'reward-scale statistics left fresh' % (save_file, saved_rs, self.reward_scale))
+            elif self.reward_scale != 'none' and hasattr(self, 'rs_state'):
+                self.rs_state.copy_(blob['reward_scale_state'])
+                if tuple(blob['reward_scale_carry'].shape) == tuple(self.rs_carry.shape):
+                    self.rs_carry.copy_(blob['reward_scale_carry'])
+                else:
+                    logging.warning('Checkpoint %s carries %d discounted returns, this model %d (another num_envs): moments loaded, '
+                                    'the carried returns left fresh' % (save_file, blob['reward_scale_carry'].numel(),
+                                                                        self.rs_carry.numel()))
             if blob.get('lr_n', -1.0) >= 0 and getattr(self, 'lr_scheduler', None) is not None:
                 self.lr_scheduler.n = blob['lr_n']       # resume the lr decay where it stopped
             logging.info('Checkpoint loaded: %s' % save_file)

@@ -663,6 +663,133 @@ __global__ __launch_bounds__(256) void standardize_apply_kernel(const int64_t ro
 #undef NMARL_STD
 }
 
+// ---- running return-based reward scaling (opt-in, MODEL_CONFIG reward_scale = return; the reference has none) ----
+// S = E (global reward [T,E]) or E * N (per-agent reward [T,E,N]) reward streams, stream s of replica e = s (/ N).  Per call:
+//   for t = 0..T-1: carry[s] = gamma carry[s] + r[t,s];  sample x = carry[s];  if done_post[t,e]: carry[s] = 0 (after the sample)
+//   (n, mean, M2) <- the running population moments merged with the call's T S samples;  sigma = sqrt(M2 / n)
+//   scale = sigma > 0 ? 1 / (sigma + eps) : 1;  r_out = fp32(double(r) scale), then clamped to +-clip if clip > 0
+// all in float64.  THREE launches, the caller's `partial` [chunks, 4] and `state` [NMARL_REWARD_SCALE_STATE] between them:
+//   (1) reward_scale_scan_kernel: one lane per stream (stream fastest in r: every load of r[t, .] coalesced), block b takes streams
+//       b 256 + lane and then, past chunks x 256 streams, every (chunks 256)-th one behind it in ascending order; each lane runs
+//       Welford over its own samples; lanes -> waves -> block by Chan's formula in one fixed order (shuffles, then the four waves);
+//       one (n, sum, mean - K, M2) per block to `partial`; carry[s] is read and written by the one lane that owns s;
+//   (2) reward_scale_merge_kernel, ONE block: the partials in one fixed tree (std_merge), then prior state + batch, the new state;
+//   (3) reward_scale_apply_kernel: r_out from `scale` in the state.
+// The running state is read and written by the same call.  Chosen: the one-block merge launch between scan and apply is the ONLY
+// writer of `state`; (1) reads the state of before the call (n and K), (3) the state of after it, and launches on a stream run in
+// order -- so no block can read a word another block of the same launch writes.  (Separate in / out words with a commit point would
+// save a launch of ~2 us and need a second buffer whose roles swap per call: a replayed graph holds fixed addresses, so the swap
+// would have to be a device-side index, one more word to get wrong.)
+// Chan's means are kept relative to K, fixed for the life of the state: the first raw reward r[0, 0] of the first call on an empty
+// state (n = 0) -- the first sample ever where the carry starts at 0 --, kept in the state; x - K carries the rounding of the spread,
+// not of the offset (standardize_moments_kernel above).  `mean` is the plain sum over all samples / n and does not go through K.
+// No atomics; 4-byte loads in (1), whose sums have an order to keep; (3) has none and moves 16 bytes per lane where aligned.
+constexpr int RS_MAX_CHUNKS = STD_MAX_CHUNKS;          // slots of (2)'s merge tree
+constexpr int RS_STATE_WORDS = 8;                      // n, mean - K, M2, K, sum, mean, sigma, scale
+
+__device__ __forceinline__ StdMoments rs_shfl_down(const StdMoments a, const int off) {
+    return StdMoments{__shfl_down(a.n, off, 64), __shfl_down(a.sum, off, 64), __shfl_down(a.mean, off, 64), __shfl_down(a.m2, off, 64)};
+}
+
+__global__ __launch_bounds__(256) void reward_scale_scan_kernel(const int64_t S, const int N, const int T, const int64_t E,
+                                                                const float* __restrict__ r, const uint8_t* __restrict__ done_post,
+                                                                const double gamma, double* __restrict__ carry,
+                                                                const double* __restrict__ state, double* __restrict__ partial) {
+    const double K = state[0] > 0.0 ? state[3] : (double)r[0];
+    double cnt = 0.0, sum = 0.0, mean = 0.0, m2 = 0.0;             // Welford over this lane's samples (mean: of x - K)
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < S; s += stride) {
+        const int64_t e = N > 0 ? s / N : s;
+        double c = carry[s];
+        for (int t0 = 0; t0 < T; t0 += 4) {
+            float rv[4];
+            uint8_t dv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                          // the four steps' operands are requested before the first wait
+                const int t = t0 + k < T ? t0 + k : T - 1;
+                rv[k] = r[(int64_t)t * S + s];
+                dv[k] = done_post[(int64_t)t * E + e];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (t0 + k < T) {
+                    c = gamma * c + (double)rv[k];
+                    const double xk = c - K;
+                    cnt += 1.0;
+                    sum += c;
+                    const double d = xk - mean;
+                    mean += d / cnt;
+                    m2 += d * (xk - mean);
+                    if (dv[k]) c = 0.0;
+                }
+            }
+        }
+        carry[s] = c;
+    }
+    StdMoments a{cnt, sum, mean, m2};
+    for (int off = 32; off > 0; off >>= 1) a = std_merge(a, rs_shfl_down(a, off));      // (lanes off the end of the wave: self, unused)
+    __shared__ StdMoments sw[4];
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const StdMoments m = std_merge(std_merge(sw[0], sw[1]), std_merge(sw[2], sw[3]));
+        double* p = partial + (int64_t)blockIdx.x * 4;
+        p[0] = m.n; p[1] = m.sum; p[2] = m.mean; p[3] = m.m2;
+    }
+}
+
+__global__ __launch_bounds__(256) void reward_scale_merge_kernel(const int C, const float* __restrict__ r, const double eps,
+                                                                 const double* __restrict__ partial, double* __restrict__ state) {
+    const int tid = threadIdx.x;
+    __shared__ StdMoments sm[256];
+    {
+        StdMoments a{0.0, 0.0, 0.0, 0.0}, b{0.0, 0.0, 0.0, 0.0};
+        if (tid < C) a = StdMoments{partial[tid * 4], partial[tid * 4 + 1], partial[tid * 4 + 2], partial[tid * 4 + 3]};
+        if (tid + 256 < C)
+            b = StdMoments{partial[(tid + 256) * 4], partial[(tid + 256) * 4 + 1], partial[(tid + 256) * 4 + 2], partial[(tid + 256) * 4 + 3]};
+        sm[tid] = std_merge(a, b);
+    }
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) sm[tid] = std_merge(sm[tid], sm[tid + off]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const bool fresh = !(state[0] > 0.0);
+        const double K = fresh ? (double)r[0] : state[3];
+        const StdMoments prior = fresh ? StdMoments{0.0, 0.0, 0.0, 0.0} : StdMoments{state[0], state[4], state[1], state[2]};
+        const StdMoments m = std_merge(prior, sm[0]);
+        const double sigma = sqrt(m.m2 / m.n);
+        state[0] = m.n; state[1] = m.mean; state[2] = m.m2; state[3] = K; state[4] = m.sum;
+        state[5] = m.sum / m.n;
+        state[6] = sigma;
+        state[7] = sigma > 0.0 ? 1.0 / (sigma + eps) : 1.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void reward_scale_apply_kernel(const int64_t n, const float* __restrict__ r, const float clip,
+                                                                 const double* __restrict__ state, float* __restrict__ out) {
+    const double scale = state[7];
+#define NMARL_RS(v, o) { float y_ = (float)((double)(v) * scale); if (clip > 0.f) y_ = y_ < -clip ? -clip : (y_ > clip ? clip : y_); o = y_; }
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    if (((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+        const int64_t n4 = n >> 2;
+        const float4* r4 = reinterpret_cast<const float4*>(r);
+        float4* o4 = reinterpret_cast<float4*>(out);
+        for (int64_t i = i0; i < n4; i += stride) {
+            const float4 v = r4[i];
+            float4 o;
+            NMARL_RS(v.x, o.x) NMARL_RS(v.y, o.y) NMARL_RS(v.z, o.z) NMARL_RS(v.w, o.w)
+            o4[i] = o;
+        }
+        const int64_t i = (n4 << 2) + i0;
+        if (i < n) NMARL_RS(r[i], out[i])
+    } else {
+        for (int64_t i = i0; i < n; i += stride) NMARL_RS(r[i], out[i])
+    }
+#undef NMARL_RS
+}
+
 // A2C loss of Policy.prepare_loss (policies.py:20-30; NCMultiAgentPolicy 232-255) for all agents and rows:
 //   pi = softmax(logits); log_pi = log(clip(pi, 1e-10, 1)); H = -sum pi log_pi
 //   policy = -mean(log_pi[a] ADV);  value = 0.5 v_coef mean((R - v)^2);  entropy = -e_coef mean(H)
@@ -921,6 +1048,30 @@ extern "C" int nmarl_standardize(int32_t G, int64_t rows, const float* x, int64_
     hipLaunchKernelGGL(standardize_moments_kernel, dim3(C, G), dim3(256), 0, s, rows, per, x, x_sg, partial);
     hipLaunchKernelGGL(standardize_apply_kernel, dim3(C, G), dim3(256), 0, s, rows, per, x, x_sg, y, y_sg, eps,
                        (const double*)partial, moments);
+    return nmarl_check_launch();
+}
+
+// Blocks of nmarl_reward_scale's scan, the first extent of its `partial`: one lane per stream up to RS_MAX_CHUNKS blocks (131 072
+// streams), the streams behind that taken by the same lanes in a fixed grid-stride order.  A function of S alone, never of the device.
+extern "C" int nmarl_reward_scale_chunks(int64_t S) {
+    const int64_t c = (S + 255) / 256;
+    return c < 1 ? 1 : (c > RS_MAX_CHUNKS ? RS_MAX_CHUNKS : (int)c);
+}
+
+extern "C" int nmarl_reward_scale(int64_t E, int32_t N_or_0, int32_t T, const float* r_raw, const uint8_t* done_post, double gamma,
+                                  double eps, float clip, double* carry, double* state, double* partial, float* r_out, void* stream) {
+    if (E < 1 || E > (1ll << 40) || N_or_0 < 0 || N_or_0 > 64 || T < 1 || !(eps >= 0.0) || !(gamma >= 0.0 && gamma <= 1.0) || clip != clip)
+        return NMARL_EINVAL;                                                                                   // (NaN included)
+    if (!r_raw || !done_post || !carry || !state || !partial || !r_out) return NMARL_EINVAL;
+    const int64_t S = E * (N_or_0 > 0 ? N_or_0 : 1), n = S * T;
+    const int C = nmarl_reward_scale_chunks(S);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(reward_scale_scan_kernel, dim3(C), dim3(256), 0, s, S, (int)N_or_0, (int)T, E, r_raw, done_post, gamma, carry,
+                       (const double*)state, partial);
+    hipLaunchKernelGGL(reward_scale_merge_kernel, dim3(1), dim3(256), 0, s, C, r_raw, eps, (const double*)partial, state);
+    const int64_t blocks = (n / 4 + 255) / 256;
+    hipLaunchKernelGGL(reward_scale_apply_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(256), 0, s, n,
+                       r_raw, clip, (const double*)state, r_out);
     return nmarl_check_launch();
 }
 

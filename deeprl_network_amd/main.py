@@ -43,6 +43,10 @@ def parse_args(argv=None):
                     help='per-batch standardisation of the advantage in the policy-gradient term (overrides MODEL_CONFIG adv_norm; '
                          'default none).  agent: zero mean and unit std per agent; all: over all agents together.  The critic\'s '
                          'target is not touched (MODEL_CONFIG adv_norm_epsilon, default 1e-8, is added to the std)')
+    sp.add_argument('--reward-scale', choices=('none', 'return'), default=None,
+                    help='scale of the training rewards (overrides MODEL_CONFIG reward_scale; default none = raw / reward_norm).  '
+                         'return: divide by the running std of the discounted return over everything seen so far, in place of '
+                         'reward_norm (MODEL_CONFIG reward_scale_epsilon, default 1e-8, is added to the std); evaluation is untouched')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -82,12 +86,13 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm), set on every rank;
-    run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale), set
+    on every rank; run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
     given = {'lstm_precision': args.lstm_precision,
              'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
              'optimizer': args.optimizer,
-             'adv_norm': args.adv_norm}
+             'adv_norm': args.adv_norm,
+             'reward_scale': getattr(args, 'reward_scale', None)}
     given = {k: v for k, v in given.items() if v is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)

@@ -1892,6 +1892,34 @@ def standardize(x, eps, out=None, partial=None, moments=None):
     return out
 
 
+REWARD_SCALE_STATE = 8          # float64 words of reward_scale's `state`: n, mean - K, M2, K, sum, mean, sigma, scale
+
+
+def reward_scale_chunks(S):
+    """Blocks of `reward_scale`'s scan (the first extent of its `partial`): a function of the number of streams alone."""
+    return int(lib.nmarl_reward_scale_chunks(int(S)))
+
+
+def reward_scale(r_raw, done_post, gamma, eps, clip, carry, state, partial, out):
+    """Running return-based reward scaling (opt-in): r_raw [T,E] | [T,E,N] fp32 and done_post [T,E] u8 advance the
+    discounted return `carry` (float64 [E] | [E*N]) and the pooled running moments in `state` (float64 [REWARD_SCALE_STATE]);
+    out = r_raw / (std of all returns seen so far, this batch included, + eps), clamped to +-clip where clip > 0.  partial:
+    float64 [reward_scale_chunks(S), 4] scratch.  Three launches, no allocation, no synchronisation; carry and state are zero before
+    the first call and stay on the device."""
+    T, E = done_post.shape
+    N = 0 if r_raw.dim() == 2 else r_raw.shape[2]
+    S = E * max(N, 1)
+    if tuple(r_raw.shape[:2]) != (T, E) or out.shape != r_raw.shape or (r_raw.dim() == 3 and N < 1):
+        raise ValueError('reward_scale: r_raw and out must be [T,E] or [T,E,N] like done_post [T,E]')
+    if carry.numel() < S or state.numel() < REWARD_SCALE_STATE or partial.numel() < 4 * reward_scale_chunks(S):
+        raise ValueError('reward_scale: carry needs [%d], state [%d] and partial [%d, 4] float64'
+                         % (S, REWARD_SCALE_STATE, reward_scale_chunks(S)))
+    check(lib.nmarl_reward_scale(E, N, T, ptr(r_raw, F32), ptr(done_post, torch.uint8), float(gamma), float(eps), float(clip),
+                                 ptr(carry, torch.float64), ptr(state, torch.float64), ptr(partial, torch.float64), ptr(out, F32),
+                                 stream()), 'nmarl_reward_scale')
+    return out
+
+
 _epilogue_scratch = {}
 
 

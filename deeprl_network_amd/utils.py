@@ -234,6 +234,8 @@ class Trainer:
         self.data.append(dict(agent=self.agent, step=at, test_id=-1, avg_reward=mean, std_reward=std))
         if self.summary_writer is not None:
             self.summary_writer.add_scalar('train_reward', mean, at)
+            if getattr(self.model, 'reward_scale', 'none') != 'none':     # (this path synchronises every lock-step anyway)
+                self.summary_writer.add_scalar('train/reward_scale_std', self.model.reward_scale_std, at)
             self.summary_writer.flush()
 
     def run(self):
@@ -463,11 +465,19 @@ class BatchedTrainer:
     def _shadow_tensors(self):
         """What a rollout overwrites and the batch epilogue does not restore: the env, the Philox counter, the persistent
         recurrent state (its bootstrap step advances it, Q2)."""
-        return self.env.state_tensors() + [self.step_dev, self.model.h_fw, self.model.c_fw]
+        return self.env.state_tensors() + [self.step_dev, self.model.h_fw, self.model.c_fw] + self._reward_scale_tensors()
 
     def _state_tensors(self):
         m = self.model
-        return self.env.state_tensors() + [m.h_fw, m.c_fw, m.buf_x[0], m.buf_fp[0], self.step_dev, self.done_pre]
+        return self.env.state_tensors() + [m.h_fw, m.c_fw, m.buf_x[0], m.buf_fp[0], self.step_dev, self.done_pre] + \
+            self._reward_scale_tensors()
+
+    def _reward_scale_tensors(self):
+        """Opt-in reward_scale = return: the carried discounted returns and the running moments, which every update advances whether
+        or not its optimiser step is refused -- a refused batch and its re-run start from the statistics the refused batch started
+        from.  Empty with the key absent."""
+        m = self.model
+        return [m.rs_carry, m.rs_state] if getattr(m, 'reward_scale', 'none') != 'none' else []
 
     def _snapshot(self):
         return [t.clone() for t in self._state_tensors()]
@@ -790,6 +800,8 @@ class BatchedTrainer:
                                 st['avg_reward'], row['avg_reward'], st['collisions']))
                 if self.summary_writer is not None:
                     self.summary_writer.add_scalar('train_reward', row['avg_reward'], step)
+                    if getattr(self.model, 'reward_scale', 'none') != 'none':     # (the host synchronised above: one more read)
+                        self.summary_writer.add_scalar('train/reward_scale_std', self.model.reward_scale_std, step)
                     self.summary_writer.flush()
 
         while not self.global_counter.should_stop():

@@ -1053,6 +1053,36 @@ int nmarl_standardize(int32_t G, int64_t rows, const float* x, int64_t x_sg, flo
                       double* partial /* [G, chunks, 3] */, double* moments /* [G, 2] = (mu, sigma), may be NULL */, void* stream);
 
 /*
+ * Opt-in running return-based reward scaling (MODEL_CONFIG reward_scale = return; the reference has none): rewards are divided by
+ * the running standard deviation of the discounted return.  r_raw, r_out: [T, E] fp32 (N_or_0 = 0, the global reward) or [T, E, N]
+ * (N_or_0 = N, per-agent rewards), dense; a stream is one reward sequence, s = e or s = e N + i, S = E or E N of them; done_post
+ * [T, E] bytes.  Persistent, device-resident, float64, owned by the caller and zero before the first call: carry [S] and
+ * state [NMARL_REWARD_SCALE_STATE].  One call, everything in float64:
+ *     for t = 0 .. T-1, every s:  carry[s] = gamma carry[s] + r_raw[t, s];  the sample is carry[s];
+ *                                 if done_post[t, e]: carry[s] = 0                        (after the sample is taken)
+ *     (n, mean, M2) <- the moments of all samples seen so far merged with the T S of this call     (population moments)
+ *     sigma = sqrt(M2 / n);  scale = sigma > 0 ? 1 / (sigma + eps) : 1                             (eps OUTSIDE the root)
+ *     r_out[t, s] = fp32(double(r_raw[t, s]) scale)                                                (one rounding)
+ *     clip > 0: r_out is clamped to +-clip, afterwards
+ * The moments include the call's own samples before anything is scaled; the mean is tracked, not subtracted; one pooled scale for
+ * all streams.  state = (n, mean - K, M2, K, sum, mean, sigma, scale): K, the point Chan's formula keeps its means relative to, is
+ * r_raw[0, 0] of the first call on an empty state (n = 0), the first sample ever where carry starts at 0; mean = sum / n.
+ * Three launches, kernel nodes only (no memset, no memcpy, no atomics, no host synchronisation: capturable, and a replayed graph
+ * advances the state; two runs from the same state give the same bits): a scan with one lane per stream -- Welford per lane, lanes
+ * -> waves -> block merged by Chan's formula in a fixed order, one (n, sum, mean - K, M2) per block into partial [chunks, 4] --, a
+ * ONE-block launch that merges the partials and the prior state in a fixed tree and is the only writer of `state`, and the pass
+ * that writes r_out.  chunks = nmarl_reward_scale_chunks(S) = min(ceil(S / 256), 512): a function of S alone; streams behind
+ * 256 x 512 are taken by the same lanes in ascending grid-stride order.  r_out must not overlap r_raw.
+ * NMARL_EINVAL (nothing written, nothing launched): E < 1, N_or_0 outside 0..64, T < 1, eps < 0, gamma outside [0, 1], a NaN in
+ * eps / gamma / clip, a null pointer.
+ */
+#define NMARL_REWARD_SCALE_STATE 8
+int nmarl_reward_scale_chunks(int64_t S);
+int nmarl_reward_scale(int64_t E, int32_t N_or_0, int32_t T, const float* r_raw, const uint8_t* done_post, double gamma, double eps,
+                       float clip, double* carry /* [S] */, double* state /* [NMARL_REWARD_SCALE_STATE] */,
+                       double* partial /* [chunks, 4] */, float* r_out, void* stream);
+
+/*
  * Between two n_step batches of the batched loop (two launches instead of ~45 elementwise ones):
  *  - episode statistics as Trainer.run keeps them (utils.py:228-229: mean / std of an episode's global rewards): g [T][E]
  *    the batch's global rewards, done [E] u8 the flags of its last lock-step; per replica running ep_sum / ep_sq / ep_len
