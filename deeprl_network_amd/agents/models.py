@@ -18,7 +18,9 @@ Engine (per n_step batch, E replicas, N agents):
             discounted return) -> nmarl_nstep_return (opt-in gae_lambda < 1: nmarl_gae_return) [-> opt-in adv_norm: nmarl_standardize, the policy term's
             advantage per agent / over all agents to zero mean and unit std] -> autograd unroll -> A2C loss (policies.py:20-30,
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
-            nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip).
+            nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip)
+            [-> opt-in ppo_epochs = K > 1: K - 1 more steps on the same batch, each the forward pass recomputed -> clipped surrogate
+            against the behaviour policy's log-probabilities (nmarl_ppo_logp, nmarl_ppo_loss_*) -> all-reduce -> optimiser].
 """
 import logging
 import os
@@ -112,6 +114,27 @@ class IA2C:
         if self.reward_scale != 'none':
             logging.info('reward_scale = %s: rewards are divided by the running std of the discounted return; reward_norm = %r '
                          'is not applied' % (self.reward_scale, self.reward_norm))
+        # optional (absent: 1 = one optimiser step per batch, as before): K > 1 makes K optimiser steps on every batch -- the first is the
+        # A2C step as it is, epochs 2..K recompute the forward pass with the current weights and apply the clipped surrogate
+        # (ops.ppo_loss) against the log-probabilities of the weights that produced the batch; ppo_clip is its epsilon
+        raw = model_config.get('ppo_epochs', fallback='1').strip()
+        try:
+            self.ppo_epochs = int(raw)
+        except ValueError:
+            raise ValueError('ppo_epochs = %r: must be an integer >= 1' % raw)
+        if self.ppo_epochs < 1:
+            raise ValueError('ppo_epochs = %r: must be an integer >= 1' % raw)
+        self.ppo_clip = model_config.getfloat('ppo_clip', fallback=0.2)
+        if not 0.0 < self.ppo_clip < float('inf'):           # (nan fails both comparisons)
+            raise ValueError('ppo_clip = %r: must be finite and > 0' % self.ppo_clip)
+        if self.ppo_epochs > 1:
+            if self.policy_cls.coupled:
+                # (as they refuse bf16x3) their in-launch hand-off guard and refused-batch rewind assume one optimiser step per batch
+                raise ValueError('ppo_epochs = %d: not available for the coupled net %s (one optimiser step per batch)'
+                                 % (self.ppo_epochs, self.policy_cls.name))
+            if self.lstm_precision == 'bf16x3':
+                raise ValueError('ppo_epochs = %d with lstm_precision = bf16x3: epochs >= 2 recompute the forward pass in fp32, the '
+                                 'ratio would not start at 1' % self.ppo_epochs)
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -237,6 +260,11 @@ class IA2C:
             self._rs_partial = torch.zeros(ops.reward_scale_chunks(S), 4, dtype=torch.float64, device=d)
             self._rs_raw = torch.zeros_like(self.buf_r)
             self._rs_pending = False
+        if self.ppo_epochs > 1:
+            # opt-in: the behaviour policy's log-probabilities of the actions taken (taken before the batch's first optimiser step)
+            # and per epoch and agent (approx_kl, clip_frac) of the last update -- row 0, the A2C step, stays zero
+            self.ppo_logp_old = torch.zeros(N, T * E, dtype=F32, device=d)
+            self.ppo_stats = torch.zeros(self.ppo_epochs, N, 2, dtype=F32, device=d)
         self.dist_dev = torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
@@ -601,11 +629,18 @@ class IA2C:
         """model.backward (models.py:34-42 / 211-215) for all replicas: R_end [N,E].  rotate=False: the caller hands the
         states / slot T of the rollout buffers over to the next batch itself (BatchedTrainer: ops.batch_epilogue).
         = the four phases below back to back; BatchedTrainer captures `update_grads` and `update_apply` in hipGraphs and
-        replays them around the (eager) gradient exchange, calling the two host-only phases itself."""
+        replays them around the (eager) gradient exchange, calling the two host-only phases itself.
+        Opt-in ppo_epochs = K > 1: K - 1 further {update_ppo_grads, update_reduce, update_apply} on the same batch, `rotate` honoured
+        on the last step only."""
         lr = self.update_begin()
+        K = self.ppo_epochs
         self.update_grads(R_end)
         self.update_reduce()
-        self.update_apply(lr, rotate=rotate)
+        self.update_apply(lr, rotate=rotate and K == 1)
+        for k in range(2, K + 1):         # opt-in PPO epochs: the same batch, returns, advantages and lr; one all-reduce per step
+            self.update_ppo_grads(k)
+            self.update_reduce()
+            self.update_apply(lr, rotate=rotate and k == K)
         self.update_end()
 
     def update_begin(self):
@@ -659,6 +694,8 @@ class IA2C:
                                           self.buf_done_pre, masked_steps=self.masked_steps, S_ext=self.S_ext, **kw)
         else:
             Hs = self.policy.unroll(X, FP, self.buf_done_pre, self.h_bw, self.c_bw, masked_steps=self.masked_steps)
+        if self.ppo_epochs > 1:          # opt-in: the behaviour policy's log-probabilities, from the hidden states this epoch's loss reads
+            self._take_logp_old(Hs)
         if not self._loss_backward_fused(Hs):
             loss = self._loss(Hs)
             loss.backward()
@@ -669,6 +706,75 @@ class IA2C:
             # a rank whose in-launch hand-off timed out contributes invalid gradients: every rank must refuse the step (and recover
             # in lock-step, BatchedTrainer).  The status word rides in the float behind the gradient, inside the ONE all-reduce
             ps.grad_tail.copy_(ops.handoff_status(self.device)[:1])           # (int32 -> f32: an element-wise kernel)
+
+    # ------------------------------------------------------------------ opt-in PPO epochs (MODEL_CONFIG ppo_epochs > 1)
+    def _loss_adv(self):
+        """The advantage the policy term reads, [N,T*E] (with quirk Q6 of `_loss` on heterogeneous one-optimiser nets)."""
+        N, T, E = self.n_agent, self.n_step, self.E
+        adv = self._policy_adv().view(N, T * E)
+        if not self.identical_agent and not self.per_agent_optimizer:
+            adv = adv.sum(dim=0, keepdim=True).expand(N, T * E).contiguous()
+        return adv
+
+    def _take_logp_old(self, Hs):
+        """ppo_logp_old = log(clip(softmax(logits_old)[a], 1e-10, 1)) of the actions taken, with the weights that produced the batch
+        (called before the batch's first optimiser step; the clamp is the loss's)."""
+        N, T, E = self.n_agent, self.n_step, self.E
+        action = self.buf_act.view(T * E, N)
+        with torch.no_grad():
+            logits, _ = self.policy.heads(Hs.detach(), action)
+            if ops.ppo_loss_supported(self.n_a):
+                ops.ppo_logp(logits, action, out=self.ppo_logp_old)
+            else:
+                log_pi = torch.log(torch.clamp(torch.softmax(logits, dim=-1), 1e-10, 1.0))
+                self.ppo_logp_old.copy_(log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1))
+
+    def update_ppo_grads(self, k):
+        """Epoch k = 2..K of an update up to the flat gradient: the forward pass recomputed with the current weights from the state
+        the batch started from, the heads, the clipped surrogate against ppo_logp_old, backward.  R, Adv and the policy term's
+        advantage are those of `update_grads`.  Capturable like it."""
+        assert 2 <= k <= self.ppo_epochs
+        N, T, E = self.n_agent, self.n_step, self.E
+        p = self.policy
+        ps = p.params
+        ps.begin_backward()
+        FP = self.buf_fp[:T].permute(1, 0, 2, 3).reshape(N, T * E, self.n_a)
+        Hs = p.unroll(self.buf_x[:T], FP, self.buf_done_pre, self.h_bw, self.c_bw, masked_steps=self.masked_steps)
+        action = self.buf_act.view(T * E, N)
+        logits, v = p.heads(Hs, action)
+        adv, R, eps = self._loss_adv(), self.R.view(N, T * E), self.ppo_clip
+        if ops.ppo_loss_supported(self.n_a):
+            per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef)
+        else:
+            pi = torch.softmax(logits, dim=-1)
+            log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
+            entropy = -(pi * log_pi).sum(-1)
+            dlp = log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1) - self.ppo_logp_old
+            rho = torch.exp(dlp)
+            policy_loss = -torch.min(rho * adv, torch.clamp(rho, 1.0 - eps, 1.0 + eps) * adv).mean(-1)
+            value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
+            entropy_loss = -entropy.mean(-1) * self.e_coef
+            per_agent = policy_loss + value_loss + entropy_loss
+            with torch.no_grad():
+                terms = torch.stack([policy_loss, value_loss, entropy_loss, (torch.expm1(dlp) - dlp).clamp_min(0.0).mean(-1),
+                                     ((rho - 1.0).abs() > eps).to(F32).mean(-1)], dim=1)
+        self.ppo_stats[k - 1].copy_(terms[:, 3:5])
+        t3 = self._terms = terms[:, :3].contiguous()
+        self.last_loss = (t3[:, 0], t3[:, 1], t3[:, 2], per_agent.detach())
+        per_agent.sum().backward()
+        ps.end_backward()
+        if ps.mask is not None:
+            ps.grad.mul_(ps.mask)
+
+    @property
+    def ppo_kl(self):
+        """approx_kl of the last update's last epoch, mean over agents (host read: synchronises); None with the key off."""
+        return None if self.ppo_epochs == 1 or not hasattr(self, 'ppo_stats') else float(self.ppo_stats[-1, :, 0].mean())
+
+    @property
+    def ppo_clip_frac(self):
+        """clip_frac of the last update's last epoch, mean over agents (host read: synchronises); None with the key off."""
+        return None if self.ppo_epochs == 1 or not hasattr(self, 'ppo_stats') else float(self.ppo_stats[-1, :, 1].mean())
 
     @property
     def _status_on_wire(self):

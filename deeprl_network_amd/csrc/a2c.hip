@@ -887,6 +887,127 @@ __global__ __launch_bounds__(64) void a2c_loss_reduce_kernel(const int C, const 
     out[n * 3 + k] = k == 0 ? s : k == 1 ? s * 0.5f * v_coef : -s * e_coef;
 }
 
+// Opt-in PPO epochs (MODEL_CONFIG ppo_epochs > 1; the reference has none): the clipped surrogate against the behaviour policy's
+// log-probabilities logp_old [N,rows], for epochs 2..K of an update.  Softmax, clamp and entropy are a2c_loss_kernel's, in its
+// operation order, so that at logp_old = lp_a (rho = 1.0f exactly) the gradient has the bits of the A2C one.
+//   rho = exp(lp_a - logp_old);  policy = -mean(min(rho ADV, clip(rho, 1-eps, 1+eps) ADV));  value, entropy: as above
+//   approx_kl = mean((rho - 1) - (lp_a - logp_old));  clip_frac = mean(|rho - 1| > eps)
+//   d policy / d logit_k = -ADV rho gate c_a (delta_ka - pi_k);  gate = 0 where (ADV > 0, rho > 1+eps) or (ADV < 0, rho < 1-eps)
+__device__ __forceinline__ void loss_row_softmax(const float* __restrict__ l, const int A, const int a, float (&p)[LOSS_MAXA],
+                                                 float (&lp)[LOSS_MAXA], float& H, float& lpa, float& pa) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXA; ++k) {
+        p[k] = k < A ? l[k] : -INFINITY;
+        m = fmaxf(m, p[k]);
+    }
+    float z = 0.0f;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXA; ++k) {
+        p[k] = k < A ? expf(p[k] - m) : 0.0f;
+        z += p[k];
+    }
+    H = 0.0f; lpa = 0.0f; pa = 0.0f;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXA; ++k) {
+        p[k] = p[k] / z;
+        lp[k] = logf(fminf(fmaxf(p[k], 1e-10f), 1.0f));
+        if (k < A) H -= p[k] * lp[k];
+        if (k == a) { lpa = lp[k]; pa = p[k]; }
+    }
+}
+
+// logp_out[n, r] = log(clip(softmax(logits[n, r])[action[r, n]], 1e-10, 1)): one thread per row
+__global__ __launch_bounds__(256) void ppo_logp_kernel(const int64_t rows, const int N, const int A, const float* __restrict__ logits,
+                                                       const int64_t l_sn, const int64_t l_row, const uint8_t* __restrict__ action,
+                                                       float* __restrict__ logp_out) {
+    const int n = blockIdx.y;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    float p[LOSS_MAXA], lp[LOSS_MAXA], H, lpa, pa;
+    loss_row_softmax(logits + (int64_t)n * l_sn + r * l_row, A, action[r * N + n], p, lp, H, lpa, pa);
+    logp_out[(int64_t)n * rows + r] = lpa;
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const int N, const int A, const int rows_per_block,
+                                                       const float* __restrict__ logits, const int64_t l_sn, const int64_t l_row,
+                                                       const float* __restrict__ v, const uint8_t* __restrict__ action,
+                                                       const float* __restrict__ adv, const float* __restrict__ R,
+                                                       const float* __restrict__ logp_old, const float clip, const float v_coef,
+                                                       const float e_coef, const float* __restrict__ g_up,
+                                                       float* __restrict__ partial, float* __restrict__ dlogits,
+                                                       float* __restrict__ dv) {
+    const int n = blockIdx.y;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    const float inv_m = 1.0f / (float)rows;
+    const float gn = BWD ? g_up[n] * inv_m : 0.0f;
+    const float lo_c = 1.0f - clip, hi_c = 1.0f + clip;
+    float s_pol = 0.0f, s_val = 0.0f, s_ent = 0.0f, s_kl = 0.0f, s_cf = 0.0f;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
+        const int a = action[r * N + n];
+        float p[LOSS_MAXA], lp[LOSS_MAXA], H, lpa, pa;
+        loss_row_softmax(logits + (int64_t)n * l_sn + r * l_row, A, a, p, lp, H, lpa, pa);
+        const int64_t i = (int64_t)n * rows + r;
+        const float ad = adv[i], dR = R[i] - v[i];
+        const float dlp = lpa - logp_old[i];
+        const float rho = expf(dlp);
+        if (!BWD) {
+            s_pol -= fminf(rho * ad, fminf(fmaxf(rho, lo_c), hi_c) * ad);
+            s_val += dR * dR;
+            s_ent += H;
+            // (rho - 1) - log rho >= 0; rho - 1 taken as expm1 of the difference: expf's rounding (6e-8) would swamp a term of d^2 / 2
+            s_kl += fmaxf(expm1f(dlp) - dlp, 0.0f);
+            s_cf += fabsf(rho - 1.0f) > clip ? 1.0f : 0.0f;
+        } else {
+            // the clipped branch is the smaller one, and constant in rho, exactly where the gate closes
+            const bool closed = (ad > 0.0f && rho > hi_c) || (ad < 0.0f && rho < lo_c);
+            const float adg = ad * (closed ? 0.0f : rho);          // rho = 1.0f: ad itself, and from here on a2c_loss_kernel's lines
+            float gbar = 0.0f;
+#pragma unroll
+            for (int k = 0; k < LOSS_MAXA; ++k)
+                if (k < A) gbar += p[k] * -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
+            const float ca = pa >= 1e-10f ? 1.0f : 0.0f;
+            float* dl = dlogits + i * A;
+#pragma unroll
+            for (int k = 0; k < LOSS_MAXA; ++k)
+                if (k < A) {
+                    const float gk = -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
+                    const float d_pol = -adg * ca * ((k == a ? 1.0f : 0.0f) - p[k]);
+                    const float d_ent = -e_coef * p[k] * (gk - gbar);
+                    dl[k] = gn * (d_pol + d_ent);
+                }
+            dv[i] = -gn * v_coef * dR;
+        }
+    }
+    if (!BWD) {
+        __shared__ float red[4][5];
+        for (int off = 32; off > 0; off >>= 1) {
+            s_pol += __shfl_down(s_pol, off, 64);
+            s_val += __shfl_down(s_val, off, 64);
+            s_ent += __shfl_down(s_ent, off, 64);
+            s_kl += __shfl_down(s_kl, off, 64);
+            s_cf += __shfl_down(s_cf, off, 64);
+        }
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        if (lane == 0) { red[w][0] = s_pol; red[w][1] = s_val; red[w][2] = s_ent; red[w][3] = s_kl; red[w][4] = s_cf; }
+        __syncthreads();
+        if (threadIdx.x < 5)
+            partial[((int64_t)n * gridDim.x + blockIdx.x) * 5 + threadIdx.x] =
+                ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+}
+
+__global__ __launch_bounds__(64) void ppo_loss_reduce_kernel(const int C, const int64_t rows, const float v_coef, const float e_coef,
+                                                             const float* __restrict__ partial, float* __restrict__ out /*[N,5]*/) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    if (k >= 5) return;
+    float s = nmarl_ordered_sum(partial + (int64_t)n * C * 5 + k, 5, C);
+    s /= (float)rows;
+    out[n * 5 + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
+}
+
 inline int grid_x(int64_t n, int cap = 2048) {
     int64_t b = (n + 255) / 256;
     return (int)(b < cap ? (b > 0 ? b : 1) : cap);
@@ -1107,6 +1228,47 @@ extern "C" int nmarl_a2c_loss_bwd(int64_t rows, int32_t N, int32_t A, const floa
     const int rpb = (int)((rows + C - 1) / C);
     hipLaunchKernelGGL(a2c_loss_kernel<true>, dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb, logits,
                        l_sn, l_row, v, action, adv, R, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_logp(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                              const uint8_t* action, float* logp_out, void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !action || !logp_out) return NMARL_EINVAL;
+    hipLaunchKernelGGL(ppo_logp_kernel, dim3((unsigned)((rows + 255) / 256), N), dim3(256), 0, static_cast<hipStream_t>(stream), rows,
+                       N, A, logits, l_sn, l_row, action, logp_out);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_loss_chunks(int64_t rows, int32_t N) { return rows > 0 && N > 0 ? loss_chunks(rows, N) : 0; }
+
+static bool ppo_clip_ok(float clip) { return clip > 0.0f && clip <= 3.402823466e+38f; }      // (NaN fails both, inf the second)
+
+extern "C" int nmarl_ppo_loss_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                                  const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
+                                  float clip, float v_coef, float e_coef, float* partial, float* loss_out, void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
+        !partial || !loss_out || !ppo_clip_ok(clip))
+        return NMARL_EINVAL;
+    const int C = loss_chunks(rows, N);
+    const int rpb = (int)((rows + C - 1) / C);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(ppo_loss_kernel<false>, dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action, adv, R,
+                       logp_old, clip, v_coef, e_coef, (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL(ppo_loss_reduce_kernel, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, partial, loss_out);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                                  const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
+                                  float clip, float v_coef, float e_coef, const float* g_up, float* dlogits, float* dv,
+                                  void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
+        !g_up || !dlogits || !dv || !ppo_clip_ok(clip))
+        return NMARL_EINVAL;
+    const int C = loss_chunks(rows, N);
+    const int rpb = (int)((rows + C - 1) / C);
+    hipLaunchKernelGGL(ppo_loss_kernel<true>, dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb, logits,
+                       l_sn, l_row, v, action, adv, R, logp_old, clip, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv);
     return nmarl_check_launch();
 }
 

@@ -47,6 +47,12 @@ def parse_args(argv=None):
                     help='scale of the training rewards (overrides MODEL_CONFIG reward_scale; default none = raw / reward_norm).  '
                          'return: divide by the running std of the discounted return over everything seen so far, in place of '
                          'reward_norm (MODEL_CONFIG reward_scale_epsilon, default 1e-8, is added to the std); evaluation is untouched')
+    sp.add_argument('--ppo-epochs', type=int, default=None,
+                    help='optimiser steps per batch (overrides MODEL_CONFIG ppo_epochs; default 1 = one A2C step).  K > 1: the first '
+                         'step is the A2C step, steps 2..K recompute the forward pass and apply the clipped surrogate against the '
+                         'policy that produced the batch; IA2C / IA2C-FP / ConseNet only, fp32 only')
+    sp.add_argument('--ppo-clip', type=float, default=None,
+                    help='epsilon of the clipped surrogate (overrides MODEL_CONFIG ppo_clip; default 0.2; finite and > 0)')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -86,13 +92,15 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale), set
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale, --ppo-epochs, --ppo-clip), set
     on every rank; run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
     given = {'lstm_precision': args.lstm_precision,
              'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
              'optimizer': args.optimizer,
              'adv_norm': args.adv_norm,
-             'reward_scale': getattr(args, 'reward_scale', None)}
+             'reward_scale': getattr(args, 'reward_scale', None),
+             'ppo_epochs': None if getattr(args, 'ppo_epochs', None) is None else str(args.ppo_epochs),
+             'ppo_clip': None if getattr(args, 'ppo_clip', None) is None else repr(args.ppo_clip)}
     given = {k: v for k, v in given.items() if v is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)

@@ -1816,6 +1816,64 @@ def a2c_loss(logits, v, action, adv, R, v_coef, e_coef):
     return _A2CLoss.apply(logits, v, action, adv, R, float(v_coef), float(e_coef))
 
 
+def ppo_loss_supported(n_a):
+    return n_a <= A2C_LOSS_MAX_A
+
+
+def ppo_logp(logits, action, out=None):
+    """logits [N,rows,A] (any row pitch), action [rows,N] u8 -> log(clip(softmax(logits)[a], 1e-10, 1)) [N,rows]: the behaviour
+    policy's log-probabilities of the opt-in PPO epochs, with ops.a2c_loss's softmax / clamp arithmetic (no autograd)."""
+    N, rows, A = logits.shape
+    logits = logits.detach()
+    if logits.stride(2) != 1:
+        logits = logits.contiguous()
+    if out is None:
+        out = torch.empty(N, rows, dtype=F32, device=logits.device)
+    check(lib.nmarl_ppo_logp(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1),
+                             ptr(action, torch.uint8), ptr(out, F32), stream()), 'nmarl_ppo_logp')
+    return out
+
+
+class _PPOLoss(torch.autograd.Function):
+    """(total [N], terms [N,5]) = per-agent (policy, value, entropy, approx_kl, clip_frac) of the clipped surrogate against
+    logp_old [N,rows]; everything else as _A2CLoss (total = the first three terms): one streaming pass forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, logits, v, action, adv, R, logp_old, clip, v_coef, e_coef):
+        N, rows, A = logits.shape
+        if logits.stride(2) != 1:
+            logits = logits.contiguous()
+        v, adv, R, logp_old = v.contiguous(), adv.contiguous(), R.contiguous(), logp_old.contiguous()
+        C_ = lib.nmarl_ppo_loss_chunks(rows, N)
+        partial = torch.empty(N, C_, 5, dtype=F32, device=logits.device)
+        out = torch.empty(N, 5, dtype=F32, device=logits.device)
+        check(lib.nmarl_ppo_loss_fwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
+                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32), clip, v_coef, e_coef,
+                                     ptr(partial), ptr(out), stream()), 'nmarl_ppo_loss_fwd')
+        ctx.save_for_backward(logits, v, action, adv, R, logp_old)
+        ctx.coefs = (clip, v_coef, e_coef)
+        ctx.mark_non_differentiable(out)
+        return out[:, :3].sum(dim=1), out
+
+    @staticmethod
+    def backward(ctx, g, _):
+        logits, v, action, adv, R, logp_old = ctx.saved_tensors
+        N, rows, A = logits.shape
+        gn = g.contiguous()
+        dlogits = torch.empty(N, rows, A, dtype=F32, device=logits.device)
+        dv = torch.empty(N, rows, dtype=F32, device=logits.device)
+        check(lib.nmarl_ppo_loss_bwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
+                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32), ctx.coefs[0],
+                                     ctx.coefs[1], ctx.coefs[2], ptr(gn, F32), ptr(dlogits), ptr(dv), stream()), 'nmarl_ppo_loss_bwd')
+        return dlogits, dv, None, None, None, None, None, None, None
+
+
+def ppo_loss(logits, v, action, adv, R, logp_old, clip, v_coef, e_coef):
+    """-> per-agent total loss [N] (differentiable; policy + value + entropy) and the detached (policy, value, entropy, approx_kl,
+    clip_frac) terms [N,5] of the clipped surrogate with ratio exp(log_pi[a] - logp_old)."""
+    return _PPOLoss.apply(logits, v, action, adv, R, logp_old, float(clip), float(v_coef), float(e_coef))
+
+
 def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, adv_out=None):
     """r [T,E] | [T,E,N], v [T,N,E], done_post [T,E] u8, R_end [N,E] -> R, Adv [N,T,E]."""
     T, N, E = v.shape

@@ -103,6 +103,15 @@ class SummaryWriter:
         self._rows = []
 
 
+def _write_ppo_scalars(writer, model, step):
+    """Opt-in ppo_epochs > 1: approx_kl and clip_frac of the last update's last epoch (mean over agents; two host reads where the
+    caller has synchronised already).  Nothing with the key absent."""
+    if getattr(model, 'ppo_epochs', 1) > 1:
+        name = model.policy.summary_name
+        writer.add_scalar('train/%s_ppo_kl' % name, model.ppo_kl, step)
+        writer.add_scalar('train/%s_ppo_clipfrac' % name, model.ppo_clip_frac, step)
+
+
 # ------------------------------------------------------------------ the E = 1 driver behind the reference's Trainer surface
 class _Decision:
     """What all agents decided at one lock-step: the policies pi, the drawn (or arg-max) actions, the critic values and the
@@ -236,6 +245,7 @@ class Trainer:
             self.summary_writer.add_scalar('train_reward', mean, at)
             if getattr(self.model, 'reward_scale', 'none') != 'none':     # (this path synchronises every lock-step anyway)
                 self.summary_writer.add_scalar('train/reward_scale_std', self.model.reward_scale_std, at)
+            _write_ppo_scalars(self.summary_writer, self.model, at)
             self.summary_writer.flush()
 
     def run(self):
@@ -505,7 +515,10 @@ class BatchedTrainer:
     def _capture_update(self):
         """Capture the update of a batch as hipGraphs (after at least one eager batch: the library GEMMs are tuned, every
         lazily built table and workspace exists).  One graph [rewards, returns, loss, backward, clip + RMSProp, epilogue];
-        with several ranks two, around the eager gradient all-reduce.  Capturing runs no kernel; the host-side state the
+        with several ranks two, around the eager gradient all-reduce.  Under the opt-in ppo_epochs = K > 1 the one graph goes on
+        with {update_ppo_grads(k), update_apply} for k = 2..K in front of the record; with several ranks it is a chain of K + 1
+        graphs split at every all-reduce, [grads 1] [apply k | grads k+1] .. [apply K | record | epilogue] (`_upd['chain']` holds
+        the K - 1 in the middle; with K = 1 `_upd` has the keys of before).  Capturing runs no kernel; the host-side state the
         captured Python code touches is put back."""
         m = self.model
         split = m.dist_group is not None
@@ -522,16 +535,26 @@ class BatchedTrainer:
         ops.keepalive_begin(self._keepalive)
         try:
             torch.cuda.synchronize()
-            g1, g2 = self._new_graph(), None
+            K = getattr(m, 'ppo_epochs', 1)
+            g1, g2, chain = self._new_graph(), None, []
             with torch.cuda.graph(g1):
                 m.load_rewards(self.buf_rraw)
                 m.update_grads(self.R_end)
                 if not split:
                     m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
+                    for k in range(2, K + 1):          # opt-in PPO epochs: the same graph goes on with {grads k, apply}
+                        m.update_ppo_grads(k)
+                        m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
                     self._record(0.0, lr_dev=self.lr_dev)
                     if inside:
                         self._epilogue()
             if split:
+                for k in range(2, K + 1):              # [apply k-1 | grads k]: one graph between every two all-reduces
+                    g = self._new_graph()
+                    with torch.cuda.graph(g):
+                        m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
+                        m.update_ppo_grads(k)
+                    chain.append(g)
                 g2 = self._new_graph()
                 with torch.cuda.graph(g2):
                     m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
@@ -539,6 +562,8 @@ class BatchedTrainer:
                     if inside:
                         self._epilogue()
             self._upd = dict(grads=g1, apply=g2, epilogue_inside=inside)
+            if K > 1:
+                self._upd['chain'] = chain
         finally:
             ops.keepalive_end()
             m.t, m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps = host
@@ -569,6 +594,9 @@ class BatchedTrainer:
         self._upd['grads'].replay()
         if self._upd['apply'] is not None:
             m.update_reduce()
+            for g in self._upd.get('chain', ()):       # opt-in PPO epochs under data parallelism: K all-reduces per update
+                g.replay()
+                m.update_reduce()
             self._upd['apply'].replay()
         m.update_end()
         return self._upd['epilogue_inside']
@@ -802,6 +830,7 @@ class BatchedTrainer:
                     self.summary_writer.add_scalar('train_reward', row['avg_reward'], step)
                     if getattr(self.model, 'reward_scale', 'none') != 'none':     # (the host synchronised above: one more read)
                         self.summary_writer.add_scalar('train/reward_scale_std', self.model.reward_scale_std, step)
+                    _write_ppo_scalars(self.summary_writer, self.model, step)
                     self.summary_writer.flush()
 
         while not self.global_counter.should_stop():

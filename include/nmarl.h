@@ -949,6 +949,30 @@ int nmarl_a2c_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, 
                        const float* v, const uint8_t* action, const float* adv, const float* R, float v_coef,
                        float e_coef, const float* g_up, float* dlogits, float* dv, void* stream);
 /*
+ * Clipped-surrogate (PPO) loss of the opt-in epochs 2..K of an update (MODEL_CONFIG ppo_epochs; the reference has none).  Layouts,
+ * softmax / clamp arithmetic and return codes of nmarl_a2c_loss_*; logp_old, logp_out [N,rows]; clip finite and > 0 (else
+ * NMARL_EINVAL, as for rows < 1, N < 1, A outside 1..8, l_row < A or a null pointer: nothing launched, nothing written).
+ *   nmarl_ppo_logp:  logp_out[n,r] = log(clip(softmax(logits[n,r])[a], 1e-10, 1)) for the action taken, one launch
+ *   rho = exp(log_pi[a] - logp_old)
+ *   loss_out[n] = { -mean(min(rho ADV, clip(rho, 1-clip, 1+clip) ADV)),  0.5 v_coef mean((R-v)^2),  -e_coef mean(H),
+ *                   approx_kl = mean((rho - 1) - (log_pi[a] - logp_old)),  clip_frac = mean(|rho - 1| > clip) }
+ *   (approx_kl: rho - 1 taken as expm1 of the difference, every row's term floored at 0 -- it is >= 0, and exactly 0 at rho = 1)
+ *   bwd: dlogits, dv = g_up[n] * d(sum of the first three terms); the policy part is -ADV rho gate c_a (delta_ka - pi_k) with
+ *   c_a = [pi_a >= 1e-10] and gate = 0 where (ADV > 0 and rho > 1+clip) or (ADV < 0 and rho < 1-clip), else 1.  At logp_old =
+ *   nmarl_ppo_logp of the same logits rho is 1.0f exactly and dlogits / dv have the bits of nmarl_a2c_loss_bwd.
+ * partial: [N, nmarl_ppo_loss_chunks(rows,N), 5]; fixed-order sums, no atomics: the same inputs give the same bits.
+ */
+int nmarl_ppo_logp(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                   const uint8_t* action, float* logp_out, void* stream);
+int nmarl_ppo_loss_chunks(int64_t rows, int32_t N);
+int nmarl_ppo_loss_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                       const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
+                       float clip, float v_coef, float e_coef, float* partial, float* loss_out, void* stream);
+int nmarl_ppo_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                       const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
+                       float clip, float v_coef, float e_coef, const float* g_up, float* dlogits, float* dv,
+                       void* stream);
+/*
  * n-step return and advantage -- OnPolicyBuffer._add_R_Adv / _add_s_R_Adv
  * (agents/utils.py:763-775, 800-816) and the MultiAgent variants (837-855,
  * 888-912).  r [T,E] (alpha < 0: global reward) or [T,E,N] (alpha >= 0: spatial
