@@ -267,6 +267,10 @@ SIGNATURES = {
     'nmarl_ppo_loss_chunks': [_i64, _i32],
     'nmarl_ppo_loss_fwd': [_i64, _i32, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _f32, _f32, _f32, _p, _p, _p],
     'nmarl_ppo_loss_bwd': [_i64, _i32, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _f32, _f32, _f32, _p, _p, _p, _p],
+    'nmarl_ppo_loss_vclip_fwd': [_i64, _i32, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _f32, _f32, _f32, _f32, _p, _p, _p],
+    'nmarl_ppo_loss_vclip_bwd': [_i64, _i32, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _f32, _f32, _f32, _f32, _p, _p, _p, _p],
+    'nmarl_ppo_kl_sum': [_i32, _p, _i64, _p, _p],
+    'nmarl_ppo_kl_gate': [_p, _i32, _f32, _p, _p],
     'nmarl_sample_actions': [_i64, _i32, _i32, _p, _p, _i32, _u64, _i64, _i64, _p, _p, _p],
     'nmarl_nstep_return': [_i64, _i32, _i32, _p, _p, _p, _p, C.c_double, C.c_double, _p, _p, _p, _p],
     'nmarl_gae_return': [_i64, _i32, _i32, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p],

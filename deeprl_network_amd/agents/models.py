@@ -20,7 +20,10 @@ Engine (per n_step batch, E replicas, N agents):
             232-255; means over T*E, sum over agents) -> [RCCL all-reduce] ->
             nmarl_rmsprop_tf_clip (policies.py:32-39; opt-in optimizer = adam: nmarl_adam_clip)
             [-> opt-in ppo_epochs = K > 1: K - 1 more steps on the same batch, each the forward pass recomputed -> clipped surrogate
-            against the behaviour policy's log-probabilities (nmarl_ppo_logp, nmarl_ppo_loss_*) -> all-reduce -> optimiser].
+            against the behaviour policy's log-probabilities (nmarl_ppo_logp, nmarl_ppo_loss_*) -> all-reduce -> optimiser;
+            opt-in ppo_vclip: the value term of those steps clipped around the behaviour critic's values (nmarl_ppo_loss_vclip_*);
+            opt-in ppo_target_kl: the steps behind the first epoch whose pooled approx_kl exceeds it change nothing, decided on
+            the device (nmarl_ppo_kl_sum -> all-reduce -> nmarl_ppo_kl_gate -> the optimiser's status word)].
 """
 import logging
 import os
@@ -135,6 +138,11 @@ class IA2C:
             if self.lstm_precision == 'bf16x3':
                 raise ValueError('ppo_epochs = %d with lstm_precision = bf16x3: epochs >= 2 recompute the forward pass in fp32, the '
                                  'ratio would not start at 1' % self.ppo_epochs)
+        # optional controls of epochs 2..K (absent: off, nothing allocated, the path of before).  ppo_vclip: the value loss clipped
+        # around the critic's values under the weights that produced the batch (PPO2 form); ppo_target_kl: once the mean approx_kl of
+        # an epoch exceeds it, the remaining optimiser steps of the update change nothing -- decided on the device
+        self.ppo_vclip = self._ppo_control(model_config, 'ppo_vclip')
+        self.ppo_target_kl = self._ppo_control(model_config, 'ppo_target_kl')
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -173,6 +181,21 @@ class IA2C:
         self.sess = None                                  # the reference Trainer reads model.sess (TF leak)
         if total_step:
             self._init_train(model_config, self.distance_mask, coop_gamma)
+
+    def _ppo_control(self, model_config, key):
+        """An optional positive float of MODEL_CONFIG that only means something with ppo_epochs > 1 (None: absent)."""
+        raw = model_config.get(key, fallback=None)
+        if raw is None:
+            return None
+        try:
+            value = float(raw)
+        except ValueError:
+            raise ValueError('%s = %r: must be finite and > 0' % (key, raw))
+        if not 0.0 < value < float('inf'):                   # (nan fails both comparisons)
+            raise ValueError('%s = %r: must be finite and > 0' % (key, raw))
+        if self.ppo_epochs == 1:
+            raise ValueError('%s = %r with ppo_epochs = 1: it acts on epochs 2..K only' % (key, raw))
+        return value
 
     def _is_ma2c(self):
         return self.name.startswith('ma2c')
@@ -265,6 +288,17 @@ class IA2C:
             # and per epoch and agent (approx_kl, clip_frac) of the last update -- row 0, the A2C step, stays zero
             self.ppo_logp_old = torch.zeros(N, T * E, dtype=F32, device=d)
             self.ppo_stats = torch.zeros(self.ppo_epochs, N, 2, dtype=F32, device=d)
+            if self.ppo_vclip is not None:
+                # opt-in: the critic's values under the weights that produced the batch (taken with ppo_logp_old) and per epoch and
+                # agent vclip_frac of the last update -- row 0 stays zero
+                self.ppo_v_old = torch.zeros(N, T * E, dtype=F32, device=d)
+                self.ppo_vclip_stats = torch.zeros(self.ppo_epochs, N, dtype=F32, device=d)
+            if self.ppo_target_kl is not None:
+                # opt-in: the KL stop's device words (ops.ppo_kl_gate: stop, steps refused, epochs applied, unused) and the values
+                # every update starts them from
+                self.ppo_gate = torch.tensor(ops.PPO_GATE_RESET, dtype=torch.int32, device=d)
+                self._ppo_gate_reset = torch.tensor(ops.PPO_GATE_RESET, dtype=torch.int32, device=d)
+                self._ppo_gate_pending = False
         self.dist_dev = torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
@@ -631,7 +665,7 @@ class IA2C:
         = the four phases below back to back; BatchedTrainer captures `update_grads` and `update_apply` in hipGraphs and
         replays them around the (eager) gradient exchange, calling the two host-only phases itself.
         Opt-in ppo_epochs = K > 1: K - 1 further {update_ppo_grads, update_reduce, update_apply} on the same batch, `rotate` honoured
-        on the last step only."""
+        on the last step only -- also where the opt-in KL stop (ppo_target_kl) refuses that step on the device."""
         lr = self.update_begin()
         K = self.ppo_epochs
         self.update_grads(R_end)
@@ -661,6 +695,10 @@ class IA2C:
         synchronisation, static shapes and addresses: capturable)."""
         alpha = self.coop_gamma if self.coop_gamma >= 0 else -1.0
         T = self.n_step
+        if self.ppo_target_kl is not None:
+            # opt-in KL stop: every update starts with the stop down and one epoch applied (a kernel, so a replayed graph does it too)
+            ops.copy_multi([(self.ppo_gate, self._ppo_gate_reset)])
+            self._ppo_gate_pending = False
         if self.reward_scale != 'none' and self._rs_pending:
             # the one-replica path (`record` per step kept the raw rewards): the same one call the batched path makes in load_rewards
             self._scale_rewards(self._rs_raw)
@@ -722,7 +760,9 @@ class IA2C:
         N, T, E = self.n_agent, self.n_step, self.E
         action = self.buf_act.view(T * E, N)
         with torch.no_grad():
-            logits, _ = self.policy.heads(Hs.detach(), action)
+            logits, v = self.policy.heads(Hs.detach(), action)
+            if self.ppo_vclip is not None:       # opt-in: the same call's values, what the clipped value loss is clipped around
+                ops.copy_multi([(self.ppo_v_old, v.contiguous())])           # (a kernel node in a captured update, not a memcpy node)
             if ops.ppo_loss_supported(self.n_a):
                 ops.ppo_logp(logits, action, out=self.ppo_logp_old)
             else:
@@ -743,8 +783,13 @@ class IA2C:
         action = self.buf_act.view(T * E, N)
         logits, v = p.heads(Hs, action)
         adv, R, eps = self._loss_adv(), self.R.view(N, T * E), self.ppo_clip
+        vclip = self.ppo_vclip
         if ops.ppo_loss_supported(self.n_a):
-            per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef)
+            if vclip is None:
+                per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef)
+            else:
+                per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef,
+                                                v_old=self.ppo_v_old, vclip=vclip)
         else:
             pi = torch.softmax(logits, dim=-1)
             log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
@@ -752,19 +797,46 @@ class IA2C:
             dlp = log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1) - self.ppo_logp_old
             rho = torch.exp(dlp)
             policy_loss = -torch.min(rho * adv, torch.clamp(rho, 1.0 - eps, 1.0 + eps) * adv).mean(-1)
-            value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
+            if vclip is None:
+                value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
+            else:           # the clipped value loss; outside the clip range the gradient follows the larger of the two errors
+                dvo = v - self.ppo_v_old
+                inside = dvo.abs() <= vclip
+                e1 = (R - v).pow(2)
+                e2 = (R - (self.ppo_v_old + torch.clamp(dvo, -vclip, vclip))).pow(2).detach()
+                value_loss = torch.where(inside | (e1 >= e2), e1, e2).mean(-1) * 0.5 * self.v_coef
             entropy_loss = -entropy.mean(-1) * self.e_coef
             per_agent = policy_loss + value_loss + entropy_loss
             with torch.no_grad():
-                terms = torch.stack([policy_loss, value_loss, entropy_loss, (torch.expm1(dlp) - dlp).clamp_min(0.0).mean(-1),
-                                     ((rho - 1.0).abs() > eps).to(F32).mean(-1)], dim=1)
+                cols = [policy_loss, value_loss, entropy_loss, (torch.expm1(dlp) - dlp).clamp_min(0.0).mean(-1),
+                        ((rho - 1.0).abs() > eps).to(F32).mean(-1)]
+                if vclip is not None:
+                    cols.append((dvo.abs() > vclip).to(F32).mean(-1))
+                terms = torch.stack(cols, dim=1)
         self.ppo_stats[k - 1].copy_(terms[:, 3:5])
+        if vclip is not None:
+            self.ppo_vclip_stats[k - 1].copy_(terms[:, 5])
         t3 = self._terms = terms[:, :3].contiguous()
         self.last_loss = (t3[:, 0], t3[:, 1], t3[:, 2], per_agent.detach())
         per_agent.sum().backward()
         ps.end_backward()
         if ps.mask is not None:
             ps.grad.mul_(ps.mask)
+        if self.ppo_target_kl is not None:
+            # opt-in KL stop: this epoch's sum of approx_kl over agents rides in the float behind the gradient through the epoch's one
+            # all-reduce (free on these nets: only the coupled ones put their hand-off word there); `update_apply` decides on it
+            ops.ppo_kl_sum(terms, ps.grad_tail)
+            self._ppo_gate_pending = True
+
+    @property
+    def ppo_vclip_frac(self):
+        """vclip_frac of the last update's last epoch, mean over agents (host read: synchronises); None with ppo_vclip off."""
+        return None if not hasattr(self, 'ppo_vclip_stats') else float(self.ppo_vclip_stats[-1].mean())
+
+    @property
+    def ppo_epochs_done(self):
+        """Optimiser steps the last update applied before the KL stop, 1..K (host read: synchronises); None with ppo_target_kl off."""
+        return None if not hasattr(self, 'ppo_gate') else int(self.ppo_gate[2])
 
     @property
     def ppo_kl(self):
@@ -798,19 +870,25 @@ class IA2C:
         if self._status_on_wire:             # some rank timed out (summed tail != 0): this rank's status word is raised as well
             st = ops.handoff_status(self.device)[:1]
             torch.maximum(st, (ps.grad_tail != 0).to(torch.int32), out=st)
+        kw = {}
+        if self.ppo_target_kl is not None:   # opt-in KL stop: the step consults the model's own word and changes nothing while it is up
+            if self._ppo_gate_pending:       # (the step of an epoch k >= 2: its KL, summed over agents and ranks, against the target)
+                ops.ppo_kl_gate(ps.grad_tail, self.world_size * self.n_agent, self.ppo_target_kl, self.ppo_gate)
+                self._ppo_gate_pending = False
+            kw['stop'] = self.ppo_gate
         if self.optimizer == 'adam':         # opt-in: the same [G,P] views, clip, scale, guard and lr; Adam's slots and device counter
             shape = (self.n_agent, ps.P) if self.per_agent_optimizer else (1, self.n_agent * ps.P)
             ops.adam_clip(ps.flat.view(shape), ps.grad.view(shape), ps.adam_m.view(shape), ps.adam_v.view(shape), ps.scratch,
                           ps.adam_t, lr, self.adam_beta1, self.adam_beta2, self.adam_epsilon, self.max_grad_norm, scale,
-                          self.grad_norm, lr_dev=lr_dev, guard=guard)
+                          self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
         elif self.per_agent_optimizer:
             ops.rmsprop_tf_clip(ps.flat, ps.grad, ps.ms, ps.scratch, lr, self.rmsp_alpha, self.rmsp_epsilon,
-                                self.max_grad_norm, scale, self.grad_norm, lr_dev=lr_dev, guard=guard)
+                                self.max_grad_norm, scale, self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
         else:
             n = self.n_agent * ps.P
             ops.rmsprop_tf_clip(ps.flat.view(1, n), ps.grad.view(1, n), ps.ms.view(1, n), ps.scratch, lr,
                                 self.rmsp_alpha, self.rmsp_epsilon, self.max_grad_norm, scale, self.grad_norm,
-                                lr_dev=lr_dev, guard=guard)
+                                lr_dev=lr_dev, guard=guard, **kw)
         self._after_apply()
         if rotate:
             T = self.n_step
@@ -1083,7 +1161,11 @@ class IA2C_CU(MA2C_NC):
     name = 'ma2c_cu'
 
     def _after_apply(self):
-        self.policy.consensus_update()
+        # (under the opt-in KL stop a refused step must leave the weights as they are: the average is committed through the same word)
+        if self.ppo_target_kl is None:
+            self.policy.consensus_update()
+        else:
+            self.policy.consensus_update(skip_if=self.ppo_gate)
 
 
 class MA2C_DIAL(MA2C_NC):

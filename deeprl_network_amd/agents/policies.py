@@ -1086,9 +1086,10 @@ class ConsensusPolicy(LstmPolicy):
         s = self._fc_infer(self._own(xv), 'fc_w', 'fc_b', ops.BIAS_RELU, out=out)
         return s if self.xside else torch.bmm(s, self.params['lstm_wx'])
 
-    def consensus_update(self):
+    def consensus_update(self, skip_if=None):
         """policies.py:357-364, 403-426: simultaneous neighbourhood average of (wx, wh, b) of every agent's LSTM.
-        The three tensors are adjacent in the flat buffer: ONE [N,N] x [N,K] product."""
+        The three tensors are adjacent in the flat buffer: ONE [N,N] x [N,K] product.  skip_if: int32 device word -- while its
+        first element is != 0 the weights keep their bits (selected on the device, no host read)."""
         ps = self.params
         o0 = ps.index['lstm_wx'][0]
         o1 = ps.index['lstm_b'][0] + ps.index['lstm_b'][1]
@@ -1102,7 +1103,10 @@ class ConsensusPolicy(LstmPolicy):
             self._avg = torch.from_numpy(A / A.sum(1, keepdims=True)).to(self.device)
         with torch.no_grad():
             blk = ps.flat[:, o0:o1]
-            blk.copy_(self._avg @ blk)
+            if skip_if is None:
+                blk.copy_(self._avg @ blk)
+            else:
+                blk.copy_(torch.where(skip_if[:1] != 0, blk, self._avg @ blk))
 
 
 class DIALMultiAgentPolicy(BatchedPolicy):

@@ -929,7 +929,12 @@ __global__ __launch_bounds__(256) void ppo_logp_kernel(const int64_t rows, const
     logp_out[(int64_t)n * rows + r] = lpa;
 }
 
-template <bool BWD>
+// VCLIP (opt-in MODEL_CONFIG ppo_vclip; the instantiations without it are the code of before): the PPO2 clipped value loss against
+// v_old [N,rows], one more 4-byte load per row and a sixth partial column:
+//   d = v - v_old;  inside = |d| <= vclip;  v_c = v_old + clip(d, -vclip, +vclip);  e1 = (R - v)^2;  e2 = (R - v_c)^2
+//   e = inside ? e1 : max(e1, e2)  (inside is tested: v_old + (v - v_old) is not v in fp32);  value = 0.5 v_coef mean(e)
+//   d value / d v = -v_coef (R - v) / rows where inside or e1 >= e2, else 0;  vclip_frac = mean(|d| > vclip)
+template <bool BWD, bool VCLIP = false>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const int N, const int A, const int rows_per_block,
                                                        const float* __restrict__ logits, const int64_t l_sn, const int64_t l_row,
                                                        const float* __restrict__ v, const uint8_t* __restrict__ action,
@@ -937,14 +942,16 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const
                                                        const float* __restrict__ logp_old, const float clip, const float v_coef,
                                                        const float e_coef, const float* __restrict__ g_up,
                                                        float* __restrict__ partial, float* __restrict__ dlogits,
-                                                       float* __restrict__ dv) {
+                                                       float* __restrict__ dv, const float* __restrict__ v_old = nullptr,
+                                                       const float vclip = 0.0f) {
+    constexpr int NT = VCLIP ? 6 : 5;
     const int n = blockIdx.y;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
     const float inv_m = 1.0f / (float)rows;
     const float gn = BWD ? g_up[n] * inv_m : 0.0f;
     const float lo_c = 1.0f - clip, hi_c = 1.0f + clip;
-    float s_pol = 0.0f, s_val = 0.0f, s_ent = 0.0f, s_kl = 0.0f, s_cf = 0.0f;
+    float s_pol = 0.0f, s_val = 0.0f, s_ent = 0.0f, s_kl = 0.0f, s_cf = 0.0f, s_vf = 0.0f;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
         const int a = action[r * N + n];
         float p[LOSS_MAXA], lp[LOSS_MAXA], H, lpa, pa;
@@ -953,9 +960,26 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const
         const float ad = adv[i], dR = R[i] - v[i];
         const float dlp = lpa - logp_old[i];
         const float rho = expf(dlp);
+        float e_v = 0.0f, over = 0.0f;
+        bool v_open = true;
+        if (VCLIP) {
+            const float vo = v_old[i];
+            const float d = v[i] - vo;
+            const bool inside = fabsf(d) <= vclip;
+            const float dRc = R[i] - (vo + fminf(fmaxf(d, -vclip), vclip));
+            const float e1 = dR * dR, e2 = dRc * dRc;
+            e_v = inside ? e1 : fmaxf(e1, e2);
+            v_open = inside || e1 >= e2;
+            over = fabsf(d) > vclip ? 1.0f : 0.0f;
+        }
         if (!BWD) {
             s_pol -= fminf(rho * ad, fminf(fmaxf(rho, lo_c), hi_c) * ad);
-            s_val += dR * dR;
+            if (VCLIP) {
+                s_val += e_v;
+                s_vf += over;
+            } else {
+                s_val += dR * dR;
+            }
             s_ent += H;
             // (rho - 1) - log rho >= 0; rho - 1 taken as expm1 of the difference: expf's rounding (6e-8) would swamp a term of d^2 / 2
             s_kl += fmaxf(expm1f(dlp) - dlp, 0.0f);
@@ -978,23 +1002,25 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const
                     const float d_ent = -e_coef * p[k] * (gk - gbar);
                     dl[k] = gn * (d_pol + d_ent);
                 }
-            dv[i] = -gn * v_coef * dR;
+            dv[i] = v_open ? -gn * v_coef * dR : 0.0f;
         }
     }
     if (!BWD) {
-        __shared__ float red[4][5];
+        __shared__ float red[4][NT];
         for (int off = 32; off > 0; off >>= 1) {
             s_pol += __shfl_down(s_pol, off, 64);
             s_val += __shfl_down(s_val, off, 64);
             s_ent += __shfl_down(s_ent, off, 64);
             s_kl += __shfl_down(s_kl, off, 64);
             s_cf += __shfl_down(s_cf, off, 64);
+            if (VCLIP) s_vf += __shfl_down(s_vf, off, 64);
         }
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         if (lane == 0) { red[w][0] = s_pol; red[w][1] = s_val; red[w][2] = s_ent; red[w][3] = s_kl; red[w][4] = s_cf; }
+        if (VCLIP && lane == 0) red[w][NT - 1] = s_vf;
         __syncthreads();
-        if (threadIdx.x < 5)
-            partial[((int64_t)n * gridDim.x + blockIdx.x) * 5 + threadIdx.x] =
+        if (threadIdx.x < NT)
+            partial[((int64_t)n * gridDim.x + blockIdx.x) * NT + threadIdx.x] =
                 ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
     }
 }
@@ -1006,6 +1032,43 @@ __global__ __launch_bounds__(64) void ppo_loss_reduce_kernel(const int C, const 
     float s = nmarl_ordered_sum(partial + (int64_t)n * C * 5 + k, 5, C);
     s /= (float)rows;
     out[n * 5 + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
+}
+
+// the value-clip instantiation's second stage: six columns, the sixth vclip_frac
+__global__ __launch_bounds__(64) void ppo_loss_vclip_reduce_kernel(const int C, const int64_t rows, const float v_coef,
+                                                                   const float e_coef, const float* __restrict__ partial,
+                                                                   float* __restrict__ out /*[N,6]*/) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    if (k >= 6) return;
+    float s = nmarl_ordered_sum(partial + (int64_t)n * C * 6 + k, 6, C);
+    s /= (float)rows;
+    out[n * 6 + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
+}
+
+// Opt-in KL stop of the PPO epochs (MODEL_CONFIG ppo_target_kl), no host synchronisation.  gate: int32 x 4 owned by the model --
+// [0] stop (what nmarl_rmsprop_tf_clip_guarded / nmarl_adam_clip_guarded take as their status word: while != 0 a step changes
+// nothing), [1] the steps those refused, [2] ppo_epochs_done, [3] unused; the host resets it to (0, 0, 1, 0) at the start of every update.
+//   ppo_kl_sum_kernel:  tail[0] = sum over agents of terms[n, 3] (approx_kl) in index order -- the float behind the gradient, so
+//                       that the update's one all-reduce per epoch carries it and every rank sees the same sum
+//   ppo_kl_gate_kernel: kl = tail[0] / count (count = ranks x agents);  kl > kappa (or NaN) raises stop, which stays raised;
+//                       while stop is 0 the epoch counts as done
+// One thread each: N <= a few dozen, and one owner of the words needs no atomics.
+__global__ __launch_bounds__(64) void ppo_kl_sum_kernel(const int N, const float* __restrict__ terms, const int64_t t_stride,
+                                                        float* __restrict__ tail) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float s = 0.0f;
+    for (int n = 0; n < N; ++n) s += terms[(int64_t)n * t_stride + 3];
+    tail[0] = s;
+}
+
+__global__ __launch_bounds__(64) void ppo_kl_gate_kernel(const float* __restrict__ tail, const int count, const float kappa,
+                                                         int32_t* __restrict__ gate) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float kl = tail[0] / (float)count;
+    int32_t stop = gate[0];
+    if (!(kl <= kappa)) stop = 1;                 // strict: kl == kappa goes on; a NaN fails closed
+    gate[0] = stop;
+    if (stop == 0) gate[2] = gate[2] + 1;
 }
 
 inline int grid_x(int64_t n, int cap = 2048) {
@@ -1269,6 +1332,50 @@ extern "C" int nmarl_ppo_loss_bwd(int64_t rows, int32_t N, int32_t A, const floa
     const int rpb = (int)((rows + C - 1) / C);
     hipLaunchKernelGGL(ppo_loss_kernel<true>, dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb, logits,
                        l_sn, l_row, v, action, adv, R, logp_old, clip, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_loss_vclip_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                                        const float* v, const uint8_t* action, const float* adv, const float* R,
+                                        const float* logp_old, const float* v_old, float clip, float vclip, float v_coef,
+                                        float e_coef, float* partial, float* loss_out, void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
+        !v_old || !partial || !loss_out || !ppo_clip_ok(clip) || !ppo_clip_ok(vclip))
+        return NMARL_EINVAL;
+    const int C = loss_chunks(rows, N);
+    const int rpb = (int)((rows + C - 1) / C);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL((ppo_loss_kernel<false, true>), dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action,
+                       adv, R, logp_old, clip, v_coef, e_coef, (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr,
+                       v_old, vclip);
+    hipLaunchKernelGGL(ppo_loss_vclip_reduce_kernel, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, partial, loss_out);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_loss_vclip_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                                        const float* v, const uint8_t* action, const float* adv, const float* R,
+                                        const float* logp_old, const float* v_old, float clip, float vclip, float v_coef,
+                                        float e_coef, const float* g_up, float* dlogits, float* dv, void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
+        !v_old || !g_up || !dlogits || !dv || !ppo_clip_ok(clip) || !ppo_clip_ok(vclip))
+        return NMARL_EINVAL;
+    const int C = loss_chunks(rows, N);
+    const int rpb = (int)((rows + C - 1) / C);
+    hipLaunchKernelGGL((ppo_loss_kernel<true, true>), dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb,
+                       logits, l_sn, l_row, v, action, adv, R, logp_old, clip, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv,
+                       v_old, vclip);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_kl_sum(int32_t N, const float* terms, int64_t t_stride, float* tail, void* stream) {
+    if (N <= 0 || !terms || t_stride < 4 || !tail) return NMARL_EINVAL;
+    hipLaunchKernelGGL(ppo_kl_sum_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), N, terms, t_stride, tail);
+    return nmarl_check_launch();
+}
+
+extern "C" int nmarl_ppo_kl_gate(const float* tail, int32_t count, float kappa, int32_t* gate, void* stream) {
+    if (!tail || count <= 0 || !ppo_clip_ok(kappa) || !gate || ((uintptr_t)gate % 4)) return NMARL_EINVAL;
+    hipLaunchKernelGGL(ppo_kl_gate_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), tail, count, kappa, gate);
     return nmarl_check_launch();
 }
 

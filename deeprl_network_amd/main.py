@@ -53,6 +53,14 @@ def parse_args(argv=None):
                          'policy that produced the batch; IA2C / IA2C-FP / ConseNet only, fp32 only')
     sp.add_argument('--ppo-clip', type=float, default=None,
                     help='epsilon of the clipped surrogate (overrides MODEL_CONFIG ppo_clip; default 0.2; finite and > 0)')
+    sp.add_argument('--ppo-vclip', type=float, default=None,
+                    help='clip range of the value loss in steps 2..K (overrides MODEL_CONFIG ppo_vclip; default absent = unclipped).  '
+                         'The critic\'s error is the larger of (R - v)^2 and (R - v_clipped)^2, v_clipped within +-this of the value '
+                         'under the weights that produced the batch; finite and > 0, needs --ppo-epochs / ppo_epochs > 1')
+    sp.add_argument('--ppo-target-kl', type=float, default=None,
+                    help='KL stop of steps 2..K (overrides MODEL_CONFIG ppo_target_kl; default absent = no stop).  Once the mean '
+                         'approx_kl of a step exceeds this, that step and the rest of the update change nothing; decided on the '
+                         'device, the remaining passes still run (it buys stability, not time); finite and > 0, needs ppo_epochs > 1')
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -92,7 +100,8 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale, --ppo-epochs, --ppo-clip), set
+    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale, --ppo-epochs, --ppo-clip,
+    --ppo-vclip, --ppo-target-kl), set
     on every rank; run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
     given = {'lstm_precision': args.lstm_precision,
              'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
@@ -100,7 +109,9 @@ def apply_overrides(config, args, run_ini=None):
              'adv_norm': args.adv_norm,
              'reward_scale': getattr(args, 'reward_scale', None),
              'ppo_epochs': None if getattr(args, 'ppo_epochs', None) is None else str(args.ppo_epochs),
-             'ppo_clip': None if getattr(args, 'ppo_clip', None) is None else repr(args.ppo_clip)}
+             'ppo_clip': None if getattr(args, 'ppo_clip', None) is None else repr(args.ppo_clip),
+             'ppo_vclip': None if getattr(args, 'ppo_vclip', None) is None else repr(args.ppo_vclip),
+             'ppo_target_kl': None if getattr(args, 'ppo_target_kl', None) is None else repr(args.ppo_target_kl)}
     given = {k: v for k, v in given.items() if v is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)

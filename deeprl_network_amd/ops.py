@@ -1868,10 +1868,77 @@ class _PPOLoss(torch.autograd.Function):
         return dlogits, dv, None, None, None, None, None, None, None
 
 
-def ppo_loss(logits, v, action, adv, R, logp_old, clip, v_coef, e_coef):
+class _PPOLossVClip(torch.autograd.Function):
+    """_PPOLoss with the value term clipped around v_old [N,rows] (nmarl_ppo_loss_vclip_*): terms [N,6], the sixth vclip_frac."""
+
+    @staticmethod
+    def forward(ctx, logits, v, action, adv, R, logp_old, v_old, clip, vclip, v_coef, e_coef):
+        N, rows, A = logits.shape
+        if logits.stride(2) != 1:
+            logits = logits.contiguous()
+        v, adv, R, logp_old, v_old = v.contiguous(), adv.contiguous(), R.contiguous(), logp_old.contiguous(), v_old.contiguous()
+        C_ = lib.nmarl_ppo_loss_chunks(rows, N)
+        partial = torch.empty(N, C_, 6, dtype=F32, device=logits.device)
+        out = torch.empty(N, 6, dtype=F32, device=logits.device)
+        check(lib.nmarl_ppo_loss_vclip_fwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1),
+                                           ptr(v, F32), ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32),
+                                           ptr(v_old, F32), clip, vclip, v_coef, e_coef, ptr(partial), ptr(out), stream()),
+              'nmarl_ppo_loss_vclip_fwd')
+        ctx.save_for_backward(logits, v, action, adv, R, logp_old, v_old)
+        ctx.coefs = (clip, vclip, v_coef, e_coef)
+        ctx.mark_non_differentiable(out)
+        return out[:, :3].sum(dim=1), out
+
+    @staticmethod
+    def backward(ctx, g, _):
+        logits, v, action, adv, R, logp_old, v_old = ctx.saved_tensors
+        N, rows, A = logits.shape
+        gn = g.contiguous()
+        dlogits = torch.empty(N, rows, A, dtype=F32, device=logits.device)
+        dv = torch.empty(N, rows, dtype=F32, device=logits.device)
+        clip, vclip, v_coef, e_coef = ctx.coefs
+        check(lib.nmarl_ppo_loss_vclip_bwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1),
+                                           ptr(v, F32), ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32),
+                                           ptr(v_old, F32), clip, vclip, v_coef, e_coef, ptr(gn, F32), ptr(dlogits), ptr(dv),
+                                           stream()), 'nmarl_ppo_loss_vclip_bwd')
+        return dlogits, dv, None, None, None, None, None, None, None, None, None
+
+
+def ppo_loss(logits, v, action, adv, R, logp_old, clip, v_coef, e_coef, v_old=None, vclip=None):
     """-> per-agent total loss [N] (differentiable; policy + value + entropy) and the detached (policy, value, entropy, approx_kl,
-    clip_frac) terms [N,5] of the clipped surrogate with ratio exp(log_pi[a] - logp_old)."""
-    return _PPOLoss.apply(logits, v, action, adv, R, logp_old, float(clip), float(v_coef), float(e_coef))
+    clip_frac) terms [N,5] of the clipped surrogate with ratio exp(log_pi[a] - logp_old).  v_old [N,rows] and vclip (both or
+    neither): the value term clipped around v_old, terms [N,6] with vclip_frac behind the five."""
+    if (v_old is None) != (vclip is None):
+        raise ValueError('ppo_loss: v_old and vclip go together')
+    if v_old is None:
+        return _PPOLoss.apply(logits, v, action, adv, R, logp_old, float(clip), float(v_coef), float(e_coef))
+    if tuple(v_old.shape) != tuple(v.shape):
+        raise ValueError('ppo_loss: v_old must have the shape of v, %s (got %s)' % (tuple(v.shape), tuple(v_old.shape)))
+    return _PPOLossVClip.apply(logits, v, action, adv, R, logp_old, v_old.detach(), float(clip), float(vclip), float(v_coef),
+                               float(e_coef))
+
+
+def ppo_kl_sum(terms, tail):
+    """tail [1] f32 <- the sum over agents of terms[:, 3] (approx_kl of ops.ppo_loss's terms [N,5] | [N,6]) in index order: one
+    launch, capturable.  tail is the float behind the flat gradient (params.grad_tail): the epoch's all-reduce sums it over ranks."""
+    if terms.dim() != 2 or terms.shape[1] < 4 or terms.stride(1) != 1 or tail.numel() != 1:
+        raise ValueError('ppo_kl_sum: terms [N, >= 4] with unit column stride, tail one float')
+    N = terms.shape[0]
+    check(lib.nmarl_ppo_kl_sum(N, ptr(terms, F32, strided=True), terms.stride(0) if N > 1 else terms.shape[1],
+                               ptr(tail, F32, strided=True), stream()), 'nmarl_ppo_kl_sum')
+
+
+PPO_GATE_WORDS = 4          # int32 words of the KL stop's `gate`: stop, steps refused, epochs done, unused
+PPO_GATE_RESET = (0, 0, 1, 0)
+
+
+def ppo_kl_gate(tail, count, kappa, gate):
+    """The KL stop's decision on the device: kl = tail / count (count = ranks x agents); kl > kappa raises gate[0] (sticky); while
+    gate[0] is 0, gate[2] (the epochs applied) advances.  gate: int32 [PPO_GATE_WORDS], reset to PPO_GATE_RESET per update."""
+    if gate.dtype != torch.int32 or gate.numel() < PPO_GATE_WORDS or not gate.is_contiguous() or tail.numel() != 1:
+        raise ValueError('ppo_kl_gate: gate int32 [%d] contiguous, tail one float' % PPO_GATE_WORDS)
+    check(lib.nmarl_ppo_kl_gate(ptr(tail, F32, strided=True), int(count), float(kappa), ptr(gate, torch.int32), stream()),
+          'nmarl_ppo_kl_gate')
 
 
 def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, adv_out=None):
@@ -1900,28 +1967,41 @@ def gae_return(r, v, done_post, R_end, gamma, lam, alpha, dist=None, R_out=None,
     return R_out, adv_out
 
 
-def rmsprop_tf_clip(w, g, ms, scratch, lr, rho, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False):
+def _status_word(w, guard, stop):
+    """The status word of a guarded optimiser step: the device's hand-off word (guard), the caller's own (stop) or none."""
+    if stop is None:
+        return ptr(handoff_status(w.device), torch.int32) if (guard and w.is_cuda) else None
+    if guard:
+        raise ValueError('optimiser step: guard (the hand-off word) and stop (the caller\'s word) exclude each other')
+    if stop.dtype != torch.int32 or stop.numel() < 2 or not stop.is_contiguous():
+        raise ValueError('optimiser step: stop must be a contiguous int32 tensor of at least two words')
+    return ptr(stop, torch.int32)
+
+
+def rmsprop_tf_clip(w, g, ms, scratch, lr, rho, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False, stop=None):
     """In-place clip_by_global_norm + TF RMSProp on flat [G,P] buffers.  guard: the caller's model launches in-launch
     hand-off kernels -- the step then consults the device's hand-off status word and changes nothing while it is set (a
     batch whose hand-off timed out cannot reach the weights: fail closed).  Models without such kernels do not look at the
-    word, so another model's time-out on the same device cannot silence their updates."""
+    word, so another model's time-out on the same device cannot silence their updates.  stop: an int32 device word of the caller's
+    (at least two words: the second counts the refused steps) consulted in the hand-off word's place -- the opt-in KL stop of the
+    PPO epochs, on nets without hand-off kernels; not together with guard."""
     G, P = w.shape
     check(lib.nmarl_rmsprop_tf_clip_guarded(G, P, ptr(w, F32), ptr(g, F32), ptr(ms, F32), ptr(scratch, F32),
                                             ptr(lr_dev, F32), float(lr), float(rho), float(eps), float(max_norm),
                                             float(grad_scale), ptr(norm_out, F32),
-                                            ptr(handoff_status(w.device), torch.int32) if (guard and w.is_cuda) else None, stream()),
+                                            _status_word(w, guard, stop), stream()),
           'nmarl_rmsprop_tf_clip')
 
 
-def adam_clip(w, g, m, v, scratch, step, lr, beta1, beta2, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False):
+def adam_clip(w, g, m, v, scratch, step, lr, beta1, beta2, eps, max_norm, grad_scale=1.0, norm_out=None, lr_dev=None, guard=False, stop=None):
     """In-place clip_by_global_norm + bias-corrected Adam on flat [G,P] buffers (the opt-in second optimiser).  m, v: fp32 slots
     that start at 0; step: one device int32, the steps applied so far, advanced by the call.  guard as in `rmsprop_tf_clip`: a
-    refused step changes neither w, m, v nor step."""
+    refused step changes neither w, m, v nor step.  stop as in `rmsprop_tf_clip`."""
     G, P = w.shape
     check(lib.nmarl_adam_clip_guarded(G, P, ptr(w, F32), ptr(g, F32), ptr(m, F32), ptr(v, F32), ptr(scratch, F32),
                                       ptr(step, torch.int32), ptr(lr_dev, F32), float(lr), float(beta1), float(beta2), float(eps),
                                       float(max_norm), float(grad_scale), ptr(norm_out, F32),
-                                      ptr(handoff_status(w.device), torch.int32) if (guard and w.is_cuda) else None, stream()),
+                                      _status_word(w, guard, stop), stream()),
           'nmarl_adam_clip')
 
 

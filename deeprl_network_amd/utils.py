@@ -110,6 +110,10 @@ def _write_ppo_scalars(writer, model, step):
         name = model.policy.summary_name
         writer.add_scalar('train/%s_ppo_kl' % name, model.ppo_kl, step)
         writer.add_scalar('train/%s_ppo_clipfrac' % name, model.ppo_clip_frac, step)
+        if getattr(model, 'ppo_vclip', None) is not None:           # opt-in value clipping: the share of rows outside the clip range
+            writer.add_scalar('train/%s_ppo_vclipfrac' % name, model.ppo_vclip_frac, step)
+        if getattr(model, 'ppo_target_kl', None) is not None:       # opt-in KL stop: the optimiser steps the last update applied
+            writer.add_scalar('train/%s_ppo_epochs_done' % name, model.ppo_epochs_done, step)
 
 
 # ------------------------------------------------------------------ the E = 1 driver behind the reference's Trainer surface

@@ -973,6 +973,37 @@ int nmarl_ppo_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, 
                        float clip, float v_coef, float e_coef, const float* g_up, float* dlogits, float* dv,
                        void* stream);
 /*
+ * The same loss with the value term clipped around v_old [N,rows], the critic's values under the weights that produced the batch
+ * (opt-in MODEL_CONFIG ppo_vclip; PPO2 form).  Everything of nmarl_ppo_loss_* holds; in addition v_old non-null and vclip finite
+ * and > 0, else NMARL_EINVAL.  One more 4-byte load per row, partial [N, nmarl_ppo_loss_chunks(rows,N), 6], loss_out [N,6]:
+ *   d = v - v_old;  inside = |d| <= vclip;  v_c = v_old + clip(d, -vclip, +vclip);  e1 = (R-v)^2;  e2 = (R-v_c)^2
+ *   loss_out[n][1] = 0.5 v_coef mean(inside ? e1 : max(e1, e2));  loss_out[n][5] = vclip_frac = mean(|d| > vclip)
+ *   bwd: dv = -g_up[n] v_coef (R-v) / rows where inside or e1 >= e2, else 0
+ * The other four terms and dlogits are those of nmarl_ppo_loss_*; where every row is inside (vclip huge), terms 0..4, dlogits and dv
+ * have its bits (inside is tested explicitly: v_old + (v - v_old) is not v in fp32).
+ */
+int nmarl_ppo_loss_vclip_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                             const float* v, const uint8_t* action, const float* adv, const float* R,
+                             const float* logp_old, const float* v_old, float clip, float vclip, float v_coef, float e_coef,
+                             float* partial, float* loss_out, void* stream);
+int nmarl_ppo_loss_vclip_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                             const float* v, const uint8_t* action, const float* adv, const float* R,
+                             const float* logp_old, const float* v_old, float clip, float vclip, float v_coef, float e_coef,
+                             const float* g_up, float* dlogits, float* dv, void* stream);
+/*
+ * KL stop of the PPO epochs without a host synchronisation (opt-in MODEL_CONFIG ppo_target_kl).  gate: int32 x 4 the caller owns
+ * and sets to (0, 0, 1, 0) at the start of every update -- [0] stop, the status word nmarl_rmsprop_tf_clip_guarded /
+ * nmarl_adam_clip_guarded are given (while != 0 a step changes nothing and counts itself in [1]), [2] epochs applied, [3] unused.
+ *   nmarl_ppo_kl_sum:   tail[0] = sum_n terms[n * t_stride + 3] in index order (terms: loss_out of nmarl_ppo_loss_*[_vclip]_fwd,
+ *                       t_stride 5 or 6); tail is the float behind the gradient, so the epoch's all-reduce sums it over the ranks
+ *   nmarl_ppo_kl_gate:  kl = tail[0] / count (count = ranks x agents); kl > kappa, or a NaN, raises gate[0], which stays raised;
+ *                       while gate[0] is 0, gate[2] += 1
+ * One launch of one thread each, capturable.  NMARL_EINVAL without a launch for N < 1, t_stride < 4, count < 1, a null pointer,
+ * a misaligned gate, kappa <= 0 / NaN / inf.
+ */
+int nmarl_ppo_kl_sum(int32_t N, const float* terms, int64_t t_stride, float* tail, void* stream);
+int nmarl_ppo_kl_gate(const float* tail, int32_t count, float kappa, int32_t* gate, void* stream);
+/*
  * n-step return and advantage -- OnPolicyBuffer._add_R_Adv / _add_s_R_Adv
  * (agents/utils.py:763-775, 800-816) and the MultiAgent variants (837-855,
  * 888-912).  r [T,E] (alpha < 0: global reward) or [T,E,N] (alpha >= 0: spatial
