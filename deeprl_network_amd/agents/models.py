@@ -39,6 +39,36 @@ from .utils import Scheduler
 F32 = torch.float32
 
 
+# Readers of the optional MODEL_CONFIG keys (absent: the default, so every reference ini runs unchanged)
+def _cfg_choice(model_config, key, default, choices):
+    value = model_config.get(key, fallback=default).strip().lower()
+    if value not in choices:
+        raise ValueError('%s = %r: must be %s' % (key, value, ' or '.join([', '.join(choices[:-1]), choices[-1]])))
+    return value
+
+
+def _cfg_float(model_config, key, default, ok, must):
+    """A float that satisfies `ok` (written so that nan fails it), or ValueError '<key> = <value>: <must>'."""
+    value = model_config.getfloat(key, fallback=default)
+    if not ok(value):
+        raise ValueError('%s = %r: %s' % (key, value, must))
+    return value
+
+
+def _cfg_positive(model_config, key):
+    """An optional finite float > 0 (None: absent)."""
+    raw = model_config.get(key, fallback=None)
+    if raw is None:
+        return None
+    try:
+        value = float(raw)
+    except ValueError:
+        value = float('nan')
+    if not 0.0 < value < float('inf'):                   # (nan fails both comparisons)
+        raise ValueError('%s = %r: must be finite and > 0' % (key, raw))
+    return value
+
+
 class IA2C:
     """Independent A2C with per-agent optimisers (models.py:15-158)."""
 
@@ -81,39 +111,22 @@ class IA2C:
         self.lstm_precision = ops.check_precision(model_config.get('lstm_precision', fallback='fp32').strip(), 'lstm_precision')
         # optional (absent: 1.0 = the reference's plain n-step advantage, ops.nstep_return): lambda of GAE -- any other value in
         # [0, 1] sends the update's return scan through ops.gae_return (R becomes the lambda-return)
-        self.gae_lambda = model_config.getfloat('gae_lambda', fallback=1.0)
-        if not 0.0 <= self.gae_lambda <= 1.0:                # (nan fails both comparisons)
-            raise ValueError('gae_lambda = %r: must lie in [0, 1]' % self.gae_lambda)
+        self.gae_lambda = _cfg_float(model_config, 'gae_lambda', 1.0, lambda x: 0.0 <= x <= 1.0, 'must lie in [0, 1]')
         # optional (absent: 'rmsprop' = the reference's clip + TF-1.12 RMSProp, ops.rmsprop_tf_clip): 'adam' sends the optimiser
         # step through ops.adam_clip (the same clip, then bias-corrected Adam); rmsp_alpha / rmsp_epsilon are unused then
-        self.optimizer = model_config.get('optimizer', fallback='rmsprop').strip().lower()
-        if self.optimizer not in ('rmsprop', 'adam'):
-            raise ValueError('optimizer = %r: must be rmsprop or adam' % self.optimizer)
-        self.adam_beta1 = model_config.getfloat('adam_beta1', fallback=0.9)
-        self.adam_beta2 = model_config.getfloat('adam_beta2', fallback=0.999)
-        self.adam_epsilon = model_config.getfloat('adam_epsilon', fallback=1e-8)
-        for key in ('adam_beta1', 'adam_beta2'):
-            if not 0.0 <= getattr(self, key) < 1.0:          # (nan fails both comparisons)
-                raise ValueError('%s = %r: must lie in [0, 1)' % (key, getattr(self, key)))
-        if not self.adam_epsilon > 0.0:
-            raise ValueError('adam_epsilon = %r: must be positive' % self.adam_epsilon)
+        self.optimizer = _cfg_choice(model_config, 'optimizer', 'rmsprop', ('rmsprop', 'adam'))
+        self.adam_beta1 = _cfg_float(model_config, 'adam_beta1', 0.9, lambda x: 0.0 <= x < 1.0, 'must lie in [0, 1)')
+        self.adam_beta2 = _cfg_float(model_config, 'adam_beta2', 0.999, lambda x: 0.0 <= x < 1.0, 'must lie in [0, 1)')
+        self.adam_epsilon = _cfg_float(model_config, 'adam_epsilon', 1e-8, lambda x: x > 0.0, 'must be positive')
         # optional (absent: 'none' = the raw advantage in the policy-gradient term, as before): 'agent' standardises every agent's
         # T*E advantages of a batch to zero mean and unit std (each agent has its own critic), 'all' the N*T*E of all agents together
         # -- ops.standardize behind the return scan; the critic's target R is left alone
-        self.adv_norm = model_config.get('adv_norm', fallback='none').strip().lower()
-        if self.adv_norm not in ('none', 'agent', 'all'):
-            raise ValueError('adv_norm = %r: must be none, agent or all' % self.adv_norm)
-        self.adv_norm_epsilon = model_config.getfloat('adv_norm_epsilon', fallback=1e-8)
-        if not self.adv_norm_epsilon >= 0.0:                 # (nan fails the comparison)
-            raise ValueError('adv_norm_epsilon = %r: must be >= 0' % self.adv_norm_epsilon)
+        self.adv_norm = _cfg_choice(model_config, 'adv_norm', 'none', ('none', 'agent', 'all'))
+        self.adv_norm_epsilon = _cfg_float(model_config, 'adv_norm_epsilon', 1e-8, lambda x: x >= 0.0, 'must be >= 0')
         # optional (absent: 'none' = raw / reward_norm, as before): 'return' divides the rewards of a batch by the running standard
         # deviation of the discounted return over every sample seen so far (ops.reward_scale, in place of reward_norm)
-        self.reward_scale = model_config.get('reward_scale', fallback='none').strip().lower()
-        if self.reward_scale not in ('none', 'return'):
-            raise ValueError('reward_scale = %r: must be none or return' % self.reward_scale)
-        self.reward_scale_epsilon = model_config.getfloat('reward_scale_epsilon', fallback=1e-8)
-        if not self.reward_scale_epsilon >= 0.0:             # (nan fails the comparison)
-            raise ValueError('reward_scale_epsilon = %r: must be >= 0' % self.reward_scale_epsilon)
+        self.reward_scale = _cfg_choice(model_config, 'reward_scale', 'none', ('none', 'return'))
+        self.reward_scale_epsilon = _cfg_float(model_config, 'reward_scale_epsilon', 1e-8, lambda x: x >= 0.0, 'must be >= 0')
         if self.reward_scale != 'none':
             logging.info('reward_scale = %s: rewards are divided by the running std of the discounted return; reward_norm = %r '
                          'is not applied' % (self.reward_scale, self.reward_norm))
@@ -127,9 +140,7 @@ class IA2C:
             raise ValueError('ppo_epochs = %r: must be an integer >= 1' % raw)
         if self.ppo_epochs < 1:
             raise ValueError('ppo_epochs = %r: must be an integer >= 1' % raw)
-        self.ppo_clip = model_config.getfloat('ppo_clip', fallback=0.2)
-        if not 0.0 < self.ppo_clip < float('inf'):           # (nan fails both comparisons)
-            raise ValueError('ppo_clip = %r: must be finite and > 0' % self.ppo_clip)
+        self.ppo_clip = _cfg_float(model_config, 'ppo_clip', 0.2, lambda x: 0.0 < x < float('inf'), 'must be finite and > 0')
         if self.ppo_epochs > 1:
             if self.policy_cls.coupled:
                 # (as they refuse bf16x3) their in-launch hand-off guard and refused-batch rewind assume one optimiser step per batch
@@ -141,8 +152,11 @@ class IA2C:
         # optional controls of epochs 2..K (absent: off, nothing allocated, the path of before).  ppo_vclip: the value loss clipped
         # around the critic's values under the weights that produced the batch (PPO2 form); ppo_target_kl: once the mean approx_kl of
         # an epoch exceeds it, the remaining optimiser steps of the update change nothing -- decided on the device
-        self.ppo_vclip = self._ppo_control(model_config, 'ppo_vclip')
-        self.ppo_target_kl = self._ppo_control(model_config, 'ppo_target_kl')
+        self.ppo_vclip = _cfg_positive(model_config, 'ppo_vclip')
+        self.ppo_target_kl = _cfg_positive(model_config, 'ppo_target_kl')
+        for key in ('ppo_vclip', 'ppo_target_kl'):
+            if getattr(self, key) is not None and self.ppo_epochs == 1:
+                raise ValueError('%s = %r with ppo_epochs = 1: it acts on epochs 2..K only' % (key, model_config.get(key)))
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -181,21 +195,6 @@ class IA2C:
         self.sess = None                                  # the reference Trainer reads model.sess (TF leak)
         if total_step:
             self._init_train(model_config, self.distance_mask, coop_gamma)
-
-    def _ppo_control(self, model_config, key):
-        """An optional positive float of MODEL_CONFIG that only means something with ppo_epochs > 1 (None: absent)."""
-        raw = model_config.get(key, fallback=None)
-        if raw is None:
-            return None
-        try:
-            value = float(raw)
-        except ValueError:
-            raise ValueError('%s = %r: must be finite and > 0' % (key, raw))
-        if not 0.0 < value < float('inf'):                   # (nan fails both comparisons)
-            raise ValueError('%s = %r: must be finite and > 0' % (key, raw))
-        if self.ppo_epochs == 1:
-            raise ValueError('%s = %r with ppo_epochs = 1: it acts on epochs 2..K only' % (key, raw))
-        return value
 
     def _is_ma2c(self):
         return self.name.startswith('ma2c')
@@ -626,30 +625,50 @@ class IA2C:
         # the critic's neighbour one-hots (policies.py:66-68) are gathered from the action bytes inside the op
         action = self.buf_act.view(T * E, N)
         logits, v = p.heads(Hs, action)                                       # [N,T*E,A], [N,T*E]
-        adv = self._policy_adv().view(N, T * E)
+        adv = self._loss_adv()
         R = self.R.view(N, T * E)
-        if not self.identical_agent and not self.per_agent_optimizer:
-            # quirk Q6 (heterogeneous MA2C nets only, policies.py:241-254): the hetero branch builds prob_pi as
-            # [N,1,T], so `prob_pi * ADV` broadcasts to [N,N,T] and every agent's log-probability is weighted by the
-            # advantages of ALL agents: policy_loss = -sum_i mean_t(log pi_i[a] * sum_j ADV_j)
-            adv = adv.sum(dim=0, keepdim=True).expand(N, T * E).contiguous()
         if ops.a2c_loss_supported(self.n_a):
             per_agent, terms = ops.a2c_loss(logits, v, action, adv, R, self.v_coef, self.e_coef)
             self._terms = terms
             self.last_loss = (terms[:, 0], terms[:, 1], terms[:, 2], per_agent.detach())
             return per_agent.sum()
+        per_agent, cols = self._loss_torch(logits, v, action, adv, R)
+        self._terms = None
+        self.last_loss = tuple(c.detach() for c in cols) + (per_agent.detach(),)
+        return per_agent.sum()
+
+    def _loss_torch(self, logits, v, action, adv, R, logp_old=None, v_old=None):
+        """The loss where the native one does not reach (n_a > 8), in torch: -> per-agent total [N] (differentiable) and the terms as
+        a list of [N] columns -- (policy, value, entropy) of the A2C loss; with logp_old the clipped surrogate of ops.ppo_loss and
+        (approx_kl, clip_frac) behind the three; with v_old as well the clipped value term and vclip_frac, the sixth."""
+        eps, vclip = self.ppo_clip, self.ppo_vclip
         pi = torch.softmax(logits, dim=-1)
-        acts = action.t().long().unsqueeze(-1)                               # [N, T*E, 1]
         log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
         entropy = -(pi * log_pi).sum(-1)
-        logp_a = log_pi.gather(-1, acts).squeeze(-1)
-        policy_loss = -(logp_a * adv).mean(-1)                               # [N]
-        value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
+        logp_a = log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1)      # [N, T*E]
+        if logp_old is None:
+            policy_loss = -(logp_a * adv).mean(-1)                           # [N]
+        else:
+            dlp = logp_a - logp_old
+            rho = torch.exp(dlp)
+            policy_loss = -torch.min(rho * adv, torch.clamp(rho, 1.0 - eps, 1.0 + eps) * adv).mean(-1)
+        if v_old is None:
+            value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
+        else:           # the clipped value loss; outside the clip range the gradient follows the larger of the two errors
+            dvo = v - v_old
+            inside = dvo.abs() <= vclip
+            e1 = (R - v).pow(2)
+            e2 = (R - (v_old + torch.clamp(dvo, -vclip, vclip))).pow(2).detach()
+            value_loss = torch.where(inside | (e1 >= e2), e1, e2).mean(-1) * 0.5 * self.v_coef
         entropy_loss = -entropy.mean(-1) * self.e_coef
         per_agent = policy_loss + value_loss + entropy_loss
-        self._terms = None
-        self.last_loss = (policy_loss.detach(), value_loss.detach(), entropy_loss.detach(), per_agent.detach())
-        return per_agent.sum()
+        cols = [policy_loss, value_loss, entropy_loss]
+        if logp_old is not None:
+            with torch.no_grad():
+                cols += [(torch.expm1(dlp) - dlp).clamp_min(0.0).mean(-1), ((rho - 1.0).abs() > eps).to(F32).mean(-1)]
+                if v_old is not None:
+                    cols.append((dvo.abs() > vclip).to(F32).mean(-1))
+        return per_agent, cols
 
     def loss_terms(self):
         """[N,3] contiguous (policy, value, entropy) loss terms of the last update: the `terms` tensor of ops.heads_loss /
@@ -737,20 +756,33 @@ class IA2C:
         if not self._loss_backward_fused(Hs):
             loss = self._loss(Hs)
             loss.backward()
+        self._end_grads()
+
+    def _end_grads(self, kl_terms=None):
+        """Close a gradient pass: the flat gradient, masked, and the float behind it that rides through the pass's ONE all-reduce --
+        kl_terms (an epoch k >= 2 under the opt-in KL stop): that epoch's terms, whose approx_kl summed over agents goes there."""
+        ps = self.policy.params
         ps.end_backward()
         if ps.mask is not None:          # entries of variables the reference does not create (heterogeneous nets)
             ps.grad.mul_(ps.mask)
-        if self._status_on_wire:
+        if kl_terms is not None:
+            # free on these nets: only the coupled ones put their hand-off word there; `update_apply` decides on the sum
+            ops.ppo_kl_sum(kl_terms, ps.grad_tail)
+            self._ppo_gate_pending = True
+        elif self._status_on_wire:
             # a rank whose in-launch hand-off timed out contributes invalid gradients: every rank must refuse the step (and recover
-            # in lock-step, BatchedTrainer).  The status word rides in the float behind the gradient, inside the ONE all-reduce
+            # in lock-step, BatchedTrainer): the status word
             ps.grad_tail.copy_(ops.handoff_status(self.device)[:1])           # (int32 -> f32: an element-wise kernel)
 
     # ------------------------------------------------------------------ opt-in PPO epochs (MODEL_CONFIG ppo_epochs > 1)
     def _loss_adv(self):
-        """The advantage the policy term reads, [N,T*E] (with quirk Q6 of `_loss` on heterogeneous one-optimiser nets)."""
+        """The advantage the policy term reads, [N,T*E]."""
         N, T, E = self.n_agent, self.n_step, self.E
         adv = self._policy_adv().view(N, T * E)
         if not self.identical_agent and not self.per_agent_optimizer:
+            # quirk Q6 (heterogeneous MA2C nets only, policies.py:241-254): the hetero branch builds prob_pi as
+            # [N,1,T], so `prob_pi * ADV` broadcasts to [N,N,T] and every agent's log-probability is weighted by the
+            # advantages of ALL agents: policy_loss = -sum_i mean_t(log pi_i[a] * sum_j ADV_j)
             adv = adv.sum(dim=0, keepdim=True).expand(N, T * E).contiguous()
         return adv
 
@@ -782,36 +814,14 @@ class IA2C:
         Hs = p.unroll(self.buf_x[:T], FP, self.buf_done_pre, self.h_bw, self.c_bw, masked_steps=self.masked_steps)
         action = self.buf_act.view(T * E, N)
         logits, v = p.heads(Hs, action)
-        adv, R, eps = self._loss_adv(), self.R.view(N, T * E), self.ppo_clip
+        adv, R = self._loss_adv(), self.R.view(N, T * E)
         vclip = self.ppo_vclip
+        kw = {} if vclip is None else dict(v_old=self.ppo_v_old, vclip=vclip)
         if ops.ppo_loss_supported(self.n_a):
-            if vclip is None:
-                per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef)
-            else:
-                per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, eps, self.v_coef, self.e_coef,
-                                                v_old=self.ppo_v_old, vclip=vclip)
+            per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, self.ppo_clip, self.v_coef, self.e_coef, **kw)
         else:
-            pi = torch.softmax(logits, dim=-1)
-            log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
-            entropy = -(pi * log_pi).sum(-1)
-            dlp = log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1) - self.ppo_logp_old
-            rho = torch.exp(dlp)
-            policy_loss = -torch.min(rho * adv, torch.clamp(rho, 1.0 - eps, 1.0 + eps) * adv).mean(-1)
-            if vclip is None:
-                value_loss = (R - v).pow(2).mean(-1) * 0.5 * self.v_coef
-            else:           # the clipped value loss; outside the clip range the gradient follows the larger of the two errors
-                dvo = v - self.ppo_v_old
-                inside = dvo.abs() <= vclip
-                e1 = (R - v).pow(2)
-                e2 = (R - (self.ppo_v_old + torch.clamp(dvo, -vclip, vclip))).pow(2).detach()
-                value_loss = torch.where(inside | (e1 >= e2), e1, e2).mean(-1) * 0.5 * self.v_coef
-            entropy_loss = -entropy.mean(-1) * self.e_coef
-            per_agent = policy_loss + value_loss + entropy_loss
+            per_agent, cols = self._loss_torch(logits, v, action, adv, R, self.ppo_logp_old, kw.get('v_old'))
             with torch.no_grad():
-                cols = [policy_loss, value_loss, entropy_loss, (torch.expm1(dlp) - dlp).clamp_min(0.0).mean(-1),
-                        ((rho - 1.0).abs() > eps).to(F32).mean(-1)]
-                if vclip is not None:
-                    cols.append((dvo.abs() > vclip).to(F32).mean(-1))
                 terms = torch.stack(cols, dim=1)
         self.ppo_stats[k - 1].copy_(terms[:, 3:5])
         if vclip is not None:
@@ -819,14 +829,7 @@ class IA2C:
         t3 = self._terms = terms[:, :3].contiguous()
         self.last_loss = (t3[:, 0], t3[:, 1], t3[:, 2], per_agent.detach())
         per_agent.sum().backward()
-        ps.end_backward()
-        if ps.mask is not None:
-            ps.grad.mul_(ps.mask)
-        if self.ppo_target_kl is not None:
-            # opt-in KL stop: this epoch's sum of approx_kl over agents rides in the float behind the gradient through the epoch's one
-            # all-reduce (free on these nets: only the coupled ones put their hand-off word there); `update_apply` decides on it
-            ops.ppo_kl_sum(terms, ps.grad_tail)
-            self._ppo_gate_pending = True
+        self._end_grads(kl_terms=None if self.ppo_target_kl is None else terms)
 
     @property
     def ppo_vclip_frac(self):
@@ -876,19 +879,15 @@ class IA2C:
                 ops.ppo_kl_gate(ps.grad_tail, self.world_size * self.n_agent, self.ppo_target_kl, self.ppo_gate)
                 self._ppo_gate_pending = False
             kw['stop'] = self.ppo_gate
-        if self.optimizer == 'adam':         # opt-in: the same [G,P] views, clip, scale, guard and lr; Adam's slots and device counter
-            shape = (self.n_agent, ps.P) if self.per_agent_optimizer else (1, self.n_agent * ps.P)
-            ops.adam_clip(ps.flat.view(shape), ps.grad.view(shape), ps.adam_m.view(shape), ps.adam_v.view(shape), ps.scratch,
-                          ps.adam_t, lr, self.adam_beta1, self.adam_beta2, self.adam_epsilon, self.max_grad_norm, scale,
-                          self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
-        elif self.per_agent_optimizer:
-            ops.rmsprop_tf_clip(ps.flat, ps.grad, ps.ms, ps.scratch, lr, self.rmsp_alpha, self.rmsp_epsilon,
-                                self.max_grad_norm, scale, self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
+        # [G,P]: one group and one clip norm per agent (IA2C) or one over all agents
+        shape = (self.n_agent, ps.P) if self.per_agent_optimizer else (1, self.n_agent * ps.P)
+        w, g = ps.flat.view(shape), ps.grad.view(shape)
+        if self.optimizer == 'adam':         # opt-in: the same clip, scale, guard and lr; Adam's slots and device counter
+            ops.adam_clip(w, g, ps.adam_m.view(shape), ps.adam_v.view(shape), ps.scratch, ps.adam_t, lr, self.adam_beta1,
+                          self.adam_beta2, self.adam_epsilon, self.max_grad_norm, scale, self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
         else:
-            n = self.n_agent * ps.P
-            ops.rmsprop_tf_clip(ps.flat.view(1, n), ps.grad.view(1, n), ps.ms.view(1, n), ps.scratch, lr,
-                                self.rmsp_alpha, self.rmsp_epsilon, self.max_grad_norm, scale, self.grad_norm,
-                                lr_dev=lr_dev, guard=guard, **kw)
+            ops.rmsprop_tf_clip(w, g, ps.ms.view(shape), ps.scratch, lr, self.rmsp_alpha, self.rmsp_epsilon, self.max_grad_norm, scale,
+                                self.grad_norm, lr_dev=lr_dev, guard=guard, **kw)
         self._after_apply()
         if rotate:
             T = self.n_step

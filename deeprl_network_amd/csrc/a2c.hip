@@ -221,15 +221,11 @@ __global__ __launch_bounds__(256) void nstep_kernel(
         }
         for (int t = T - 1; t >= 0; --t) {
             const double keep = 1.0 - (double)done_post[(int64_t)t * E + e];
-            if (!spatial) {
-                R = (double)r[(int64_t)t * E + e] + gamma * R * keep;
-            } else {
-                R = gamma * R * keep;
-                const float* rt = r + ((int64_t)t * E + e) * N;
-                double add = 0.0;
-                for (int j = 0; j < N; ++j) add += s_w[n * N + j] * (double)rt[j];
-                R += add;
-            }
+            R = gamma * R * keep;
+            const float* rt = r + ((int64_t)t * E + e) * N;
+            double add = 0.0;
+            for (int j = 0; j < N; ++j) add += s_w[n * N + j] * (double)rt[j];
+            R += add;
             const int64_t o = ((int64_t)n * T + t) * E + e;
             R_out[o] = (float)R;
             adv_out[o] = (float)(R - (double)v[((int64_t)t * N + n) * E + e]);
@@ -447,6 +443,19 @@ __device__ __forceinline__ void sumsq_block(const int64_t P, const float* __rest
     if (threadIdx.x == 0) partial[grp * SUMSQ_BLOCKS + blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
 }
 
+// Fail closed: a hand-off kernel of this batch reported a wave that gave up waiting (status[0] != 0, see nmarl_handoff_status in
+// nmarl.h) -- its gradients are invalid, so an optimiser step applies NOTHING: weights and slots keep their values, the skipped
+// update is counted (status[1], from one thread of the launch) and the host re-runs the batch on the launch-per-step path.
+__device__ __forceinline__ bool status_raised(const int32_t* status) {
+    return status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
+__device__ __forceinline__ bool step_refused(int32_t* status) {
+    if (!status_raised(status)) return false;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(status + 1, 1);
+    return true;
+}
+
 __global__ __launch_bounds__(256) void sumsq_kernel(const int64_t P, const float* __restrict__ g,
                                                     float* __restrict__ partial /*[G, SUMSQ_BLOCKS]*/) {
     sumsq_block(P, g, partial, blockDim.x, gridDim.x);
@@ -457,13 +466,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(
     const float* __restrict__ partial, const float* __restrict__ lr_ptr, const float lr_host, const float rho,
     const float eps, const float max_norm, const float grad_scale, float* __restrict__ norm_out, int32_t* status) {
     const int grp = blockIdx.y;
-    // fail closed: a hand-off kernel of this batch reported a wave that gave up waiting (status[0] != 0, see
-    // nmarl_handoff_status in nmarl.h) -- its gradients are invalid, so NOTHING is applied: weights and slots keep their
-    // values, the skipped update is counted (status[1]) and the host re-runs the batch on the launch-per-step path
-    if (status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(status + 1, 1);
-        return;
-    }
+    if (step_refused(status)) return;
     // every block re-reduces its group's 64 partials in the same fixed order
     const float tot = nmarl_ordered_sum(partial + grp * SUMSQ_BLOCKS, 1, SUMSQ_BLOCKS);
     const float norm = sqrtf(tot) * fabsf(grad_scale);
@@ -486,8 +489,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(
 // lets the step through; the SECOND only reads it -- no launch reads it for the bias correction and writes it.
 __global__ __launch_bounds__(256) void adam_sumsq_kernel(const int64_t P, const float* __restrict__ g, float* __restrict__ partial,
                                                          int32_t* __restrict__ step, const int32_t* status) {
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 &&
-        !(status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && !status_raised(status))
         step[0] = step[0] + 1;                         // a refused batch keeps t (the host re-runs it)
     sumsq_block(P, g, partial, blockDim.x, gridDim.x);
 }
@@ -498,11 +500,7 @@ __global__ __launch_bounds__(256) void adam_kernel(
     const float beta1, const float beta2, const float eps, const float max_norm, const float grad_scale,
     float* __restrict__ norm_out, int32_t* status) {
     const int grp = blockIdx.y;
-    // fail closed, exactly as rmsprop_kernel: w, m, v keep their bits (and adam_sumsq_kernel left the counter alone)
-    if (status && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(status + 1, 1);
-        return;
-    }
+    if (step_refused(status)) return;                  // w, m, v keep their bits (and adam_sumsq_kernel left the counter alone)
     // bias corrections 1 - beta^t, once per block in float64 (t = the counter the first launch advanced), then broadcast
     __shared__ float bc[2];
     if (threadIdx.x == 0) {
@@ -790,109 +788,9 @@ __global__ __launch_bounds__(256) void reward_scale_apply_kernel(const int64_t n
 #undef NMARL_RS
 }
 
-// A2C loss of Policy.prepare_loss (policies.py:20-30; NCMultiAgentPolicy 232-255) for all agents and rows:
-//   pi = softmax(logits); log_pi = log(clip(pi, 1e-10, 1)); H = -sum pi log_pi
-//   policy = -mean(log_pi[a] ADV);  value = 0.5 v_coef mean((R - v)^2);  entropy = -e_coef mean(H)
-// fwd: per-block partial sums of the three terms -> a2c_loss_reduce_kernel (fixed order).  bwd: the closed-form
-// gradient w.r.t. logits and v (clip passes the gradient where 1e-10 <= pi), scaled by the per-agent upstream g.
-// logits [N,rows,A] with row pitch l_row (a column block of the heads' GEMM output), everything else [N,rows];
-// action [rows,N] u8.  One pass each instead of ~35 elementwise / reduction launches over [N,rows,A].
 constexpr int LOSS_MAXA = 8;
 
-template <bool BWD>
-__global__ __launch_bounds__(256) void a2c_loss_kernel(const int64_t rows, const int N, const int A, const int rows_per_block,
-                                                       const float* __restrict__ logits, const int64_t l_sn, const int64_t l_row,
-                                                       const float* __restrict__ v, const uint8_t* __restrict__ action,
-                                                       const float* __restrict__ adv, const float* __restrict__ R,
-                                                       const float v_coef, const float e_coef, const float* __restrict__ g_up,
-                                                       float* __restrict__ partial, float* __restrict__ dlogits,
-                                                       float* __restrict__ dv) {
-    const int n = blockIdx.y;
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-    const float inv_m = 1.0f / (float)rows;
-    const float gn = BWD ? g_up[n] * inv_m : 0.0f;
-    float s_pol = 0.0f, s_val = 0.0f, s_ent = 0.0f;
-    for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
-        const float* l = logits + (int64_t)n * l_sn + r * l_row;
-        float p[LOSS_MAXA], lp[LOSS_MAXA];
-        float m = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < LOSS_MAXA; ++k) {
-            p[k] = k < A ? l[k] : -INFINITY;
-            m = fmaxf(m, p[k]);
-        }
-        float z = 0.0f;
-#pragma unroll
-        for (int k = 0; k < LOSS_MAXA; ++k) {
-            p[k] = k < A ? expf(p[k] - m) : 0.0f;
-            z += p[k];
-        }
-        const int a = action[r * N + n];
-        float H = 0.0f, lpa = 0.0f, pa = 0.0f;
-#pragma unroll
-        for (int k = 0; k < LOSS_MAXA; ++k) {
-            p[k] = p[k] / z;
-            lp[k] = logf(fminf(fmaxf(p[k], 1e-10f), 1.0f));
-            if (k < A) H -= p[k] * lp[k];
-            if (k == a) { lpa = lp[k]; pa = p[k]; }
-        }
-        const int64_t i = (int64_t)n * rows + r;
-        const float ad = adv[i], dR = R[i] - v[i];
-        if (!BWD) {
-            s_pol -= lpa * ad;
-            s_val += dR * dR;
-            s_ent += H;
-        } else {
-            // g_k = dH/dpi_k = -(log_pi_k + c_k), c_k = [pi_k >= 1e-10];  dH/dlogit_j = pi_j (g_j - sum_k pi_k g_k)
-            float gbar = 0.0f;
-#pragma unroll
-            for (int k = 0; k < LOSS_MAXA; ++k)
-                if (k < A) gbar += p[k] * -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
-            const float ca = pa >= 1e-10f ? 1.0f : 0.0f;
-            float* dl = dlogits + i * A;
-#pragma unroll
-            for (int k = 0; k < LOSS_MAXA; ++k)
-                if (k < A) {
-                    const float gk = -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
-                    const float d_pol = -ad * ca * ((k == a ? 1.0f : 0.0f) - p[k]);
-                    const float d_ent = -e_coef * p[k] * (gk - gbar);
-                    dl[k] = gn * (d_pol + d_ent);
-                }
-            dv[i] = -gn * v_coef * dR;
-        }
-    }
-    if (!BWD) {
-        __shared__ float red[4][3];
-        for (int off = 32; off > 0; off >>= 1) {
-            s_pol += __shfl_down(s_pol, off, 64);
-            s_val += __shfl_down(s_val, off, 64);
-            s_ent += __shfl_down(s_ent, off, 64);
-        }
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        if (lane == 0) { red[w][0] = s_pol; red[w][1] = s_val; red[w][2] = s_ent; }
-        __syncthreads();
-        if (threadIdx.x < 3)
-            partial[((int64_t)n * gridDim.x + blockIdx.x) * 3 + threadIdx.x] =
-                ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    }
-}
-
-__global__ __launch_bounds__(64) void a2c_loss_reduce_kernel(const int C, const int64_t rows, const float v_coef, const float e_coef,
-                                                             const float* __restrict__ partial, float* __restrict__ out /*[N,3]*/) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= 3) return;
-    float s = nmarl_ordered_sum(partial + (int64_t)n * C * 3 + k, 3, C);
-    s /= (float)rows;
-    out[n * 3 + k] = k == 0 ? s : k == 1 ? s * 0.5f * v_coef : -s * e_coef;
-}
-
-// Opt-in PPO epochs (MODEL_CONFIG ppo_epochs > 1; the reference has none): the clipped surrogate against the behaviour policy's
-// log-probabilities logp_old [N,rows], for epochs 2..K of an update.  Softmax, clamp and entropy are a2c_loss_kernel's, in its
-// operation order, so that at logp_old = lp_a (rho = 1.0f exactly) the gradient has the bits of the A2C one.
-//   rho = exp(lp_a - logp_old);  policy = -mean(min(rho ADV, clip(rho, 1-eps, 1+eps) ADV));  value, entropy: as above
-//   approx_kl = mean((rho - 1) - (lp_a - logp_old));  clip_frac = mean(|rho - 1| > eps)
-//   d policy / d logit_k = -ADV rho gate c_a (delta_ka - pi_k);  gate = 0 where (ADV > 0, rho > 1+eps) or (ADV < 0, rho < 1-eps)
+// One row's softmax, clamped log and entropy, A <= LOSS_MAXA probabilities in registers (lanes k >= A hold 0); lpa / pa: those of action a.
 __device__ __forceinline__ void loss_row_softmax(const float* __restrict__ l, const int A, const int a, float (&p)[LOSS_MAXA],
                                                  float (&lp)[LOSS_MAXA], float& H, float& lpa, float& pa) {
     float m = -INFINITY;
@@ -917,6 +815,97 @@ __device__ __forceinline__ void loss_row_softmax(const float* __restrict__ l, co
     }
 }
 
+// dl[k] = gn (d policy + d entropy) / d logit_k of a row, `w_pol` the weight of the policy term (ADV, or ADV rho gate of the surrogate):
+//   g_k = dH/dpi_k = -(log_pi_k + c_k), c_k = [pi_k >= 1e-10];  dH/dlogit_j = pi_j (g_j - sum_k pi_k g_k)
+__device__ __forceinline__ void loss_row_dlogits(const int A, const int a, const float (&p)[LOSS_MAXA], const float (&lp)[LOSS_MAXA],
+                                                 const float pa, const float w_pol, const float e_coef, const float gn,
+                                                 float* __restrict__ dl) {
+    float gbar = 0.0f;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXA; ++k)
+        if (k < A) gbar += p[k] * -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
+    const float ca = pa >= 1e-10f ? 1.0f : 0.0f;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXA; ++k)
+        if (k < A) {
+            const float gk = -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
+            const float d_pol = -w_pol * ca * ((k == a ? 1.0f : 0.0f) - p[k]);
+            const float d_ent = -e_coef * p[k] * (gk - gbar);
+            dl[k] = gn * (d_pol + d_ent);
+        }
+}
+
+// The block's sums of NT per-thread partial columns, in a fixed order (lanes by shuffle, then the four waves as ((w0 + w1) + w2) + w3),
+// to the block's slot of agent n's `partial` [N, gridDim.x, NT] (the index is formed inside the guarded store, by the NT lanes that write)
+template <int NT>
+__device__ __forceinline__ void loss_block_partials(float (&s)[NT], float* __restrict__ partial, const int n) {
+    __shared__ float red[4][NT];
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k) s[k] += __shfl_down(s[k], off, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k) red[w][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NT)
+        partial[((int64_t)n * gridDim.x + blockIdx.x) * NT + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// A2C loss of Policy.prepare_loss (policies.py:20-30; NCMultiAgentPolicy 232-255) for all agents and rows:
+//   pi = softmax(logits); log_pi = log(clip(pi, 1e-10, 1)); H = -sum pi log_pi
+//   policy = -mean(log_pi[a] ADV);  value = 0.5 v_coef mean((R - v)^2);  entropy = -e_coef mean(H)
+// fwd: per-block partial sums of the three terms -> loss_reduce_kernel<3> (fixed order).  bwd: the closed-form
+// gradient w.r.t. logits and v (clip passes the gradient where 1e-10 <= pi), scaled by the per-agent upstream g.
+// logits [N,rows,A] with row pitch l_row (a column block of the heads' GEMM output), everything else [N,rows];
+// action [rows,N] u8.  One pass each instead of ~35 elementwise / reduction launches over [N,rows,A].
+template <bool BWD>
+__global__ __launch_bounds__(256) void a2c_loss_kernel(const int64_t rows, const int N, const int A, const int rows_per_block,
+                                                       const float* __restrict__ logits, const int64_t l_sn, const int64_t l_row,
+                                                       const float* __restrict__ v, const uint8_t* __restrict__ action,
+                                                       const float* __restrict__ adv, const float* __restrict__ R,
+                                                       const float v_coef, const float e_coef, const float* __restrict__ g_up,
+                                                       float* __restrict__ partial, float* __restrict__ dlogits,
+                                                       float* __restrict__ dv) {
+    const int n = blockIdx.y;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+    const float inv_m = 1.0f / (float)rows;
+    const float gn = BWD ? g_up[n] * inv_m : 0.0f;
+    float s[3] = {0.0f, 0.0f, 0.0f};                               // policy, value, entropy
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
+        const int a = action[r * N + n];
+        float p[LOSS_MAXA], lp[LOSS_MAXA], H, lpa, pa;
+        loss_row_softmax(logits + (int64_t)n * l_sn + r * l_row, A, a, p, lp, H, lpa, pa);
+        const int64_t i = (int64_t)n * rows + r;
+        const float ad = adv[i], dR = R[i] - v[i];
+        if (!BWD) {
+            s[0] -= lpa * ad;
+            s[1] += dR * dR;
+            s[2] += H;
+        } else {
+            loss_row_dlogits(A, a, p, lp, pa, ad, e_coef, gn, dlogits + i * A);
+            dv[i] = -gn * v_coef * dR;
+        }
+    }
+    if (!BWD) loss_block_partials(s, partial, n);
+}
+
+// Second stage of a loss forward: column k of the C per-block partials of agent n in index order, / rows; column 1 (value) times
+// 0.5 v_coef, column 2 (entropy) times -e_coef, every other column the plain mean.  NT = 3 (A2C), 5 (PPO), 6 (PPO with value clip).
+template <int NT>
+__global__ __launch_bounds__(64) void loss_reduce_kernel(const int C, const int64_t rows, const float v_coef, const float e_coef,
+                                                         const float* __restrict__ partial, float* __restrict__ out /*[N,NT]*/) {
+    const int n = blockIdx.x, k = threadIdx.x;
+    if (k >= NT) return;
+    float s = nmarl_ordered_sum(partial + (int64_t)n * C * NT + k, NT, C);
+    s /= (float)rows;
+    out[n * NT + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
+}
+
 // logp_out[n, r] = log(clip(softmax(logits[n, r])[action[r, n]], 1e-10, 1)): one thread per row
 __global__ __launch_bounds__(256) void ppo_logp_kernel(const int64_t rows, const int N, const int A, const float* __restrict__ logits,
                                                        const int64_t l_sn, const int64_t l_row, const uint8_t* __restrict__ action,
@@ -929,8 +918,14 @@ __global__ __launch_bounds__(256) void ppo_logp_kernel(const int64_t rows, const
     logp_out[(int64_t)n * rows + r] = lpa;
 }
 
-// VCLIP (opt-in MODEL_CONFIG ppo_vclip; the instantiations without it are the code of before): the PPO2 clipped value loss against
-// v_old [N,rows], one more 4-byte load per row and a sixth partial column:
+// Opt-in PPO epochs (MODEL_CONFIG ppo_epochs > 1; the reference has none): the clipped surrogate against the behaviour policy's
+// log-probabilities logp_old [N,rows], for epochs 2..K of an update.  The row arithmetic is the A2C loss's (loss_row_softmax,
+// loss_row_dlogits), so that at logp_old = lp_a (rho = 1.0f exactly) the gradient has the bits of the A2C one.
+//   rho = exp(lp_a - logp_old);  policy = -mean(min(rho ADV, clip(rho, 1-eps, 1+eps) ADV));  value, entropy: as above
+//   approx_kl = mean((rho - 1) - (lp_a - logp_old));  clip_frac = mean(|rho - 1| > eps)
+//   d policy / d logit_k = -ADV rho gate c_a (delta_ka - pi_k);  gate = 0 where (ADV > 0, rho > 1+eps) or (ADV < 0, rho < 1-eps)
+// VCLIP (opt-in MODEL_CONFIG ppo_vclip): the PPO2 clipped value loss against v_old [N,rows], one more 4-byte load per row and a
+// sixth partial column:
 //   d = v - v_old;  inside = |d| <= vclip;  v_c = v_old + clip(d, -vclip, +vclip);  e1 = (R - v)^2;  e2 = (R - v_c)^2
 //   e = inside ? e1 : max(e1, e2)  (inside is tested: v_old + (v - v_old) is not v in fp32);  value = 0.5 v_coef mean(e)
 //   d value / d v = -v_coef (R - v) / rows where inside or e1 >= e2, else 0;  vclip_frac = mean(|d| > vclip)
@@ -951,7 +946,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const
     const float inv_m = 1.0f / (float)rows;
     const float gn = BWD ? g_up[n] * inv_m : 0.0f;
     const float lo_c = 1.0f - clip, hi_c = 1.0f + clip;
-    float s_pol = 0.0f, s_val = 0.0f, s_ent = 0.0f, s_kl = 0.0f, s_cf = 0.0f, s_vf = 0.0f;
+    float s[NT] = {};                                              // policy, value, entropy, approx_kl, clip_frac(, vclip_frac)
     for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
         const int a = action[r * N + n];
         float p[LOSS_MAXA], lp[LOSS_MAXA], H, lpa, pa;
@@ -973,76 +968,25 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const int64_t rows, const
             over = fabsf(d) > vclip ? 1.0f : 0.0f;
         }
         if (!BWD) {
-            s_pol -= fminf(rho * ad, fminf(fmaxf(rho, lo_c), hi_c) * ad);
+            s[0] -= fminf(rho * ad, fminf(fmaxf(rho, lo_c), hi_c) * ad);
             if (VCLIP) {
-                s_val += e_v;
-                s_vf += over;
+                s[1] += e_v;
+                s[NT - 1] += over;
             } else {
-                s_val += dR * dR;
+                s[1] += dR * dR;
             }
-            s_ent += H;
+            s[2] += H;
             // (rho - 1) - log rho >= 0; rho - 1 taken as expm1 of the difference: expf's rounding (6e-8) would swamp a term of d^2 / 2
-            s_kl += fmaxf(expm1f(dlp) - dlp, 0.0f);
-            s_cf += fabsf(rho - 1.0f) > clip ? 1.0f : 0.0f;
+            s[3] += fmaxf(expm1f(dlp) - dlp, 0.0f);
+            s[4] += fabsf(rho - 1.0f) > clip ? 1.0f : 0.0f;
         } else {
             // the clipped branch is the smaller one, and constant in rho, exactly where the gate closes
             const bool closed = (ad > 0.0f && rho > hi_c) || (ad < 0.0f && rho < lo_c);
-            const float adg = ad * (closed ? 0.0f : rho);          // rho = 1.0f: ad itself, and from here on a2c_loss_kernel's lines
-            float gbar = 0.0f;
-#pragma unroll
-            for (int k = 0; k < LOSS_MAXA; ++k)
-                if (k < A) gbar += p[k] * -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
-            const float ca = pa >= 1e-10f ? 1.0f : 0.0f;
-            float* dl = dlogits + i * A;
-#pragma unroll
-            for (int k = 0; k < LOSS_MAXA; ++k)
-                if (k < A) {
-                    const float gk = -(lp[k] + (p[k] >= 1e-10f ? 1.0f : 0.0f));
-                    const float d_pol = -adg * ca * ((k == a ? 1.0f : 0.0f) - p[k]);
-                    const float d_ent = -e_coef * p[k] * (gk - gbar);
-                    dl[k] = gn * (d_pol + d_ent);
-                }
+            loss_row_dlogits(A, a, p, lp, pa, ad * (closed ? 0.0f : rho), e_coef, gn, dlogits + i * A);   // rho = 1.0f: ad itself
             dv[i] = v_open ? -gn * v_coef * dR : 0.0f;
         }
     }
-    if (!BWD) {
-        __shared__ float red[4][NT];
-        for (int off = 32; off > 0; off >>= 1) {
-            s_pol += __shfl_down(s_pol, off, 64);
-            s_val += __shfl_down(s_val, off, 64);
-            s_ent += __shfl_down(s_ent, off, 64);
-            s_kl += __shfl_down(s_kl, off, 64);
-            s_cf += __shfl_down(s_cf, off, 64);
-            if (VCLIP) s_vf += __shfl_down(s_vf, off, 64);
-        }
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        if (lane == 0) { red[w][0] = s_pol; red[w][1] = s_val; red[w][2] = s_ent; red[w][3] = s_kl; red[w][4] = s_cf; }
-        if (VCLIP && lane == 0) red[w][NT - 1] = s_vf;
-        __syncthreads();
-        if (threadIdx.x < NT)
-            partial[((int64_t)n * gridDim.x + blockIdx.x) * NT + threadIdx.x] =
-                ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    }
-}
-
-__global__ __launch_bounds__(64) void ppo_loss_reduce_kernel(const int C, const int64_t rows, const float v_coef, const float e_coef,
-                                                             const float* __restrict__ partial, float* __restrict__ out /*[N,5]*/) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= 5) return;
-    float s = nmarl_ordered_sum(partial + (int64_t)n * C * 5 + k, 5, C);
-    s /= (float)rows;
-    out[n * 5 + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
-}
-
-// the value-clip instantiation's second stage: six columns, the sixth vclip_frac
-__global__ __launch_bounds__(64) void ppo_loss_vclip_reduce_kernel(const int C, const int64_t rows, const float v_coef,
-                                                                   const float e_coef, const float* __restrict__ partial,
-                                                                   float* __restrict__ out /*[N,6]*/) {
-    const int n = blockIdx.x, k = threadIdx.x;
-    if (k >= 6) return;
-    float s = nmarl_ordered_sum(partial + (int64_t)n * C * 6 + k, 6, C);
-    s /= (float)rows;
-    out[n * 6 + k] = k == 1 ? s * 0.5f * v_coef : k == 2 ? -s * e_coef : s;
+    if (!BWD) loss_block_partials(s, partial, n);
 }
 
 // Opt-in KL stop of the PPO epochs (MODEL_CONFIG ppo_target_kl), no host synchronisation.  gate: int32 x 4 owned by the model --
@@ -1268,30 +1212,52 @@ static int loss_chunks(int64_t rows, int N) {
 
 extern "C" int nmarl_a2c_loss_chunks(int64_t rows, int32_t N) { return rows > 0 && N > 0 ? loss_chunks(rows, N) : 0; }
 
-extern "C" int nmarl_a2c_loss_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
-                                  const float* v, const uint8_t* action, const float* adv, const float* R, float v_coef,
-                                  float e_coef, float* partial, float* loss_out, void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !partial || !loss_out)
-        return NMARL_EINVAL;
+static bool ppo_clip_ok(float clip) { return clip > 0.0f && clip <= 3.402823466e+38f; }      // (NaN fails both, inf the second)
+
+enum LossKind { LOSS_A2C, LOSS_PPO, LOSS_PPO_VCLIP };
+
+// The loss entries' one argument check and launch.  Forward: the loss kernel and its second stage (partial, loss_out must be there);
+// backward: the loss kernel alone (g_up, dlogits, dv must be there).  logp_old / clip and v_old / vclip are checked for the kinds that read them.
+static int loss_launch(LossKind kind, bool bwd, int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                       const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
+                       const float* v_old, float clip, float vclip, float v_coef, float e_coef, const float* g_up, float* partial,
+                       float* loss_out, float* dlogits, float* dv, void* stream) {
+    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R) return NMARL_EINVAL;
+    if (kind != LOSS_A2C && (!logp_old || !ppo_clip_ok(clip))) return NMARL_EINVAL;
+    if (kind == LOSS_PPO_VCLIP && (!v_old || !ppo_clip_ok(vclip))) return NMARL_EINVAL;
+    if (bwd ? (!g_up || !dlogits || !dv) : (!partial || !loss_out)) return NMARL_EINVAL;
     const int C = loss_chunks(rows, N);
     const int rpb = (int)((rows + C - 1) / C);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(a2c_loss_kernel<false>, dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action, adv, R,
-                       v_coef, e_coef, (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(a2c_loss_reduce_kernel, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, partial, loss_out);
+    if (kind == LOSS_A2C) {
+        const auto k = bwd ? a2c_loss_kernel<true> : a2c_loss_kernel<false>;
+        hipLaunchKernelGGL(k, dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action, adv, R, v_coef, e_coef, g_up,
+                           partial, dlogits, dv);
+    } else {
+        const auto k = kind == LOSS_PPO ? (bwd ? ppo_loss_kernel<true, false> : ppo_loss_kernel<false, false>)
+                                        : (bwd ? ppo_loss_kernel<true, true> : ppo_loss_kernel<false, true>);
+        hipLaunchKernelGGL(k, dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action, adv, R, logp_old, clip,
+                           v_coef, e_coef, g_up, partial, dlogits, dv, v_old, vclip);
+    }
+    if (!bwd) {
+        const auto k = kind == LOSS_A2C ? loss_reduce_kernel<3> : kind == LOSS_PPO ? loss_reduce_kernel<5> : loss_reduce_kernel<6>;
+        hipLaunchKernelGGL(k, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, (const float*)partial, loss_out);
+    }
     return nmarl_check_launch();
+}
+
+extern "C" int nmarl_a2c_loss_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
+                                  const float* v, const uint8_t* action, const float* adv, const float* R, float v_coef,
+                                  float e_coef, float* partial, float* loss_out, void* stream) {
+    return loss_launch(LOSS_A2C, false, rows, N, A, logits, l_sn, l_row, v, action, adv, R, nullptr, nullptr, 0.0f, 0.0f, v_coef, e_coef,
+                       nullptr, partial, loss_out, nullptr, nullptr, stream);
 }
 
 extern "C" int nmarl_a2c_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
                                   const float* v, const uint8_t* action, const float* adv, const float* R, float v_coef,
                                   float e_coef, const float* g_up, float* dlogits, float* dv, void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !g_up || !dlogits || !dv)
-        return NMARL_EINVAL;
-    const int C = loss_chunks(rows, N);
-    const int rpb = (int)((rows + C - 1) / C);
-    hipLaunchKernelGGL(a2c_loss_kernel<true>, dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb, logits,
-                       l_sn, l_row, v, action, adv, R, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv);
-    return nmarl_check_launch();
+    return loss_launch(LOSS_A2C, true, rows, N, A, logits, l_sn, l_row, v, action, adv, R, nullptr, nullptr, 0.0f, 0.0f, v_coef, e_coef,
+                       g_up, nullptr, nullptr, dlogits, dv, stream);
 }
 
 extern "C" int nmarl_ppo_logp(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
@@ -1302,69 +1268,37 @@ extern "C" int nmarl_ppo_logp(int64_t rows, int32_t N, int32_t A, const float* l
     return nmarl_check_launch();
 }
 
-extern "C" int nmarl_ppo_loss_chunks(int64_t rows, int32_t N) { return rows > 0 && N > 0 ? loss_chunks(rows, N) : 0; }
-
-static bool ppo_clip_ok(float clip) { return clip > 0.0f && clip <= 3.402823466e+38f; }      // (NaN fails both, inf the second)
+extern "C" int nmarl_ppo_loss_chunks(int64_t rows, int32_t N) { return nmarl_a2c_loss_chunks(rows, N); }
 
 extern "C" int nmarl_ppo_loss_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
                                   const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
                                   float clip, float v_coef, float e_coef, float* partial, float* loss_out, void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
-        !partial || !loss_out || !ppo_clip_ok(clip))
-        return NMARL_EINVAL;
-    const int C = loss_chunks(rows, N);
-    const int rpb = (int)((rows + C - 1) / C);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(ppo_loss_kernel<false>, dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action, adv, R,
-                       logp_old, clip, v_coef, e_coef, (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(ppo_loss_reduce_kernel, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, partial, loss_out);
-    return nmarl_check_launch();
+    return loss_launch(LOSS_PPO, false, rows, N, A, logits, l_sn, l_row, v, action, adv, R, logp_old, nullptr, clip, 0.0f, v_coef, e_coef,
+                       nullptr, partial, loss_out, nullptr, nullptr, stream);
 }
 
 extern "C" int nmarl_ppo_loss_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
                                   const float* v, const uint8_t* action, const float* adv, const float* R, const float* logp_old,
                                   float clip, float v_coef, float e_coef, const float* g_up, float* dlogits, float* dv,
                                   void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
-        !g_up || !dlogits || !dv || !ppo_clip_ok(clip))
-        return NMARL_EINVAL;
-    const int C = loss_chunks(rows, N);
-    const int rpb = (int)((rows + C - 1) / C);
-    hipLaunchKernelGGL(ppo_loss_kernel<true>, dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb, logits,
-                       l_sn, l_row, v, action, adv, R, logp_old, clip, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv);
-    return nmarl_check_launch();
+    return loss_launch(LOSS_PPO, true, rows, N, A, logits, l_sn, l_row, v, action, adv, R, logp_old, nullptr, clip, 0.0f, v_coef, e_coef,
+                       g_up, nullptr, nullptr, dlogits, dv, stream);
 }
 
 extern "C" int nmarl_ppo_loss_vclip_fwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
                                         const float* v, const uint8_t* action, const float* adv, const float* R,
                                         const float* logp_old, const float* v_old, float clip, float vclip, float v_coef,
                                         float e_coef, float* partial, float* loss_out, void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
-        !v_old || !partial || !loss_out || !ppo_clip_ok(clip) || !ppo_clip_ok(vclip))
-        return NMARL_EINVAL;
-    const int C = loss_chunks(rows, N);
-    const int rpb = (int)((rows + C - 1) / C);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((ppo_loss_kernel<false, true>), dim3(C, N), dim3(256), 0, st, rows, N, A, rpb, logits, l_sn, l_row, v, action,
-                       adv, R, logp_old, clip, v_coef, e_coef, (const float*)nullptr, partial, (float*)nullptr, (float*)nullptr,
-                       v_old, vclip);
-    hipLaunchKernelGGL(ppo_loss_vclip_reduce_kernel, dim3(N), dim3(64), 0, st, C, rows, v_coef, e_coef, partial, loss_out);
-    return nmarl_check_launch();
+    return loss_launch(LOSS_PPO_VCLIP, false, rows, N, A, logits, l_sn, l_row, v, action, adv, R, logp_old, v_old, clip, vclip, v_coef,
+                       e_coef, nullptr, partial, loss_out, nullptr, nullptr, stream);
 }
 
 extern "C" int nmarl_ppo_loss_vclip_bwd(int64_t rows, int32_t N, int32_t A, const float* logits, int64_t l_sn, int64_t l_row,
                                         const float* v, const uint8_t* action, const float* adv, const float* R,
                                         const float* logp_old, const float* v_old, float clip, float vclip, float v_coef,
                                         float e_coef, const float* g_up, float* dlogits, float* dv, void* stream) {
-    if (rows <= 0 || N <= 0 || A <= 0 || A > LOSS_MAXA || l_row < A || !logits || !v || !action || !adv || !R || !logp_old ||
-        !v_old || !g_up || !dlogits || !dv || !ppo_clip_ok(clip) || !ppo_clip_ok(vclip))
-        return NMARL_EINVAL;
-    const int C = loss_chunks(rows, N);
-    const int rpb = (int)((rows + C - 1) / C);
-    hipLaunchKernelGGL((ppo_loss_kernel<true, true>), dim3(C, N), dim3(256), 0, static_cast<hipStream_t>(stream), rows, N, A, rpb,
-                       logits, l_sn, l_row, v, action, adv, R, logp_old, clip, v_coef, e_coef, g_up, (float*)nullptr, dlogits, dv,
-                       v_old, vclip);
-    return nmarl_check_launch();
+    return loss_launch(LOSS_PPO_VCLIP, true, rows, N, A, logits, l_sn, l_row, v, action, adv, R, logp_old, v_old, clip, vclip, v_coef,
+                       e_coef, g_up, nullptr, nullptr, dlogits, dv, stream);
 }
 
 extern "C" int nmarl_ppo_kl_sum(int32_t N, const float* terms, int64_t t_stride, float* tail, void* stream) {

@@ -19,6 +19,43 @@ AGENTS = {'ia2c': IA2C, 'ia2c_fp': IA2C_FP, 'ma2c_nc': MA2C_NC, 'ma2c_ic3': MA2C
           'ma2c_dial': MA2C_DIAL}
 
 
+# The MODEL_CONFIG keys `train` overrides from the command line: (flag, key, how the parsed value is written into the ini, argparse's
+# type or choices of the flag, its help)
+OVERRIDES = (
+    ('--lstm-precision', 'lstm_precision', str, dict(choices=('fp32', 'bf16x3')),
+     'arithmetic of the rollout\'s LSTM products (overrides MODEL_CONFIG lstm_precision; default fp32). '
+     'bf16x3: opt-in split-bf16 form, IA2C / IA2C-FP / ConseNet only; the update stays fp32'),
+    ('--gae-lambda', 'gae_lambda', repr, dict(type=float),
+     'lambda of generalised advantage estimation in [0, 1] (overrides MODEL_CONFIG gae_lambda; default 1 = the '
+     'reference\'s n-step advantage).  Below 1 the critic\'s target is the lambda-return'),
+    ('--optimizer', 'optimizer', str, dict(choices=('rmsprop', 'adam')),
+     'optimiser behind the gradient clip (overrides MODEL_CONFIG optimizer; default rmsprop = the reference\'s '
+     'TF-1.12 RMSProp).  adam: opt-in bias-corrected Adam (MODEL_CONFIG adam_beta1 / adam_beta2 / adam_epsilon)'),
+    ('--adv-norm', 'adv_norm', str, dict(choices=('none', 'agent', 'all')),
+     'per-batch standardisation of the advantage in the policy-gradient term (overrides MODEL_CONFIG adv_norm; '
+     'default none).  agent: zero mean and unit std per agent; all: over all agents together.  The critic\'s '
+     'target is not touched (MODEL_CONFIG adv_norm_epsilon, default 1e-8, is added to the std)'),
+    ('--reward-scale', 'reward_scale', str, dict(choices=('none', 'return')),
+     'scale of the training rewards (overrides MODEL_CONFIG reward_scale; default none = raw / reward_norm).  '
+     'return: divide by the running std of the discounted return over everything seen so far, in place of '
+     'reward_norm (MODEL_CONFIG reward_scale_epsilon, default 1e-8, is added to the std); evaluation is untouched'),
+    ('--ppo-epochs', 'ppo_epochs', str, dict(type=int),
+     'optimiser steps per batch (overrides MODEL_CONFIG ppo_epochs; default 1 = one A2C step).  K > 1: the first '
+     'step is the A2C step, steps 2..K recompute the forward pass and apply the clipped surrogate against the '
+     'policy that produced the batch; IA2C / IA2C-FP / ConseNet only, fp32 only'),
+    ('--ppo-clip', 'ppo_clip', repr, dict(type=float),
+     'epsilon of the clipped surrogate (overrides MODEL_CONFIG ppo_clip; default 0.2; finite and > 0)'),
+    ('--ppo-vclip', 'ppo_vclip', repr, dict(type=float),
+     'clip range of the value loss in steps 2..K (overrides MODEL_CONFIG ppo_vclip; default absent = unclipped).  '
+     'The critic\'s error is the larger of (R - v)^2 and (R - v_clipped)^2, v_clipped within +-this of the value '
+     'under the weights that produced the batch; finite and > 0, needs --ppo-epochs / ppo_epochs > 1'),
+    ('--ppo-target-kl', 'ppo_target_kl', repr, dict(type=float),
+     'KL stop of steps 2..K (overrides MODEL_CONFIG ppo_target_kl; default absent = no stop).  Once the mean '
+     'approx_kl of a step exceeds this, that step and the rest of the update change nothing; decided on the '
+     'device, the remaining passes still run (it buys stability, not time); finite and > 0, needs ppo_epochs > 1'),
+)
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--base-dir', type=str, required=False, default='./runs/default', help='experiment base dir')
@@ -30,37 +67,8 @@ def parse_args(argv=None):
     sp.add_argument('--no-graph', action='store_true', help='do not capture the rollout in a hipGraph')
     sp.add_argument('--no-train-record', action='store_true',
                     help='batched training: no per-update loss / lr / gradnorm scalars and no train_summary.csv')
-    sp.add_argument('--lstm-precision', choices=('fp32', 'bf16x3'), default=None,
-                    help='arithmetic of the rollout\'s LSTM products (overrides MODEL_CONFIG lstm_precision; default fp32). '
-                         'bf16x3: opt-in split-bf16 form, IA2C / IA2C-FP / ConseNet only; the update stays fp32')
-    sp.add_argument('--gae-lambda', type=float, default=None,
-                    help='lambda of generalised advantage estimation in [0, 1] (overrides MODEL_CONFIG gae_lambda; default 1 = the '
-                         'reference\'s n-step advantage).  Below 1 the critic\'s target is the lambda-return')
-    sp.add_argument('--optimizer', choices=('rmsprop', 'adam'), default=None,
-                    help='optimiser behind the gradient clip (overrides MODEL_CONFIG optimizer; default rmsprop = the reference\'s '
-                         'TF-1.12 RMSProp).  adam: opt-in bias-corrected Adam (MODEL_CONFIG adam_beta1 / adam_beta2 / adam_epsilon)')
-    sp.add_argument('--adv-norm', choices=('none', 'agent', 'all'), default=None,
-                    help='per-batch standardisation of the advantage in the policy-gradient term (overrides MODEL_CONFIG adv_norm; '
-                         'default none).  agent: zero mean and unit std per agent; all: over all agents together.  The critic\'s '
-                         'target is not touched (MODEL_CONFIG adv_norm_epsilon, default 1e-8, is added to the std)')
-    sp.add_argument('--reward-scale', choices=('none', 'return'), default=None,
-                    help='scale of the training rewards (overrides MODEL_CONFIG reward_scale; default none = raw / reward_norm).  '
-                         'return: divide by the running std of the discounted return over everything seen so far, in place of '
-                         'reward_norm (MODEL_CONFIG reward_scale_epsilon, default 1e-8, is added to the std); evaluation is untouched')
-    sp.add_argument('--ppo-epochs', type=int, default=None,
-                    help='optimiser steps per batch (overrides MODEL_CONFIG ppo_epochs; default 1 = one A2C step).  K > 1: the first '
-                         'step is the A2C step, steps 2..K recompute the forward pass and apply the clipped surrogate against the '
-                         'policy that produced the batch; IA2C / IA2C-FP / ConseNet only, fp32 only')
-    sp.add_argument('--ppo-clip', type=float, default=None,
-                    help='epsilon of the clipped surrogate (overrides MODEL_CONFIG ppo_clip; default 0.2; finite and > 0)')
-    sp.add_argument('--ppo-vclip', type=float, default=None,
-                    help='clip range of the value loss in steps 2..K (overrides MODEL_CONFIG ppo_vclip; default absent = unclipped).  '
-                         'The critic\'s error is the larger of (R - v)^2 and (R - v_clipped)^2, v_clipped within +-this of the value '
-                         'under the weights that produced the batch; finite and > 0, needs --ppo-epochs / ppo_epochs > 1')
-    sp.add_argument('--ppo-target-kl', type=float, default=None,
-                    help='KL stop of steps 2..K (overrides MODEL_CONFIG ppo_target_kl; default absent = no stop).  Once the mean '
-                         'approx_kl of a step exceeds this, that step and the rest of the update change nothing; decided on the '
-                         'device, the remaining passes still run (it buys stability, not time); finite and > 0, needs ppo_epochs > 1')
+    for flag, _, _, kw, text in OVERRIDES:
+        sp.add_argument(flag, default=None, help=text, **kw)
     sp = subparsers.add_parser('evaluate', help='evaluate and compare agents under base dir')
     sp.add_argument('--evaluation-seeds', type=str, required=False,
                     default=','.join([str(i) for i in range(2000, 2500, 10)]),
@@ -100,19 +108,9 @@ def _dist():
 
 
 def apply_overrides(config, args, run_ini=None):
-    """The MODEL_CONFIG keys the command line overrides (--lstm-precision, --gae-lambda, --optimizer, --adv-norm, --reward-scale, --ppo-epochs, --ppo-clip,
-    --ppo-vclip, --ppo-target-kl), set
+    """The MODEL_CONFIG keys the command line overrides (OVERRIDES), set
     on every rank; run_ini (rank 0): the run's copy of the ini, rewritten with them -- `evaluate` rebuilds the policy from that file."""
-    given = {'lstm_precision': args.lstm_precision,
-             'gae_lambda': None if args.gae_lambda is None else repr(args.gae_lambda),
-             'optimizer': args.optimizer,
-             'adv_norm': args.adv_norm,
-             'reward_scale': getattr(args, 'reward_scale', None),
-             'ppo_epochs': None if getattr(args, 'ppo_epochs', None) is None else str(args.ppo_epochs),
-             'ppo_clip': None if getattr(args, 'ppo_clip', None) is None else repr(args.ppo_clip),
-             'ppo_vclip': None if getattr(args, 'ppo_vclip', None) is None else repr(args.ppo_vclip),
-             'ppo_target_kl': None if getattr(args, 'ppo_target_kl', None) is None else repr(args.ppo_target_kl)}
-    given = {k: v for k, v in given.items() if v is not None}
+    given = {key: render(getattr(args, key)) for _, key, render, _, _ in OVERRIDES if getattr(args, key, None) is not None}
     for k, v in given.items():
         config.set('MODEL_CONFIG', k, v)
     if given and run_ini is not None:

@@ -1772,39 +1772,52 @@ def atsc_maxpressure(n_a, mask, gptr, gpair, tgrp, tw, obs, out, n_feat, a_max=8
 A2C_LOSS_MAX_A = 8
 
 
-class _A2CLoss(torch.autograd.Function):
+def _loss_entry(direction, logp_old, v_old):
+    """The C entry of a loss pass ('fwd' | 'bwd'): A2C without logp_old, PPO with it, PPO with value clip with v_old as well."""
+    if logp_old is None:
+        return 'nmarl_a2c_loss_' + direction
+    return 'nmarl_ppo_loss_' + ('' if v_old is None else 'vclip_') + direction
+
+
+class _Loss(torch.autograd.Function):
     """(total [N], terms [N,3]) = per-agent (policy, value, entropy) loss terms of Policy.prepare_loss (policies.py:20-30) from logits
     [N,rows,A] (any row pitch), v / adv / R [N,rows] and the env-major action bytes [rows,N]: one streaming pass
-    forward, one backward (closed-form d/dlogits, d/dv), instead of the softmax / log / clamp / gather / mean chain."""
+    forward, one backward (closed-form d/dlogits, d/dv), instead of the softmax / log / clamp / gather / mean chain.
+    With logp_old [N,rows] and clip: the clipped surrogate, terms [N,5] (approx_kl, clip_frac behind the three); with v_old [N,rows]
+    and vclip as well: the value term clipped around v_old, terms [N,6] (vclip_frac the sixth).  total = the first three terms."""
 
     @staticmethod
-    def forward(ctx, logits, v, action, adv, R, v_coef, e_coef):
+    def forward(ctx, logits, v, action, adv, R, logp_old, v_old, clip, vclip, v_coef, e_coef):
         N, rows, A = logits.shape
         if logits.stride(2) != 1:
             logits = logits.contiguous()
         v, adv, R = v.contiguous(), adv.contiguous(), R.contiguous()
+        old = [t.contiguous() for t in (logp_old, v_old) if t is not None]
+        W = 3 + (0 if logp_old is None else 2 if v_old is None else 3)
         C_ = lib.nmarl_a2c_loss_chunks(rows, N)
-        partial = torch.empty(N, C_, 3, dtype=F32, device=logits.device)
-        out = torch.empty(N, 3, dtype=F32, device=logits.device)
-        check(lib.nmarl_a2c_loss_fwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
-                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), v_coef, e_coef, ptr(partial), ptr(out),
-                                     stream()), 'nmarl_a2c_loss_fwd')
-        ctx.save_for_backward(logits, v, action, adv, R)
-        ctx.coefs = (v_coef, e_coef)
+        partial = torch.empty(N, C_, W, dtype=F32, device=logits.device)
+        out = torch.empty(N, W, dtype=F32, device=logits.device)
+        name = _loss_entry('fwd', logp_old, v_old)
+        ctx.coefs = [c for c in (clip, vclip) if c is not None] + [v_coef, e_coef]
+        check(getattr(lib, name)(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
+                                 ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), *[ptr(t, F32) for t in old], *ctx.coefs,
+                                 ptr(partial), ptr(out), stream()), name)
+        ctx.save_for_backward(logits, v, action, adv, R, *old)
+        ctx.name = _loss_entry('bwd', logp_old, v_old)
         ctx.mark_non_differentiable(out)
-        return out.sum(dim=1), out            # (differentiable per-agent total [N], the three terms for logging)
+        return out[:, :3].sum(dim=1), out            # (differentiable per-agent total [N], the terms for logging)
 
     @staticmethod
     def backward(ctx, g, _):
-        logits, v, action, adv, R = ctx.saved_tensors
+        logits, v, action, adv, R, *old = ctx.saved_tensors
         N, rows, A = logits.shape
         gn = g.contiguous()
         dlogits = torch.empty(N, rows, A, dtype=F32, device=logits.device)
         dv = torch.empty(N, rows, dtype=F32, device=logits.device)
-        check(lib.nmarl_a2c_loss_bwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
-                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ctx.coefs[0], ctx.coefs[1],
-                                     ptr(gn, F32), ptr(dlogits), ptr(dv), stream()), 'nmarl_a2c_loss_bwd')
-        return dlogits, dv, None, None, None, None, None
+        check(getattr(lib, ctx.name)(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
+                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), *[ptr(t, F32) for t in old], *ctx.coefs,
+                                     ptr(gn, F32), ptr(dlogits), ptr(dv), stream()), ctx.name)
+        return (dlogits, dv) + (None,) * 9
 
 
 def a2c_loss_supported(n_a):
@@ -1813,7 +1826,7 @@ def a2c_loss_supported(n_a):
 
 def a2c_loss(logits, v, action, adv, R, v_coef, e_coef):
     """-> per-agent total loss [N] (differentiable) and the detached (policy, value, entropy) terms [N,3]."""
-    return _A2CLoss.apply(logits, v, action, adv, R, float(v_coef), float(e_coef))
+    return _Loss.apply(logits, v, action, adv, R, None, None, None, None, float(v_coef), float(e_coef))
 
 
 def ppo_loss_supported(n_a):
@@ -1834,88 +1847,17 @@ def ppo_logp(logits, action, out=None):
     return out
 
 
-class _PPOLoss(torch.autograd.Function):
-    """(total [N], terms [N,5]) = per-agent (policy, value, entropy, approx_kl, clip_frac) of the clipped surrogate against
-    logp_old [N,rows]; everything else as _A2CLoss (total = the first three terms): one streaming pass forward, one backward."""
-
-    @staticmethod
-    def forward(ctx, logits, v, action, adv, R, logp_old, clip, v_coef, e_coef):
-        N, rows, A = logits.shape
-        if logits.stride(2) != 1:
-            logits = logits.contiguous()
-        v, adv, R, logp_old = v.contiguous(), adv.contiguous(), R.contiguous(), logp_old.contiguous()
-        C_ = lib.nmarl_ppo_loss_chunks(rows, N)
-        partial = torch.empty(N, C_, 5, dtype=F32, device=logits.device)
-        out = torch.empty(N, 5, dtype=F32, device=logits.device)
-        check(lib.nmarl_ppo_loss_fwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
-                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32), clip, v_coef, e_coef,
-                                     ptr(partial), ptr(out), stream()), 'nmarl_ppo_loss_fwd')
-        ctx.save_for_backward(logits, v, action, adv, R, logp_old)
-        ctx.coefs = (clip, v_coef, e_coef)
-        ctx.mark_non_differentiable(out)
-        return out[:, :3].sum(dim=1), out
-
-    @staticmethod
-    def backward(ctx, g, _):
-        logits, v, action, adv, R, logp_old = ctx.saved_tensors
-        N, rows, A = logits.shape
-        gn = g.contiguous()
-        dlogits = torch.empty(N, rows, A, dtype=F32, device=logits.device)
-        dv = torch.empty(N, rows, dtype=F32, device=logits.device)
-        check(lib.nmarl_ppo_loss_bwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1), ptr(v, F32),
-                                     ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32), ctx.coefs[0],
-                                     ctx.coefs[1], ctx.coefs[2], ptr(gn, F32), ptr(dlogits), ptr(dv), stream()), 'nmarl_ppo_loss_bwd')
-        return dlogits, dv, None, None, None, None, None, None, None
-
-
-class _PPOLossVClip(torch.autograd.Function):
-    """_PPOLoss with the value term clipped around v_old [N,rows] (nmarl_ppo_loss_vclip_*): terms [N,6], the sixth vclip_frac."""
-
-    @staticmethod
-    def forward(ctx, logits, v, action, adv, R, logp_old, v_old, clip, vclip, v_coef, e_coef):
-        N, rows, A = logits.shape
-        if logits.stride(2) != 1:
-            logits = logits.contiguous()
-        v, adv, R, logp_old, v_old = v.contiguous(), adv.contiguous(), R.contiguous(), logp_old.contiguous(), v_old.contiguous()
-        C_ = lib.nmarl_ppo_loss_chunks(rows, N)
-        partial = torch.empty(N, C_, 6, dtype=F32, device=logits.device)
-        out = torch.empty(N, 6, dtype=F32, device=logits.device)
-        check(lib.nmarl_ppo_loss_vclip_fwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1),
-                                           ptr(v, F32), ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32),
-                                           ptr(v_old, F32), clip, vclip, v_coef, e_coef, ptr(partial), ptr(out), stream()),
-              'nmarl_ppo_loss_vclip_fwd')
-        ctx.save_for_backward(logits, v, action, adv, R, logp_old, v_old)
-        ctx.coefs = (clip, vclip, v_coef, e_coef)
-        ctx.mark_non_differentiable(out)
-        return out[:, :3].sum(dim=1), out
-
-    @staticmethod
-    def backward(ctx, g, _):
-        logits, v, action, adv, R, logp_old, v_old = ctx.saved_tensors
-        N, rows, A = logits.shape
-        gn = g.contiguous()
-        dlogits = torch.empty(N, rows, A, dtype=F32, device=logits.device)
-        dv = torch.empty(N, rows, dtype=F32, device=logits.device)
-        clip, vclip, v_coef, e_coef = ctx.coefs
-        check(lib.nmarl_ppo_loss_vclip_bwd(rows, N, A, ptr(logits, F32, strided=True), logits.stride(0), logits.stride(1),
-                                           ptr(v, F32), ptr(action, torch.uint8), ptr(adv, F32), ptr(R, F32), ptr(logp_old, F32),
-                                           ptr(v_old, F32), clip, vclip, v_coef, e_coef, ptr(gn, F32), ptr(dlogits), ptr(dv),
-                                           stream()), 'nmarl_ppo_loss_vclip_bwd')
-        return dlogits, dv, None, None, None, None, None, None, None, None, None
-
-
 def ppo_loss(logits, v, action, adv, R, logp_old, clip, v_coef, e_coef, v_old=None, vclip=None):
     """-> per-agent total loss [N] (differentiable; policy + value + entropy) and the detached (policy, value, entropy, approx_kl,
     clip_frac) terms [N,5] of the clipped surrogate with ratio exp(log_pi[a] - logp_old).  v_old [N,rows] and vclip (both or
     neither): the value term clipped around v_old, terms [N,6] with vclip_frac behind the five."""
     if (v_old is None) != (vclip is None):
         raise ValueError('ppo_loss: v_old and vclip go together')
-    if v_old is None:
-        return _PPOLoss.apply(logits, v, action, adv, R, logp_old, float(clip), float(v_coef), float(e_coef))
-    if tuple(v_old.shape) != tuple(v.shape):
-        raise ValueError('ppo_loss: v_old must have the shape of v, %s (got %s)' % (tuple(v.shape), tuple(v_old.shape)))
-    return _PPOLossVClip.apply(logits, v, action, adv, R, logp_old, v_old.detach(), float(clip), float(vclip), float(v_coef),
-                               float(e_coef))
+    if v_old is not None:
+        if tuple(v_old.shape) != tuple(v.shape):
+            raise ValueError('ppo_loss: v_old must have the shape of v, %s (got %s)' % (tuple(v.shape), tuple(v_old.shape)))
+        v_old, vclip = v_old.detach(), float(vclip)
+    return _Loss.apply(logits, v, action, adv, R, logp_old, v_old, float(clip), vclip, float(v_coef), float(e_coef))
 
 
 def ppo_kl_sum(terms, tail):
@@ -1941,13 +1883,19 @@ def ppo_kl_gate(tail, count, kappa, gate):
           'nmarl_ppo_kl_gate')
 
 
-def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, adv_out=None):
-    """r [T,E] | [T,E,N], v [T,N,E], done_post [T,E] u8, R_end [N,E] -> R, Adv [N,T,E]."""
+def _return_out(v, R_out, adv_out):
+    """The shape of v [T,N,E] and the two outputs [N,T,E] of a return scan, allocated where the caller gave none."""
     T, N, E = v.shape
     if R_out is None:
         R_out = torch.empty(N, T, E, dtype=F32, device=v.device)
     if adv_out is None:
         adv_out = torch.empty(N, T, E, dtype=F32, device=v.device)
+    return T, N, E, R_out, adv_out
+
+
+def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, adv_out=None):
+    """r [T,E] | [T,E,N], v [T,N,E], done_post [T,E] u8, R_end [N,E] -> R, Adv [N,T,E]."""
+    T, N, E, R_out, adv_out = _return_out(v, R_out, adv_out)
     check(lib.nmarl_nstep_return(E, N, T, ptr(r, F32), ptr(v, F32), ptr(done_post, torch.uint8), ptr(R_end, F32),
                                  float(gamma), float(alpha), ptr(dist, torch.int32), ptr(R_out), ptr(adv_out),
                                  stream()), 'nmarl_nstep_return')
@@ -1956,11 +1904,7 @@ def nstep_return(r, v, done_post, R_end, gamma, alpha, dist=None, R_out=None, ad
 
 def gae_return(r, v, done_post, R_end, gamma, lam, alpha, dist=None, R_out=None, adv_out=None):
     """GAE(lam) on the layouts of nstep_return -> lambda-return R, advantage Adv [N,T,E] (lam = 1: the n-step return)."""
-    T, N, E = v.shape
-    if R_out is None:
-        R_out = torch.empty(N, T, E, dtype=F32, device=v.device)
-    if adv_out is None:
-        adv_out = torch.empty(N, T, E, dtype=F32, device=v.device)
+    T, N, E, R_out, adv_out = _return_out(v, R_out, adv_out)
     check(lib.nmarl_gae_return(E, N, T, ptr(r, F32), ptr(v, F32), ptr(done_post, torch.uint8), ptr(R_end, F32),
                                float(gamma), float(lam), float(alpha), ptr(dist, torch.int32), ptr(R_out), ptr(adv_out),
                                stream()), 'nmarl_gae_return')

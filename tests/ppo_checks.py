@@ -21,6 +21,20 @@ V_COEF, E_COEF, CLIP = 0.5, 0.05, 0.2
 SENTINEL = -12345.0
 
 SHAPES = [(8, 4096, 4), (25, 1234, 5), (3, 1, 8), (1, 257, 2), (8, 70001, 4)]
+# beside SHAPES, the smallest inputs at which the loss kernels' shared row, block-reduction and launcher code can go wrong: the widest
+# action set over two chunks (rows * N > 4096) with a ragged last chunk and rows no multiple of 256; one row with one action (every
+# padded lane of the row inactive).  LOSS_CASES: every shape with the logits contiguous (block False) and as a column block of pitch
+# A + 1 (True), and the first edge shape once more at pitch A + 3 ('wide'), the strided form the heads hand over
+EDGE_SHAPES = [(3, 1501, 8), (1, 1, 1)]
+LOSS_CASES = [s + (block,) for s in SHAPES + EDGE_SHAPES for block in (False, True)] + [EDGE_SHAPES[0] + ('wide',)]
+
+
+def column_block(out, A, block, fill=0.0):
+    """out [N,rows,A+1] -> the tensor whose first A columns are handed over as logits: those columns alone, contiguous (block False),
+    `out` itself (True: pitch A + 1) or `out` with two more padding columns of `fill` ('wide': pitch A + 3)."""
+    if block == 'wide':
+        return torch.nn.functional.pad(out, (0, 2), value=fill)
+    return out if block else out[..., :A].contiguous()
 
 
 def logp(logits, action):

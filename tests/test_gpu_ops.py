@@ -490,14 +490,21 @@ def test_heads_and_neighbour_action_value(N, rows, A, m_max):
         torch.testing.assert_close(a.cpu().double(), b, rtol=1e-4, atol=3e-5 * rows ** 0.5)
 
 
-@pytest.mark.parametrize('N,rows,A', [(8, 4096, 4), (25, 1234, 5), (3, 1, 8), (8, 70001, 4)])
-def test_a2c_loss_fused(N, rows, A):
+# (N, rows, A, padding columns of the logits' column block).  The last three: the widest action set over two chunks with a ragged
+# last chunk and rows no multiple of 256; one row with one action (every padded lane of the row inactive); the first of the two at
+# row pitch A + 3, the strided form the heads hand over
+A2C_LOSS_CASES = [(8, 4096, 4, 1), (25, 1234, 5, 1), (3, 1, 8, 1), (8, 70001, 4, 1), (3, 1501, 8, 1), (1, 1, 1, 1), (3, 1501, 8, 3)]
+
+
+@pytest.mark.parametrize('N,rows,A,pad', A2C_LOSS_CASES,
+                         ids=['%d-%d-%d' % c[:3] + ('' if c[3] == 1 else '-pitch%d' % (c[2] + c[3])) for c in A2C_LOSS_CASES])
+def test_a2c_loss_fused(N, rows, A, pad):
     """One-pass A2C loss (values and d/dlogits, d/dv) == softmax / log / clip / gather / mean chain of
     policies.py:20-30 in float64, incl. probabilities below the 1e-10 clip and logits given as a column block."""
     from deeprl_network_amd import ops
     from oracle import ops_ref
     g = torch.Generator().manual_seed(N + rows + A)
-    out = torch.randn(N, rows, A + 1, generator=g) * 2.0
+    out = torch.randn(N, rows, A + pad, generator=g) * 2.0
     out[:, ::7, 0] = -60.0                                   # pi_0 ~ 1e-26 < 1e-10: clipped, gradient blocked
     act = torch.randint(0, A, (rows, N), generator=g).to(torch.uint8)
     act[::7] = 0                                             # ... and it is the action taken on some rows
@@ -517,7 +524,7 @@ def test_a2c_loss_fused(N, rows, A):
     torch.testing.assert_close(termg.cpu().double(), termr, rtol=2e-5, atol=1e-6)
     torch.testing.assert_close(dog.cpu().double(), dor, rtol=1e-4, atol=1e-9)
     torch.testing.assert_close(dvg.cpu().double(), dvr, rtol=1e-4, atol=1e-9)
-    assert torch.all(dog[..., A] == 0)
+    assert torch.all(dog[..., A:] == 0)
 
 
 def test_sample_actions_modes():

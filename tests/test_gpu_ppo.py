@@ -1,4 +1,4 @@
-"""The opt-in PPO epochs on the device: the kernels of csrc/a2c.hip (ppo_logp_kernel, ppo_loss_kernel, ppo_loss_reduce_kernel) against
+"""The opt-in PPO epochs on the device: the kernels of csrc/a2c.hip (ppo_logp_kernel, ppo_loss_kernel, loss_reduce_kernel) against
 the float64 restatement of tests/ppo_checks.py, their bit-equality with the A2C loss at rho = 1, determinism and the ABI's refusals;
 and MODEL_CONFIG ppo_epochs through BatchedTrainer (eager and captured) and the one-replica path."""
 import os
@@ -28,15 +28,11 @@ def _case(N, rows, A):
 
 
 def _native(d, block, loss=None, logp_old=None):
-    """ops.ppo_loss forward + backward on the device: logits as a column block of pitch A + 1 (`block`) or contiguous."""
+    """ops.ppo_loss forward + backward on the device: logits contiguous or as a column block (`block`, pc.column_block)."""
     from deeprl_network_amd import ops
     A = d['A']
-    if block:
-        o = d['out'].cuda().requires_grad_()
-        logits = o[..., :A]
-    else:
-        o = d['out'][..., :A].contiguous().cuda().requires_grad_()
-        logits = o
+    o = pc.column_block(d['out'], A, block).cuda().requires_grad_()
+    logits = o[..., :A]
     vv = d['v'].cuda().requires_grad_()
     lo = d['logp_old'].cuda() if logp_old is None else logp_old
     tot, terms = (loss or ops.ppo_loss)(logits, vv, d['action'].cuda(), d['adv'].cuda(), d['R'].cuda(), lo, d['clip'], pc.V_COEF,
@@ -46,8 +42,7 @@ def _native(d, block, loss=None, logp_old=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels
-@pytest.mark.parametrize('block', [False, True])
-@pytest.mark.parametrize('N,rows,A', pc.SHAPES)
+@pytest.mark.parametrize('N,rows,A,block', pc.LOSS_CASES)
 def test_ppo_loss_equals_the_restatement(N, rows, A, block):
     d, e, _ = _case(N, rows, A)
     g = _native(d, block)
@@ -56,26 +51,24 @@ def test_ppo_loss_equals_the_restatement(N, rows, A, block):
     print('max |term error|:', dict(zip(names, dev.tolist())))
     torch.testing.assert_close(g['terms'].cpu().double(), e['terms'], **pc.TERMS_TOL)
     torch.testing.assert_close(g['total'].cpu().double(), e['total'], **pc.TERMS_TOL)
-    want = e['dlogits'] if block else e['dlogits'][..., :A]
-    torch.testing.assert_close(g['dlogits'].cpu().double(), want, **pc.GRAD_TOL)
+    torch.testing.assert_close(g['dlogits'].cpu().double(), pc.column_block(e['dlogits'], A, block), **pc.GRAD_TOL)
     torch.testing.assert_close(g['dv'].cpu().double(), e['dv'], **pc.GRAD_TOL)
     if block:
-        assert torch.all(g['dlogits'][..., A] == 0)                # the padding column receives no gradient
+        assert torch.all(g['dlogits'][..., A:] == 0)               # the padding columns receive no gradient
 
 
-@pytest.mark.parametrize('block', [False, True])
-@pytest.mark.parametrize('N,rows,A', pc.SHAPES)
+@pytest.mark.parametrize('N,rows,A,block', pc.LOSS_CASES)
 def test_ppo_logp_equals_the_restatement(N, rows, A, block):
     from deeprl_network_amd import ops
     d, _, lp = _case(N, rows, A)
     out = d['out'].clone()
     out[..., A] = pc.SENTINEL
-    out = out.cuda()
+    out = pc.column_block(out, A, block or True, fill=pc.SENTINEL).cuda()
     logits = out[..., :A] if block else out[..., :A].contiguous()
     got = ops.ppo_logp(logits, d['action'].cuda())
     assert tuple(got.shape) == (N, rows) and got.dtype == torch.float32
     torch.testing.assert_close(got.cpu().double(), lp, **pc.LOGP_TOL)
-    assert bool((out[..., A] == pc.SENTINEL).all())                # the padding column of the column block is not written
+    assert bool((out[..., A:] == pc.SENTINEL).all())               # the padding columns of the column block are not written
     dst = torch.full((N, rows), pc.SENTINEL, device='cuda')
     assert ops.ppo_logp(logits, d['action'].cuda(), out=dst) is dst and torch.equal(dst, got)
     # the probability below the clamp: log(1e-10)
@@ -83,12 +76,11 @@ def test_ppo_logp_equals_the_restatement(N, rows, A, block):
         assert float((got[:, ::7] - float(np.log(np.float32(1e-10)))).abs().max()) < 1e-5
 
 
-@pytest.mark.parametrize('block', [False, True])
-@pytest.mark.parametrize('N,rows,A', pc.SHAPES)
+@pytest.mark.parametrize('N,rows,A,block', pc.LOSS_CASES)
 def test_at_the_behaviour_policy_the_gradient_has_the_bits_of_the_a2c_loss(N, rows, A, block):
     from deeprl_network_amd import ops
     d, _, _ = _case(N, rows, A)
-    src = d['out'].cuda()
+    src = pc.column_block(d['out'], A, block or True).cuda()
     logits = src[..., :A] if block else src[..., :A].contiguous()
     lo = ops.ppo_logp(logits, d['action'].cuda())
     g = _native(d, block, logp_old=lo)

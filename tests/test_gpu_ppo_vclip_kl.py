@@ -33,13 +33,13 @@ def _case(N, rows, A):
 
 def _raw(d, block, vclip):
     """The C entries themselves, forward and backward with g_up = d['w'], every output filled with the sentinel beforehand.
-    vclip None: nmarl_ppo_loss_*; block: logits as a column block of pitch A + 1."""
+    vclip None: nmarl_ppo_loss_*; block: logits contiguous or as a column block (pc.column_block)."""
     from deeprl_network_amd import _lib
     lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream
     A = d['A']
     N, rows = d['v'].shape
-    lg = d['out'].cuda() if block else d['out'][..., :A].contiguous().cuda()
-    pitch = A + 1 if block else A
+    lg = pc.column_block(d['out'], A, block).cuda()
+    pitch = lg.shape[-1]
     v, adv, R, lo, vo, act, w = (d[k].cuda() for k in ('v', 'adv', 'R', 'logp_old', 'v_old', 'action', 'w'))
     C = lib.nmarl_ppo_loss_chunks(rows, N)
     cols = 5 if vclip is None else 6
@@ -62,8 +62,7 @@ def _bits(t):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the kernels
-@pytest.mark.parametrize('block', [False, True])
-@pytest.mark.parametrize('N,rows,A', pc.SHAPES)
+@pytest.mark.parametrize('N,rows,A,block', pc.LOSS_CASES)
 def test_vclip_loss_equals_the_restatement(N, rows, A, block):
     d, e = _case(N, rows, A)
     g = _raw(d, block, d['vclip'])
@@ -81,8 +80,7 @@ def test_vclip_loss_equals_the_restatement(N, rows, A, block):
     assert torch.equal(g['dv'].cpu() == 0, e['dv'] == 0)
 
 
-@pytest.mark.parametrize('block', [False, True])
-@pytest.mark.parametrize('N,rows,A', pc.SHAPES)
+@pytest.mark.parametrize('N,rows,A,block', pc.LOSS_CASES)
 def test_where_every_row_is_inside_the_bits_are_those_of_the_unclipped_loss(N, rows, A, block):
     d, _ = _case(N, rows, A)
     g, p = _raw(d, block, vc.HUGE), _raw(d, block, None)

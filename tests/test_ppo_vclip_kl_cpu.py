@@ -393,9 +393,9 @@ def test_new_kernels_use_no_scratch():
     rows = {r['name']: r for r in resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))}
     loss = [n for n in rows if 'ppo_loss_kernel' in n]
     assert len(loss) == 4, sorted(rows)                                   # <BWD, VCLIP>: the two of before and the two new ones
-    for want in ('ppo_loss_vclip_reduce_kernel', 'ppo_kl_sum_kernel', 'ppo_kl_gate_kernel'):
+    for want in ('loss_reduce_kernel<6>', 'ppo_kl_sum_kernel', 'ppo_kl_gate_kernel'):
         assert any(want in n for n in rows), (want, sorted(rows))
     for n, g in rows.items():
-        if 'ppo_' in n:
+        if 'ppo_' in n or 'loss_reduce_kernel' in n:
             assert g['ScratchSize [bytes/lane]'] == 0 and g['VGPRs Spill'] == 0 and g['SGPRs Spill'] == 0, (n, g)
             print(n, {k: g[k] for k in g if 'GPR' in k or 'LDS' in k or 'Scratch' in k})

@@ -13,25 +13,11 @@ import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 SHAPES = [(8, 409568 // 8), (1, 1021990)]
 LR, MAX_NORM = 5e-4, 40.0
-
-
-def resources():
-    import resource_usage
-    rows = {r['name']: r for r in resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))}
-    print('compiler resource report, gfx950:')
-    for k in ('sumsq_kernel', 'rmsprop_kernel', 'adam_sumsq_kernel', 'adam_kernel'):
-        r = [v for n, v in rows.items() if n.split('(')[0] == k][0]
-        print('    %-17s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-              % (k, r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'], r['LDS Size [bytes/block]'],
-                 r['Occupancy [waves/SIMD]']))
-    return rows
 
 
 def measure(G, P):
@@ -92,7 +78,7 @@ def main():
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('clip + Adam step next to the clip + RMSProp step (tools/adam_profile.py), %s' % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(17, names=('sumsq_kernel', 'rmsprop_kernel', 'adam_sumsq_kernel', 'adam_kernel'))
     worst = 0.0
     for G, P in SHAPES:
         worst = max(worst, *measure(G, P))

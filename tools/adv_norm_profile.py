@@ -17,32 +17,17 @@ that an effect of the order on a trainer's batch time shows next to the effect o
 --gpus 1 --steps 20 --warmup 3` of that tree and of this one, each run a fresh child process, alternating, 4 runs each: the key is
 absent in bench.py, so this is the parent's batch time against this tree's on one box.
 The kernels' registers, LDS, scratch and occupancy are the compiler's resource report for gfx950 (tools/resource_usage.py)."""
-import configparser
 import contextlib
 import io
 import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 SHAPES = [(8, 4096, 60), (25, 1024, 120)]
 GAMMA, EPS = 0.99, 1e-8
-
-
-def resources():
-    import resource_usage
-    rows = {r['name']: r for r in resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))}
-    print('compiler resource report, gfx950:')
-    for k in ('nstep_kernel', 'standardize_moments_kernel', 'standardize_apply_kernel'):
-        r = [v for n, v in rows.items() if n.split('(')[0] == k][0]
-        print('    %-27s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-              % (k, r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'], r['LDS Size [bytes/block]'],
-                 r['Occupancy [waves/SIMD]']))
 
 
 def measure(N, E, T, mode):
@@ -104,89 +89,32 @@ def measure(N, E, T, mode):
           % tuple(med['standardize'][i] / med['nstep_return'][i] for i in (0, 1)))
 
 
-def _trainer(adv_norm, E):
-    from deeprl_network_amd.envs import make_batch_env
-    from deeprl_network_amd.main import init_agent
-    from deeprl_network_amd.utils import BatchedTrainer, Counter
-    import numpy as np
-    cp = configparser.ConfigParser()
-    cp.read(os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini'))
-    if adv_norm is not None:
-        cp['MODEL_CONFIG']['adv_norm'] = adv_norm
-    env = make_batch_env(cp['ENV_CONFIG'], num_envs=E)
-    np.random.seed(env.seed)
-    model = init_agent(env, cp['MODEL_CONFIG'], int(1e9), env.seed, num_envs=E)
-    return env, model, BatchedTrainer(env, model, Counter(int(1e18), int(1e18), int(1e18)), use_graph=True)
-
-
-def training_ab(first, E=4096, per_block=20, blocks=8):
-    import gc
-    import torch
-    keys = {'key absent': None, 'adv_norm = agent': 'agent'}
-    arms = {k: _trainer(keys[k], E) for k in sorted(keys, key=lambda k: k != first)}      # `first` is built and timed first
-    for _, _, tr in arms.values():
-        for _ in range(5):
-            tr.run_batch()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(blocks):
-        for k, (_, _, tr) in arms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(per_block):
-                tr.run_batch()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) / per_block * 1e3)
+def training_ab(first):
+    keys = {'key absent': {}, 'adv_norm = agent': dict(adv_norm='agent')}
+    arms, ms = common.training_ab({k: keys[k] for k in sorted(keys, key=lambda k: k != first)})      # `first` is built and timed first
     env, model, _ = arms['key absent']
     print('config_ia2c_fp_catchup.ini, %d agents x %d replicas, n_step %d, captured, %d blocks of %d batches per arm, alternating, '
-          '"%s" built and timed first:' % (env.n_agent, E, model.n_step, blocks, per_block, first))
-    med = {}
-    for k in arms:
-        med[k] = statistics.median(ms[k])
-        print('    %-17s median %7.3f ms per batch (min %7.3f, max %7.3f; spread of the blocks %.2f %%)'
-              % (k, med[k], min(ms[k]), max(ms[k]), (max(ms[k]) - min(ms[k])) / med[k] * 100))
+          '"%s" built and timed first:' % (env.n_agent, model.E, model.n_step, len(ms[first]), common.PER_BLOCK, first))
+    med = common.report_arms(ms, 17)
     print('    adv_norm = agent / key absent: %.4f (%+.2f %%; the documented run-to-run spread of the batch time is +-1.5 %%)'
           % (med['adv_norm = agent'] / med['key absent'], (med['adv_norm = agent'] / med['key absent'] - 1) * 100))
-    for k, (_, model, tr) in arms.items():
-        assert torch.isfinite(model.policy.params.flat).all() and tr.handoff_fallbacks == 0, k
-    del arms, env, model, tr
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def bench_ab(parent, runs=4):
-    import json
-    import subprocess
-    trees = {'parent': os.path.abspath(parent), 'this tree': ROOT}
-    ms = {k: [] for k in trees}
-    for _ in range(runs):
-        for k, d in trees.items():
-            out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '20', '--warmup', '3'], cwd=d, check=True,
-                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300).stdout.decode()
-            ms[k].append(json.loads([l for l in out.splitlines() if l.startswith('{')][-1])['ms_per_step'])
-    print('bench.py --gpus 1 --steps 20 --warmup 3 (key absent), the parent commit\'s tree and this one, %d runs each, alternating:' % runs)
-    for k in trees:
-        print('    %-10s ms per batch: %s; median %.3f' % (k, ', '.join('%.3f' % v for v in ms[k]), statistics.median(ms[k])))
-    r = statistics.median(ms['this tree']) / statistics.median(ms['parent'])
-    print('    this tree / parent: %.4f (%+.2f %%; the documented run-to-run spread of the batch time is +-1.5 %%)' % (r, (r - 1) * 100))
+    del env, model
+    common.close_arms(arms)
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit: adds the bench.py A/B against it')
-    args = ap.parse_args()
+    parent = common.parent_tree_arg()
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('advantage standardisation next to the n-step return scan (tools/adv_norm_profile.py), %s' % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(27, names=('nstep_kernel', 'standardize_moments_kernel', 'standardize_apply_kernel'))
     for N, E, T in SHAPES:
         for mode in ('agent', 'all'):
             measure(N, E, T, mode)
     for first in ('key absent', 'adv_norm = agent'):      # two fresh pairs of trainers, built in either order
         training_ab(first)
-    if args.parent_tree:
-        bench_ab(args.parent_tree)
+    if parent:
+        common.bench_ab(parent)
     return 0
 
 

@@ -12,24 +12,11 @@ import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 SHAPES = [(8, 4096, 60), (25, 1024, 120)]
 GAMMA, LAMBDA = 0.99, 0.95
-
-
-def resources():
-    import resource_usage
-    rows = {r['name']: r for r in resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))}
-    print('compiler resource report, gfx950:')
-    for k in ('nstep_kernel', 'gae_kernel<false>', 'gae_kernel<true>'):
-        r = rows[k]
-        print('    %-17s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-              % (k, r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'], r['LDS Size [bytes/block]'],
-                 r['Occupancy [waves/SIMD]']))
-    return rows
 
 
 def bytes_moved(N, E, T, spatial):
@@ -98,7 +85,7 @@ def main():
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('GAE(lambda) return scan next to the n-step scan (tools/gae_profile.py), %s' % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(17, names=('nstep_kernel', 'gae_kernel<false>', 'gae_kernel<true>'))
     worst = 0.0
     for N, E, T in SHAPES:
         for alpha in (-1.0, 0.9):

@@ -1,7 +1,7 @@
 """First measurement of the opt-in PPO epochs, one box, one process:
     python tools/ppo_profile.py [--parent-tree DIR] > profiles/r22_ppo.txt
 
-(1) ops.ppo_loss forward + backward (ppo_loss_kernel<fwd> + ppo_loss_reduce_kernel, ppo_loss_kernel<bwd>) next to ops.a2c_loss forward +
+(1) ops.ppo_loss forward + backward (ppo_loss_kernel<fwd> + loss_reduce_kernel<5>, ppo_loss_kernel<bwd>) next to ops.a2c_loss forward +
 backward on the same logits, values, actions, advantages and returns, and ops.ppo_logp alone, at 8 agents x 245 760 rows x 4 actions and
 25 x 122 880 x 5: 50 calls back to back between two events, the arms alternating block by block, 10 blocks each: median us per call.
 The timed ppo_loss call is first held to the float64 restatement of tests/ppo_checks.py at the tests' tolerances.
@@ -12,29 +12,14 @@ the +-1.5 % run-to-run spread of the batch time.  Done twice with fresh trainers
 one, each run a fresh child process, alternating, 4 runs each: the key is absent in bench.py, so this is the parent's batch time
 against this tree's on one box.
 The kernels' registers, LDS, scratch and occupancy are the compiler's resource report for gfx950 (tools/resource_usage.py)."""
-import configparser
 import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 SHAPES = [(8, 245760, 4), (25, 122880, 5)]
-
-
-def resources():
-    import resource_usage
-    rows = resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))
-    print('compiler resource report, gfx950:')
-    for r in rows:
-        if r['name'].startswith('ppo_') or r['name'].startswith('a2c_loss_'):
-            print('    %-30s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-                  % (r['name'].split('(')[0], r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'],
-                     r['LDS Size [bytes/block]'], r['Occupancy [waves/SIMD]']))
 
 
 def measure(N, rows, A):
@@ -87,91 +72,34 @@ def measure(N, rows, A):
     print('    ppo_loss / a2c_loss: %.2f' % (med['ppo_loss fwd + bwd'] / med['a2c_loss fwd + bwd']))
 
 
-def _trainer(K, E):
-    from deeprl_network_amd.envs import make_batch_env
-    from deeprl_network_amd.main import init_agent
-    from deeprl_network_amd.utils import BatchedTrainer, Counter
-    import numpy as np
-    cp = configparser.ConfigParser()
-    cp.read(os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini'))
-    if K is not None:
-        cp['MODEL_CONFIG']['ppo_epochs'] = str(K)
-    env = make_batch_env(cp['ENV_CONFIG'], num_envs=E)
-    np.random.seed(env.seed)
-    model = init_agent(env, cp['MODEL_CONFIG'], int(1e9), env.seed, num_envs=E)
-    return env, model, BatchedTrainer(env, model, Counter(int(1e18), int(1e18), int(1e18)), use_graph=True)
-
-
-def training_ab(order, E=4096, per_block=20, blocks=8):
-    import gc
-    import torch
+def training_ab(order):
     names = {None: 'key absent', 2: 'ppo_epochs = 2', 4: 'ppo_epochs = 4'}
-    arms = {names[K]: _trainer(K, E) for K in order}
-    for _, _, tr in arms.values():
-        for _ in range(5):
-            tr.run_batch()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(blocks):
-        for k, (_, _, tr) in arms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(per_block):
-                tr.run_batch()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) / per_block * 1e3)
+    arms, ms = common.training_ab({names[K]: {} if K is None else dict(ppo_epochs=K) for K in order})
     env, model, _ = arms['key absent']
     print('config_ia2c_fp_catchup.ini, %d agents x %d replicas, n_step %d, captured, %d blocks of %d batches per arm, alternating, '
-          'built and timed in the order %s:' % (env.n_agent, E, model.n_step, blocks, per_block, ', '.join(arms)))
-    med = {k: statistics.median(ms[k]) for k in arms}
-    for k in arms:
-        print('    %-15s median %7.3f ms per batch (min %7.3f, max %7.3f; spread of the blocks %.2f %%)'
-              % (k, med[k], min(ms[k]), max(ms[k]), (max(ms[k]) - min(ms[k])) / med[k] * 100))
+          'built and timed in the order %s:' % (env.n_agent, model.E, model.n_step, len(ms['key absent']), common.PER_BLOCK, ', '.join(arms)))
+    med = common.report_arms(ms, 15)
     for K in (2, 4):
         print('    %s: %+.3f ms per batch over the key absent = %.3f ms per extra epoch; approx_kl %.3g, clip_frac %.3g in the last epoch'
               % (names[K], med[names[K]] - med['key absent'], (med[names[K]] - med['key absent']) / (K - 1), arms[names[K]][1].ppo_kl,
                  arms[names[K]][1].ppo_clip_frac))
-    for k, (_, model, tr) in arms.items():
-        assert torch.isfinite(model.policy.params.flat).all() and tr.handoff_fallbacks == 0 and tr.update_capture_error is None, k
-    del arms, env, model, tr
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def bench_ab(parent, runs=4):
-    import json
-    import subprocess
-    trees = {'parent': os.path.abspath(parent), 'this tree': ROOT}
-    ms = {k: [] for k in trees}
-    for _ in range(runs):
-        for k, d in trees.items():
-            out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '20', '--warmup', '3'], cwd=d, check=True,
-                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300).stdout.decode()
-            ms[k].append(json.loads([l for l in out.splitlines() if l.startswith('{')][-1])['ms_per_step'])
-            print('bench.py of %s: %.3f ms per batch' % (k, ms[k][-1]), file=sys.stderr, flush=True)
-    print('bench.py --gpus 1 --steps 20 --warmup 3 (key absent), the parent commit\'s tree and this one, %d runs each, alternating:' % runs)
-    for k in trees:
-        print('    %-10s ms per batch: %s; median %.3f' % (k, ', '.join('%.3f' % v for v in ms[k]), statistics.median(ms[k])))
-    r = statistics.median(ms['this tree']) / statistics.median(ms['parent'])
-    print('    this tree / parent: %.4f (%+.2f %%; the documented run-to-run spread of the batch time is +-1.5 %%)' % (r, (r - 1) * 100))
+    del env, model
+    common.close_arms(arms, captured_update=True)
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit: adds the bench.py A/B against it')
-    args = ap.parse_args()
+    parent = common.parent_tree_arg()
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('PPO epochs: the clipped-surrogate loss next to the A2C loss, and K optimiser steps per batch (tools/ppo_profile.py), %s'
           % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(30, prefixes=('ppo_', 'a2c_loss_', 'loss_reduce_'))
     for shape in SHAPES:
         measure(*shape)
     for order in ((None, 2, 4), (4, 2, None)):      # two fresh sets of trainers, built in either order
         training_ab(order)
-    if args.parent_tree:
-        bench_ab(args.parent_tree)
+    if parent:
+        common.bench_ab(parent)
     return 0
 
 

@@ -1,7 +1,7 @@
 """First measurement of the opt-in value clipping and KL stop of the PPO epochs, one box, one process:
     python tools/ppo_vclip_kl_profile.py [--parent-tree DIR] > profiles/r23_ppo_vclip_kl.txt
 
-(1) ops.ppo_loss forward + backward with v_old / vclip (ppo_loss_kernel<fwd, vclip> + ppo_loss_vclip_reduce_kernel,
+(1) ops.ppo_loss forward + backward with v_old / vclip (ppo_loss_kernel<fwd, vclip> + loss_reduce_kernel<6>,
 ppo_loss_kernel<bwd, vclip>) next to the same call without them, on the same data, at 8 agents x 245 760 rows x 4 actions and
 25 x 122 880 x 5: 50 calls back to back between two events, the arms alternating block by block, 10 blocks each: median us per call.
 The timed value-clip call is first held to the float64 restatement of tests/ppo_vclip_checks.py at the tests' tolerances.
@@ -9,33 +9,19 @@ The timed value-clip call is first held to the float64 restatement of tests/ppo_
 (3) config_ia2c_fp_catchup.ini at 8 x 4096 with ppo_epochs = 2 through BatchedTrainer (captured), both keys absent against both keys
 on (ppo_vclip = 0.2, ppo_target_kl = 0.02), blocks of 20 batches alternating, 8 blocks each, done twice with fresh trainers built and
 timed in either order: median ms per batch, to be read against the +-1.5 % run-to-run spread of the batch time.
-(4) with --parent-tree DIR (a built checkout of the parent commit): tools/ppo_profile.py's bench.py A/B -- the keys are absent in
+(4) with --parent-tree DIR (a built checkout of the parent commit): the bench.py A/B of tools/profile_common.py -- the keys are absent in
 bench.py, so this is the parent's batch time against this tree's on one box.
 The kernels' registers, LDS, scratch and occupancy are the compiler's resource report for gfx950 (tools/resource_usage.py)."""
 import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 import ppo_profile as base  # noqa: E402
 
 KEYS = dict(ppo_vclip='0.2', ppo_target_kl='0.02')
-
-
-def resources():
-    import resource_usage
-    rows = resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))
-    print('compiler resource report, gfx950 (ppo_loss_kernel<BWD, VCLIP>):')
-    for r in rows:
-        if r['name'].startswith('ppo_'):
-            print('    %-36s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-                  % (r['name'].split('(')[0], r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'],
-                     r['LDS Size [bytes/block]'], r['Occupancy [waves/SIMD]']))
 
 
 def _blocks(run, reps, blocks=10):
@@ -100,75 +86,34 @@ def gate(N=8):
         print('    ops.ppo_%-8s median %6.2f us per launch (min %6.2f, max %6.2f)' % (k, statistics.median(v), min(v), max(v)))
 
 
-def _trainer(keys, E):
-    import configparser
-    import numpy as np
-    from deeprl_network_amd.envs import make_batch_env
-    from deeprl_network_amd.main import init_agent
-    from deeprl_network_amd.utils import BatchedTrainer, Counter
-    cp = configparser.ConfigParser()
-    cp.read(os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini'))
-    cp['MODEL_CONFIG']['ppo_epochs'] = '2'
-    for k, v in keys.items():
-        cp['MODEL_CONFIG'][k] = v
-    env = make_batch_env(cp['ENV_CONFIG'], num_envs=E)
-    np.random.seed(env.seed)
-    model = init_agent(env, cp['MODEL_CONFIG'], int(1e9), env.seed, num_envs=E)
-    return env, model, BatchedTrainer(env, model, Counter(int(1e18), int(1e18), int(1e18)), use_graph=True)
-
-
-def training_ab(order, E=4096, per_block=20, blocks=8):
-    import gc
-    import torch
-    arms = {name: _trainer(KEYS if name == 'both keys on' else {}, E) for name in order}
-    for _, _, tr in arms.values():
-        for _ in range(5):
-            tr.run_batch()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(blocks):
-        for k, (_, _, tr) in arms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(per_block):
-                tr.run_batch()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) / per_block * 1e3)
+def training_ab(order):
+    arms, ms = common.training_ab({name: dict(KEYS if name == 'both keys on' else {}, ppo_epochs=2) for name in order})
     env, model, _ = arms['keys absent']
     print('config_ia2c_fp_catchup.ini, ppo_epochs = 2, %d agents x %d replicas, n_step %d, captured, %d blocks of %d batches per arm, '
-          'alternating, built and timed in the order %s:' % (env.n_agent, E, model.n_step, blocks, per_block, ', '.join(arms)))
-    med = {k: statistics.median(ms[k]) for k in arms}
-    for k in arms:
-        print('    %-13s median %7.3f ms per batch (min %7.3f, max %7.3f; spread of the blocks %.2f %%)'
-              % (k, med[k], min(ms[k]), max(ms[k]), (max(ms[k]) - min(ms[k])) / med[k] * 100))
+          'alternating, built and timed in the order %s:' % (env.n_agent, model.E, model.n_step, len(ms['keys absent']), common.PER_BLOCK, ', '.join(arms)))
+    med = common.report_arms(ms, 13)
     on = arms['both keys on'][1]
     print('    both keys on (%s): %+.3f ms per batch (%+.2f %%); approx_kl %.3g, vclip_frac %.3g, ppo_epochs_done %d in the last update'
           % (', '.join('%s = %s' % kv for kv in KEYS.items()), med['both keys on'] - med['keys absent'],
              (med['both keys on'] / med['keys absent'] - 1) * 100, on.ppo_kl, on.ppo_vclip_frac, on.ppo_epochs_done))
-    for k, (_, model, tr) in arms.items():
-        assert torch.isfinite(model.policy.params.flat).all() and tr.handoff_fallbacks == 0 and tr.update_capture_error is None, k
-    del arms, env, model, tr, on
-    gc.collect()
-    torch.cuda.empty_cache()
+    del env, model, on
+    common.close_arms(arms, captured_update=True)
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit: adds the bench.py A/B against it')
-    args = ap.parse_args()
+    parent = common.parent_tree_arg()
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('PPO epochs: the clipped value loss next to the unclipped one, the KL stop\'s launches, and both keys through the trainer '
           '(tools/ppo_vclip_kl_profile.py), %s' % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(36, prefixes=('ppo_', 'loss_reduce_'), title='compiler resource report, gfx950 (ppo_loss_kernel<BWD, VCLIP>):')
     for shape in base.SHAPES:
         measure(*shape)
     gate()
     for order in (('keys absent', 'both keys on'), ('both keys on', 'keys absent')):
         training_ab(order)
-    if args.parent_tree:
-        base.bench_ab(args.parent_tree)
+    if parent:
+        common.bench_ab(parent)
     return 0
 
 

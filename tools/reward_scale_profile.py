@@ -15,32 +15,17 @@ against the +-1.5 % run-to-run spread of the batch time.  Done twice with fresh 
 one, each run a fresh child process, alternating, 4 runs each: the key is absent in bench.py, so this is the parent's batch time
 against this tree's on one box.
 The kernels' registers, LDS, scratch and occupancy are the compiler's resource report for gfx950 (tools/resource_usage.py)."""
-import configparser
 import contextlib
 import io
 import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import profile_common as common  # noqa: E402  (puts the repository, tools/ and tests/ on sys.path)
 
 SHAPES = [(8, 4096, 60, False), (25, 1024, 120, False), (25, 1024, 120, True)]       # (agents, replicas, steps, per-agent reward)
 GAMMA, EPS, CLIP = 0.99, 1e-8, 2.0
-
-
-def resources():
-    import resource_usage
-    rows = {r['name']: r for r in resource_usage.usage(os.path.join(ROOT, 'deeprl_network_amd', 'csrc', 'a2c.hip'))}
-    print('compiler resource report, gfx950:')
-    for k in ('reward_scale_scan_kernel', 'reward_scale_merge_kernel', 'reward_scale_apply_kernel'):
-        r = [v for n, v in rows.items() if n.split('(')[0] == k][0]
-        print('    %-27s VGPRs %3d, AGPRs %d, SGPRs %3d, scratch %d bytes/lane, LDS %d bytes/block, occupancy %d waves/SIMD'
-              % (k, r['VGPRs'], r.get('AGPRs', 0), r['TotalSGPRs'], r['ScratchSize [bytes/lane]'], r['LDS Size [bytes/block]'],
-                 r['Occupancy [waves/SIMD]']))
 
 
 def measure(N, E, T, per_agent):
@@ -108,91 +93,33 @@ def measure(N, E, T, per_agent):
           % tuple(med['reward_scale'][i] / med['div + clamp_'][i] for i in (0, 1)))
 
 
-def _trainer(reward_scale, E):
-    from deeprl_network_amd.envs import make_batch_env
-    from deeprl_network_amd.main import init_agent
-    from deeprl_network_amd.utils import BatchedTrainer, Counter
-    import numpy as np
-    cp = configparser.ConfigParser()
-    cp.read(os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini'))
-    if reward_scale is not None:
-        cp['MODEL_CONFIG']['reward_scale'] = reward_scale
-    env = make_batch_env(cp['ENV_CONFIG'], num_envs=E)
-    np.random.seed(env.seed)
-    model = init_agent(env, cp['MODEL_CONFIG'], int(1e9), env.seed, num_envs=E)
-    return env, model, BatchedTrainer(env, model, Counter(int(1e18), int(1e18), int(1e18)), use_graph=True)
-
-
-def training_ab(first, E=4096, per_block=20, blocks=8):
-    import gc
-    import torch
-    keys = {'key absent': None, 'reward_scale = return': 'return'}
-    arms = {k: _trainer(keys[k], E) for k in sorted(keys, key=lambda k: k != first)}      # `first` is built and timed first
-    for _, _, tr in arms.values():
-        for _ in range(5):
-            tr.run_batch()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(blocks):
-        for k, (_, _, tr) in arms.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(per_block):
-                tr.run_batch()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) / per_block * 1e3)
+def training_ab(first):
+    keys = {'key absent': {}, 'reward_scale = return': dict(reward_scale='return')}
+    arms, ms = common.training_ab({k: keys[k] for k in sorted(keys, key=lambda k: k != first)})      # `first` is built and timed first
     env, model, _ = arms['key absent']
     print('config_ia2c_fp_catchup.ini, %d agents x %d replicas, n_step %d, captured, %d blocks of %d batches per arm, alternating, '
-          '"%s" built and timed first:' % (env.n_agent, E, model.n_step, blocks, per_block, first))
-    med = {}
-    for k in arms:
-        med[k] = statistics.median(ms[k])
-        print('    %-22s median %7.3f ms per batch (min %7.3f, max %7.3f; spread of the blocks %.2f %%)'
-              % (k, med[k], min(ms[k]), max(ms[k]), (max(ms[k]) - min(ms[k])) / med[k] * 100))
+          '"%s" built and timed first:' % (env.n_agent, model.E, model.n_step, len(ms[first]), common.PER_BLOCK, first))
+    med = common.report_arms(ms, 22)
     print('    reward_scale = return / key absent: %.4f (%+.2f %%; the documented run-to-run spread of the batch time is +-1.5 %%)'
           % (med['reward_scale = return'] / med['key absent'], (med['reward_scale = return'] / med['key absent'] - 1) * 100))
     print('    running std of the discounted return after these batches: %.6g (raw reward units)' % arms['reward_scale = return'][1].reward_scale_std)
-    for k, (_, model, tr) in arms.items():
-        assert torch.isfinite(model.policy.params.flat).all() and tr.handoff_fallbacks == 0, k
-    del arms, env, model, tr
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def bench_ab(parent, runs=4):
-    import json
-    import subprocess
-    trees = {'parent': os.path.abspath(parent), 'this tree': ROOT}
-    ms = {k: [] for k in trees}
-    for _ in range(runs):
-        for k, d in trees.items():
-            out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '20', '--warmup', '3'], cwd=d, check=True,
-                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300).stdout.decode()
-            ms[k].append(json.loads([l for l in out.splitlines() if l.startswith('{')][-1])['ms_per_step'])
-            print('bench.py of %s: %.3f ms per batch' % (k, ms[k][-1]), file=sys.stderr, flush=True)
-    print('bench.py --gpus 1 --steps 20 --warmup 3 (key absent), the parent commit\'s tree and this one, %d runs each, alternating:' % runs)
-    for k in trees:
-        print('    %-10s ms per batch: %s; median %.3f' % (k, ', '.join('%.3f' % v for v in ms[k]), statistics.median(ms[k])))
-    r = statistics.median(ms['this tree']) / statistics.median(ms['parent'])
-    print('    this tree / parent: %.4f (%+.2f %%; the documented run-to-run spread of the batch time is +-1.5 %%)' % (r, (r - 1) * 100))
+    del env, model
+    common.close_arms(arms)
 
 
 def main():
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit: adds the bench.py A/B against it')
-    args = ap.parse_args()
+    parent = common.parent_tree_arg()
     import torch
     assert torch.cuda.is_available(), 'needs the MI355X'
     print('running return-based reward scaling next to the division and clamp it replaces (tools/reward_scale_profile.py), %s'
           % torch.cuda.get_device_name(0))
-    resources()
+    common.resources(27, names=('reward_scale_scan_kernel', 'reward_scale_merge_kernel', 'reward_scale_apply_kernel'))
     for shape in SHAPES:
         measure(*shape)
     for first in ('key absent', 'reward_scale = return'):      # two fresh pairs of trainers, built in either order
         training_ab(first)
-    if args.parent_tree:
-        bench_ab(args.parent_tree)
+    if parent:
+        common.bench_ab(parent)
     return 0
 
 
