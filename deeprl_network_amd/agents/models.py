@@ -319,7 +319,7 @@ class IA2C:
         N, E, T, H, d = self.n_agent, self.E, self.n_step, self.n_lstm, self.device
         KX = p.params[p.k_wx].shape[1]
         # one zero slab more than needed, so that [S | .] and the state sequences have the SAME (T + 1)-slab shape -- the
-        # update's weight-gradient GEMMs then read the saved buffers in place (ops._lstm_seq_x_backward, agents/sequence.py)
+        # update's weight-gradient GEMMs then read the saved buffers in place (ops.seq_rows_pair / lstm_weight_grads)
         self.S_ext = torch.zeros(N, T + 1, E, KX, dtype=F32, device=d)
         self.S_buf = self.S_ext[:, :T]
         self.G_buf = torch.zeros(N, T, E, 4 * H, dtype=F32, device=d)

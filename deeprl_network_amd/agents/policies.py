@@ -524,8 +524,8 @@ class BatchedPolicy:
     @property
     def bptt_takes_head_dy(self):
         """The backward of `unroll_saved` understands ops.head_dy_placeholder (the heads' dL/dh as dy8, expanded inside the
-        BPTT kernel): the uncoupled nets' recurrence (ops._lstm_seq_x_backward) and the coupled ones (agents/sequence.py; DIAL overrides
-        this: dy8 only where its one-launch kernel applies, else the step-wise pair, which takes the tensor)."""
+        BPTT kernel): the uncoupled nets' recurrence (ops._lstm_seq_x_backward) and the coupled ones (agents/sequence.py `_choose_tier`, which
+        also turns dy8 back into the tensor for a tier without a dy8 form; DIAL overrides this: dy8 only where its one-launch kernel applies)."""
         if self.coupled and os.environ.get('NMARL_BPTT_HEAD_DY_COUPLED', '1') == '0':      # (A/B switch for the coupled kernels alone)
             return False
         return self.xside
@@ -539,7 +539,7 @@ class BatchedPolicy:
     def unroll_saved(self, X, FP, S, G, Hall, Call, done, masked_steps=None, S_ext=None, S_bits=None):
         """`unroll` for a batch whose forward pass the rollout already did with the CURRENT weights: S [N,T,E,KX] the
         LSTM inputs, G the gates, Hall / Call [N,T+1,E,H] the state sequences it saved.  Sets up the backward only.
-        S_ext: the [N,T+1,E,KX] buffer S is the first T slabs of (last slab zero), see ops._lstm_seq_x_backward."""
+        S_ext: the [N,T+1,E,KX] buffer S is the first T slabs of (last slab zero), see ops.seq_input_in_place."""
         T, E = done.shape
         Xv = X.reshape(T * E, self.N, X.shape[-1]).transpose(0, 1)          # gathered [.., n_obs] or compact [.., n_feat] slab
         if self.coupled:

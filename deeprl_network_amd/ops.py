@@ -1130,10 +1130,13 @@ def head_dy_placeholder(dy8, hw, like):
 
 
 def take_head_dy(dHs):
-    """(dy8, hw) if dHs is the placeholder of head_dy_placeholder (nothing else contributed to dL/dh), else None."""
-    pend = _pending_head_dy.pop(dHs.device, None)
+    """(dy8, hw) if dHs is the placeholder of head_dy_placeholder (nothing else contributed to dL/dh), else None.  Only a match
+    consumes the pending entry: after a backward whose recurrence got something else the entry is still there, and the caller that
+    made the placeholder notices (models._loss_backward_fused)."""
+    pend = _pending_head_dy.get(dHs.device)
     if pend is None or dHs.data_ptr() != pend[0].data_ptr() or any(dHs.stride()):
         return None
+    del _pending_head_dy[dHs.device]
     return pend[1], pend[2]
 
 
@@ -1251,6 +1254,34 @@ def reverse_neighbor_table(nbr_idx, kind):
                 r_max=r_max, r_row=r_row, symmetric=sym)
 
 
+_nbr_derived = {}
+NBR_DERIVED_KEEP = 8                 # entries kept per process (a run uses two or three; a dropped one is rebuilt on its next use)
+_keepalive = [None]
+
+
+def nbr_derived(nbr_idx, what, build):
+    """build(), once per (neighbour table, what): the ONE cache of what the update derives from a policy's table on the host (the
+    reverse tables of the BPTT kernels, the gather runs of agents/sequence.py) -- building reads the table back (.cpu()), so the
+    first use must lie outside any capture (the trainer captures after an eager batch).  Bounded, least recently used first (a
+    test session sees many tables); an entry keeps nbr_idx alive, so its key stays unique; a captured launch that holds a
+    table's addresses keeps it through the sink of `keepalive_begin`."""
+    key = (nbr_idx.data_ptr(), nbr_idx.device, tuple(nbr_idx.shape), what)
+    ent = _nbr_derived.pop(key, None)
+    if ent is None:
+        while len(_nbr_derived) >= NBR_DERIVED_KEEP:
+            _nbr_derived.pop(next(iter(_nbr_derived)))
+        ent = (nbr_idx, build())
+    _nbr_derived[key] = ent                                    # most recently used last
+    if _keepalive[0] is not None:
+        _keepalive[0].append(ent)
+    return ent[1]
+
+
+def reverse_table(nbr_idx, kind):
+    """reverse_neighbor_table(nbr_idx, kind), built once per table."""
+    return nbr_derived(nbr_idx, ('reverse', kind), lambda: reverse_neighbor_table(nbr_idx, kind))
+
+
 def bptt_coupled_supported(kind, m_max, H, rev=None):
     """nmarl_lstm_bptt_coupled handles this recurrence: 64-unit cells, message rows of 64 or 128 floats; with the reverse table
     at hand also its fan-in (lstm_comm: at most 2 sources per agent -- the launcher has no 4-source instantiation of that
@@ -1262,13 +1293,12 @@ def bptt_coupled_supported(kind, m_max, H, rev=None):
 
 
 _coupled_ws = {}
-_keepalive = [None]
 
 
 def keepalive_begin(sink):
-    """While a caller captures launches in a hipGraph: every pooled workspace handed out until `keepalive_end` is also
-    appended to `sink` (a list the graph's owner keeps), so that the pool's LRU eviction cannot free memory whose address a
-    captured graph replays."""
+    """While a caller captures launches in a hipGraph: every pooled workspace and every cached table (nbr_derived) handed out
+    until `keepalive_end` is also appended to `sink` (a list the graph's owner keeps), so that the pools' LRU eviction cannot
+    free memory whose address a captured graph replays."""
     _keepalive[0] = sink
 
 
@@ -1390,19 +1420,8 @@ def dial_bptt_table(nbr_idx, H):
     m_max = nbr_idx.shape[1]
     if not bptt_dial_supported(m_max, H, device=nbr_idx.device):
         return None
-    key = (nbr_idx.data_ptr(), nbr_idx.device, tuple(nbr_idx.shape))
-    ent = _dial_tables.pop(key, None)
-    if ent is None:
-        while len(_dial_tables) >= DIAL_TABLES_KEEP:           # least recently used first (a run has one table; a test session many)
-            _dial_tables.pop(next(iter(_dial_tables)))
-        ent = (nbr_idx, reverse_neighbor_table(nbr_idx, COUPLED_NC))                      # keeps nbr_idx alive: the key stays unique
-    _dial_tables[key] = ent                                    # most recently used last
-    rev = ent[1]
+    rev = reverse_table(nbr_idx, COUPLED_NC)
     return rev if rev is not None and bptt_dial_supported(m_max, H, rev=rev, device=nbr_idx.device) else None
-
-
-_dial_tables = {}
-DIAL_TABLES_KEEP = 8                 # reverse tables kept per process (a dropped one is rebuilt on its next use)
 
 
 def bptt_dial(rev, m_max, G, Call, done, dHs, ws, wm, img_f, hm, msg, dZ, DS, D1, D2, mode=0, head_dy=None, want_state_grad=False):
@@ -1425,8 +1444,6 @@ def bptt_dial(rev, m_max, G, Call, done, dHs, ws, wm, img_f, hm, msg, dZ, DS, D1
     if hm.dim() != 4 or hm.stride(3) != 1 or hm.shape[3] != H or msg.shape[1] < T:
         raise ValueError('bptt_dial: hm must be an [N,T,E,H] view with unit column stride, msg [N,>=T,E,H]')
     w = _coupled_workspace(G.device, N, E, K, T, dial=True)
-    if _keepalive[0] is not None:
-        _keepalive[0].append(rev)             # dial_bptt_table keeps a bounded number of tables: a captured launch holds this one's addresses
     a = _lib.BpttDial()
     a.N, a.T, a.H, a.m_max, a.r_max, a.r_row, a.symmetric, a.mode = N, T, H, m_max, rev['r_max'], rev['r_row'], int(rev['symmetric']), int(mode)
     a.E = E
@@ -1509,6 +1526,98 @@ def lstm_cell_infer(z, bias, c_prev, done, c_out, h_out, z2=None):
     return h_out, c_out
 
 
+# ---- the update's reverse recurrence: what its tiers and buffer layouts share (the uncoupled Functions below, agents/sequence.py).
+# A sequence operand is a pair (full, steps): steps the [N,T,E,W] tensor of the T steps; full the contiguous (T + 1)-slab buffer
+# whose first T slabs `steps` is, last slab zero -- or None (a flat operand).  With two padded operands a product over all rows
+# reads both buffers in place: no copy of the state sequence (which is (T + 1) slabs anyway), no gathered or masked copy.
+def seq_buffer(N, T, E, W, device, padded):
+    """A sequence operand to be written: (T + 1) slabs with the last one zeroed, or T slabs."""
+    if not padded:
+        return None, torch.empty(N, T, E, W, dtype=F32, device=device)
+    full = torch.empty(N, T + 1, E, W, dtype=F32, device=device)
+    full[:, T].zero_()
+    return full, full[:, :T]
+
+
+def seq_operand(x, T):
+    """A saved sequence [N,T,E,W] or [N,T+1,E,W] as an operand: padded iff it is a contiguous (T + 1)-slab buffer."""
+    if x.shape[1] == T + 1 and x.is_contiguous():
+        return x, x[:, :T]
+    return None, x[:, :T]
+
+
+def seq_input_in_place(s, s_ext, Hall):
+    """The LSTM inputs s [N,T,E,KX] were handed over as the first T slabs of the contiguous buffer s_ext [N,T+1,E,KX], and the state
+    sequence is contiguous: the weight gradients can read both in place."""
+    N, T, E, KX = s.shape
+    return (s_ext is not None and tuple(s_ext.shape) == (N, T + 1, E, KX) and s_ext.is_contiguous() and Hall.is_contiguous() and
+            s.data_ptr() == s_ext.data_ptr())
+
+
+def seq_rows(x):
+    """[N,slabs,E,W] -> [N,slabs*E,W] (a view of a contiguous buffer and of the first T slabs of one)."""
+    return x.reshape(x.shape[0], -1, x.shape[3])
+
+
+def seq_rows_pair(a, b):
+    """The operands of a product over all rows of two sequences: (T + 1) E rows of both buffers iff both are padded, else T E."""
+    if a[0] is not None and b[0] is not None:
+        return seq_rows(a[0]), seq_rows(b[0])
+    return seq_rows(a[1]), seq_rows(b[1])
+
+
+def masked_h_rows(Hall, keep, masked, in_place):
+    """h_{t-1} keep_t of every step, the operand of the recurrent weight's gradient: Hall [N,T+1,E,H], keep [T,E]; steps outside
+    `masked` have done_t = 0 by contract.  in_place: masked in the saved buffer itself (the next rollout rewrites it) -> its
+    (T + 1) E rows; else a masked copy -> T E rows."""
+    N, T1, E, H = Hall.shape
+    T = T1 - 1
+    if in_place:
+        with torch.no_grad():
+            for t in masked:
+                Hall[:, t].mul_(keep[t].view(1, E, 1))
+        return Hall.view(N, T1 * E, H)
+    if len(masked) == T:
+        return (Hall[:, :T] * keep.view(1, T, E, 1)).reshape(N, T * E, H)
+    Hk = Hall[:, :T].clone()
+    for t in masked:
+        Hk[:, t].mul_(keep[t].view(1, E, 1))
+    return Hk.view(N, T * E, H)
+
+
+def lstm_weight_grads(S, Hall, dZ, keep, masked):
+    """dwx = s^T dZ and dwh = (h keep)^T dZ as single GEMMs over all rows; S, dZ sequence operands.  With dZ padded the state
+    sequence is masked in place: whatever reads the un-masked h_{t-1} (the message layers, quirk Q3) comes before this call."""
+    in_place = dZ[0] is not None
+    dwh = wgrad(masked_h_rows(Hall, keep, masked, in_place), seq_rows(dZ[0] if in_place else dZ[1]))
+    return wgrad(*seq_rows_pair(S, dZ)), dwh
+
+
+def bptt_loop(G, Call, done, keep, dHs, masked, dZ, wh_t, wx_t=None, w2_t=None, adjoint=None):
+    """The torch tier of the reverse recurrence, for every net: per step cell_bwd (dL/dh_t = the heads' part dHs[:, t] + the
+    recurrent part, summed inside the kernel) and the dgrad products dhd = (dZ_t wh^T) keep_t, dx = dZ_t wx^T -- as ONE GEMM where
+    w2_t = [wx; wh]^T is at hand (adjacent rows of the flat parameter buffer).  adjoint(t, dx, dhd) -> dL/dh_{t-1}: the coupled nets'
+    message adjoint (the only part that varies); None: dhd itself.  Writes dZ [N,T,E,4H] -> (dL/dh0, dL/dc0)."""
+    N, T, E, H4 = G.shape
+    H = H4 // 4
+    dh_rec = None
+    dc = torch.zeros(N, E, H, dtype=F32, device=G.device)
+    dc_next = torch.empty_like(dc)
+    for t in range(T - 1, -1, -1):
+        cell_bwd(G[:, t], Call[:, t], Call[:, t + 1], done[t], dHs[:, t], dc, dZ[:, t], dc_next, dh2=dh_rec)
+        dc, dc_next = dc_next, dc
+        if w2_t is not None:
+            d2 = torch.bmm(dZ[:, t], w2_t)
+            dx, dhd = d2[..., :H], d2[..., H:]
+        else:
+            dx = None if wx_t is None else torch.bmm(dZ[:, t], wx_t)
+            dhd = torch.bmm(dZ[:, t], wh_t)
+        if t in masked:
+            dhd = dhd * keep[t].view(1, E, 1)
+        dh_rec = dhd if adjoint is None else adjoint(t, dx, dhd)
+    return dh_rec, dc
+
+
 class _LstmSequence(torch.autograd.Function):
     """cuDNN-style fused recurrence for agent-batched LSTMs without cross-agent coupling
     (LstmPolicy / FPPolicy, agents/utils.py:87-115 unrolled over n_step):
@@ -1549,33 +1658,12 @@ class _LstmSequence(torch.autograd.Function):
     def backward(ctx, dHs):
         G, Hall, Call, wh, done = ctx.saved_tensors
         N, T, E, H4 = G.shape
-        H = H4 // 4
-        dHs = dHs.contiguous()
         dZ = torch.empty_like(G)
         keep = (1.0 - done)
-        dh_rec = None
-        dc = torch.zeros(N, E, H, dtype=F32, device=G.device)
-        dc_next = torch.empty_like(dc)
-        wh_t = wh.transpose(1, 2)
-        for t in range(T - 1, -1, -1):
-            # dL/dh_t = head part dHs[:, t] (strided slot) + recurrent part dh_rec, summed inside the kernel
-            cell_bwd(G[:, t], Call[:, t], Call[:, t + 1], done[t], dHs[:, t], dc, dZ[:, t], dc_next, dh2=dh_rec)
-            dc, dc_next = dc_next, dc
-            dh_rec = torch.bmm(dZ[:, t], wh_t)
-            if t in ctx.masked:
-                dh_rec = dh_rec * keep[t].view(1, E, 1)
+        dh_rec, dc = bptt_loop(G, Call, done, keep, dHs.contiguous(), ctx.masked, dZ, wh.transpose(1, 2))
         dZf = dZ.view(N, T * E, H4)
-        # h_{t-1} * keep_t for all t: Hall[:, :T] is a strided view (agent stride (T+1)*E*H)
-        if len(ctx.masked) == T:
-            Hprev = (Hall[:, :T] * keep.view(1, T, E, 1)).reshape(N, T * E, H)
-        else:
-            Hprev = Hall[:, :T].clone()
-            for t in ctx.masked:
-                Hprev[:, t].mul_(keep[t].view(1, E, 1))
-            Hprev = Hprev.view(N, T * E, H)
-        dwh = wgrad(Hprev, dZf)
-        db = dZf.sum(dim=1)
-        return dZ, dwh, db, dh_rec, dc, None, None
+        dwh = wgrad(masked_h_rows(Hall, keep, ctx.masked, False), dZf)
+        return dZ, dwh, dZf.sum(dim=1), dh_rec, dc, None, None
 
 
 def lstm_sequence(pre, wh, b, h0, c0, done, masked_steps=None):
@@ -1631,56 +1719,23 @@ def _lstm_seq_x_backward(G, Hall, Call, s, wx, wh, done, masked, dHs, need_ds, w
     if head_dy is None:
         dHs = dHs.contiguous()
     keep = (1.0 - done)
-    KX = s.shape[3]
-    # In-place weight gradients: with the LSTM inputs handed over as the first T slabs of a (T + 1)-slab buffer (last slab
-    # zero), dZ allocated the same way (last slab zero) and the h sequence being (T + 1) slabs anyway, all three are plain
-    # contiguous [N, (T+1)*E, .] operands of the row-split GEMMs: no masked COPY of the h sequence (0.2 ms at T*E*N = 2 M
-    # rows).  The few maskable steps are masked in the saved buffer itself (the rollout rewrites it next batch).
-    ext = (s_ext is not None and len(masked) < T and s_ext.shape == (N, T + 1, E, KX) and s_ext.is_contiguous() and Hall.is_contiguous()
-           and s.data_ptr() == s_ext.data_ptr() and ((T + 1) * E) % WGRAD_SPLIT == 0)
-    if ext:
-        dZe = torch.empty(N, T + 1, E, H4, dtype=F32, device=G.device)
-        dZe[:, T].zero_()
-        dZ = dZe[:, :T]
-    else:
-        dZ = torch.empty_like(G)
+    # In-place weight gradients (the padded layout, see seq_buffer): no masked COPY of the h sequence (0.2 ms at T*E*N = 2 M
+    # rows); the few maskable steps are masked in the saved buffer itself.  Not when every step masks, nor when the row-split of
+    # wgrad does not divide the (T + 1) E rows.
+    in_place = len(masked) < T and ((T + 1) * E) % WGRAD_SPLIT == 0 and seq_input_in_place(s, s_ext, Hall)
+    dZ = seq_buffer(N, T, E, H4, G.device, in_place)
     db = None
     if one_launch:
         # the whole reverse recurrence in one launch; the bias gradient comes out of the same pass.  It multiplies by
         # (1 - done_t) at every step: exact also for the steps outside `masked`, whose done_t is zero by contract
-        db, dh_rec, dc = bptt_seq(G, Call, done, dHs, lstm_bptt_wimage(None, wh), dZ, want_state_grad=want_state_grad, head_dy=head_dy)
+        db, dh_rec, dc = bptt_seq(G, Call, done, dHs, lstm_bptt_wimage(None, wh), dZ[1], want_state_grad=want_state_grad, head_dy=head_dy)
     else:
-        dh_rec = None
-        dc = torch.zeros(N, E, H, dtype=F32, device=G.device)
-        dc_next = torch.empty_like(dc)
-        wh_t = wh.transpose(1, 2)
-        for t in range(T - 1, -1, -1):
-            cell_bwd(G[:, t], Call[:, t], Call[:, t + 1], done[t], dHs[:, t], dc, dZ[:, t], dc_next, dh2=dh_rec)
-            dc, dc_next = dc_next, dc
-            dh_rec = torch.bmm(dZ[:, t], wh_t)
-            if t in masked:
-                dh_rec = dh_rec * keep[t].view(1, E, 1)
-    dZf = dZ.reshape(N, T * E, H4)              # a view in both layouts (agent-strided when `ext`)
-    if ext:
-        with torch.no_grad():
-            for t in masked:
-                Hall[:, t].mul_(keep[t].view(1, E, 1))
-        dZx = dZe.view(N, (T + 1) * E, H4)
-        dwh = wgrad(Hall.view(N, (T + 1) * E, H), dZx)
-        dwx = wgrad(s_ext.view(N, (T + 1) * E, KX), dZx)
-    else:
-        if len(masked) == T:
-            Hprev = (Hall[:, :T] * keep.view(1, T, E, 1)).reshape(N, T * E, H)
-        else:
-            Hprev = Hall[:, :T].clone()
-            for t in masked:
-                Hprev[:, t].mul_(keep[t].view(1, E, 1))
-            Hprev = Hprev.view(N, T * E, H)
-        dwh = wgrad(Hprev, dZf)
-        dwx = wgrad(s.reshape(N, T * E, KX), dZf)
+        dh_rec, dc = bptt_loop(G, Call, done, keep, dHs, masked, dZ[1], wh.transpose(1, 2))
+    dwx, dwh = lstm_weight_grads((s_ext if in_place else None, s), Hall, dZ, keep, masked)
+    dZf = seq_rows(dZ[1])                       # a view in both layouts (agent-strided when padded)
     if db is None:
         db = dZf.sum(dim=1)
-    ds = torch.bmm(dZf, wx.transpose(1, 2)).view(N, T, E, KX) if need_ds else None
+    ds = torch.bmm(dZf, wx.transpose(1, 2)).view(N, T, E, s.shape[3]) if need_ds else None
     return ds, dwx, dwh, db, dh_rec, dc
 
 
