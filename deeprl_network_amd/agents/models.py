@@ -25,6 +25,7 @@ Engine (per n_step batch, E replicas, N agents):
             opt-in ppo_target_kl: the steps behind the first epoch whose pooled approx_kl exceeds it change nothing, decided on
             the device (nmarl_ppo_kl_sum -> all-reduce -> nmarl_ppo_kl_gate -> the optimiser's status word)].
 """
+import functools
 import logging
 import os
 
@@ -37,6 +38,23 @@ from .policies import (ConsensusPolicy, DIALMultiAgentPolicy, FPPolicy, IC3Multi
 from .utils import Scheduler
 
 F32 = torch.float32
+
+
+class LockStepForm:
+    """How a lock-step of `model` is launched (IA2C.lock_step_form).  Made anew per lock-step and per update, each field evaluated from the
+    switches when it is read: a reader pays only for the predicates it asks (the eager rollout's host time; `encoders` is asked for thrice)."""
+    def __init__(self, model):
+        self.m, self.p = model, model.policy
+
+    # 1: policy step and value re-step in one kernel (without saved activations a coupled net takes the pair); else 2
+    launches = property(lambda f: 1 if (f.p.pv_one_launch(f.m.E) if f.m.save_acts else f.p.fused_pv) else 2)
+    # the input encoders inside that launch: 'both', 'ob' (the observation encoder) or 'none'
+    encoders = functools.cached_property(lambda f: 'none' if not f.m.save_acts else 'both' if f.p.enc_in_kernel(f.m.E, f.m.compact_obs) else
+                                         'ob' if f.p.encodes_in_step(f.m.E, f.m.compact_obs) else 'none')
+    # the re-step's message term goes on to the next lock-step's policy step (`_msg_carry`)
+    carry = property(lambda f: bool(f.m.save_acts and f.launches == 1 and f.m._carries_msg()))
+    # the launch writes the sign image of its encoders' output (`_relu_bits`)
+    sign_image = property(lambda f: f.encoders == 'both' and f.p.enc_writes_bits and os.environ.get('NMARL_FC_BWD_PAIR', '1') != '0')
 
 
 # Readers of the optional MODEL_CONFIG keys (absent: the default, so every reference ini runs unchanged)
@@ -329,11 +347,9 @@ class IA2C:
         # coupled nets: further per-step message terms the backward needs (policy.save_spec)
         # (`save_next` keys: one slab more -- the policy step of lock-step t fills slot t + 1, e.g. lstm_dial's message vectors)
         # (`save_pad` keys: one ZERO slab more, like S_ext -- the update's weight-gradient GEMM reads the (T + 1)-slab buffer in place)
-        nxt, pad = getattr(p, 'save_next', ()), getattr(p, 'save_pad', ())
-        full = {k: torch.zeros(N, T + 1 if (k in nxt or k in pad) else T, E, w, dtype=F32, device=d) for k, w in p.save_spec().items()}
+        full = {k: torch.zeros(N, T + 1 if (k in p.save_next or k in p.save_pad) else T, E, w, dtype=F32, device=d) for k, w in p.save_spec().items()}
         p._extra = {k: v[:, :T] for k, v in full.items()}
         p._extra_full = full
-        self._extra_next = {k: full[k] for k in nxt if k in full}
         self.save_acts = True
         return True
 
@@ -351,20 +367,21 @@ class IA2C:
         return True
 
     compact_obs = False
+    _enc_boot = None           # the bootstrap step's scratch LSTM input (encode_target)
 
     def _save_slots(self, t):
         """Slots of lock-step t in the saved activations, for the policy step of a coupled net."""
-        d = {k: v[:, t] for k, v in self.policy._extra.items()}
+        p = self.policy
+        d = {k: v[:, t] for k, v in p._extra.items()}
         d['S'] = self.S_buf[:, t]
-        for k, v in getattr(self, '_extra_next', {}).items():
-            d[k + '_next'] = v[:, t + 1]
+        d.update({k + '_next': p._extra_full[k][:, t + 1] for k in p.save_next if k in p._extra_full})
         return d
 
     # ------------------------------------------------------------------ batched engine
     def reset_states(self, mask=None):
         """Policy._reset (policies.py:151-154, 334-336) for all replicas or those with mask != 0;
         also restores the uniform fingerprint of a fresh episode (cacc_env.py:184)."""
-        self.policy.invalidate_cached_msg()
+        self.invalidate_carried()
         if mask is None:
             for s in (self.h_fw, self.c_fw, self.h_bw, self.c_bw):
                 s.zero_()
@@ -374,6 +391,12 @@ class IA2C:
             for s in (self.h_fw, self.c_fw, self.h_bw, self.c_bw):
                 s.mul_(keep)
             self.fp.mul_(keep).add_((1.0 - keep) * self.fp_uniform)
+
+    def invalidate_carried(self):
+        """The recurrent state is written out of band (a reset, a restored snapshot, the batch hand-over's kernel): the next lock-step takes
+        neither the carried message term (include/nmarl.h: carry_in = NULL after such a write) nor lstm_dial's cached message vectors."""
+        self._carry_holds = -1
+        self.policy.invalidate_cached_msg()
 
     def _policy_step(self, obs, done, done_is_zero=False):
         """forward('p'): advances states_fw (policies.py:119-134); returns the pi LOGITS' softmax."""
@@ -400,7 +423,7 @@ class IA2C:
         inputs must stay zero: it pads the update's weight-gradient GEMMs)."""
         if t < self.n_step:
             return self.S_buf[:, t]
-        if getattr(self, '_enc_boot', None) is None:
+        if self._enc_boot is None:
             self._enc_boot = torch.zeros_like(self.S_buf[:, 0])
         return self._enc_boot
 
@@ -411,64 +434,75 @@ class IA2C:
         new policy into buf_fp[t+1] (env.update_fingerprint, utils.py:173).  done [E] f32 is the pre-step
         flag.  Two kernels after the encoder when the heads fuse (H = 64).  Returns the action slot (input
         of the env kernel)."""
-        t = self.t
-        p = self.policy
-        ob = None
+        return self._lock_step(self.t, done, dict(mode=mode, u=u, seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev),
+                               done_is_zero, pre_encoded, env_step)[0]
+
+    def bootstrap(self, done, action_scratch, mode=ops.SAMPLE_PHILOX, u=None, seed=0, env_id_base=0,
+                  step=0, step_dev=None, done_is_zero=False, pre_encoded=False):
+        """R for the unfinished replicas (utils.py:192-196) from buf_x[T] / buf_fp[T]: one more policy
+        step (which advances states_fw -- quirk Q2) and the double-stepped value."""
+        assert self.t == self.n_step
+        return self._lock_step(self.n_step, done, dict(mode=mode, u=u, seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev),
+                               done_is_zero, pre_encoded, None, act_out=action_scratch)[1]
+
+    def lock_step_form(self):
+        """The one description of a lock-step's launches: read by `_lock_step`, `update_grads` and BatchedTrainer (which adds the env's part)."""
+        return LockStepForm(self)
+
+    def _lstm_input(self, t, form, pre_encoded, env_step):
+        """(enc, ob) of lock-step t.  enc: the LSTM input's h-independent part, shared by the policy step and the value re-step (Q1)
+        -- or, with encoders inside the launch, the slot their output goes to.  ob: what those encoders read, else None."""
+        p, boot, x = self.policy, t == self.n_step, self.buf_x[t]
+        if pre_encoded:             # the env kernel of the previous lock-step already encoded buf_x[t] / fp[t] into its target
+            return self.encode_target(t), None
+        if form.encoders == 'both':
+            # both encoders inside the launch, from the compact observation and the fingerprints of slot t (env_step: the CACC env step too).
+            # Nothing of the bootstrap step is kept; a coupled net's encoders reach the K loop THROUGH the x slot, a scratch one there
+            return (self.encode_target(t) if (p.coupled or not boot) else None), \
+                dict(x=x, fp=self.fp, env=env_step, bits=self._relu_bits(t) if (form.sign_image and not boot) else None)
+        slot = None
+        if self.save_acts and not boot:
+            slot = self.S_buf[:, t]
+            if 'ENC' in p._extra:   # the encoder output is NOT the LSTM input itself (CommNet: s = enc + message term): kept per lock-step, so
+                slot, p._enc_was_saved = p._extra['ENC'][:, t], True          # that the update's encoder backward needs no forward pass
+        if form.encoders == 'ob':   # the observation encoder inside the launch, writing to `enc` (env_step: the grid env step as well)
+            return (slot if slot is not None else self.encode_target(t)), dict(x=x, genv=env_step)
+        return p.encode(x, self.fp, out=slot), None
+
+    def _lock_step(self, t, done, draw, done_is_zero=False, pre_encoded=False, env_step=None, act_out=None):
+        """Lock-step t = 0..n_step of a batch (t = n_step: the bootstrap step, whose action goes to the caller's scratch `act_out`):
+        -> (action slot, value slot).  What varies with t is the table below; the launches are the same code."""
+        p, T, saved = self.policy, self.n_step, self.save_acts
         if t == 0:
             p.refresh_wimage()                             # weights change between batches only (inside the hipGraph: one
-            if self.save_acts:                             # small node)
+            if saved:                                      # small node)
                 self.H_all[:, 0].copy_(self.h_fw)
                 self.C_all[:, 0].copy_(self.c_fw)
-        # enc is shared by the policy step and the value re-step (Q1)
-        if pre_encoded:             # the env kernel of the previous lock-step already encoded buf_x[t] / fp[t] into slot t
-            enc = self.S_buf[:, t]
-        elif self.save_acts and p.enc_in_kernel(self.E, self.compact_obs):
-            # the lock-step kernel runs both input encoders itself, from the compact observation and the fingerprints of slot t,
-            # and leaves the LSTM input in slot t of the saved activations: no encoder launch at all
-            # (env_step: the same launch also steps the env with the actions it draws -- CACCBatchEnv.inkernel_step)
-            enc, ob = self.S_buf[:, t], dict(x=self.buf_x[t], fp=self.fp, env=env_step, bits=self._relu_bits(t))
-        elif self.save_acts and 'ENC' in p._extra:
-            # nets whose encoder output is NOT the LSTM input itself (CommNet: s = enc + message term): kept per lock-step so
-            # that the update's encoder backward needs no forward pass.  Where the one-launch step runs the encoder too, `enc`
-            # is only the slot its output goes to
-            if p.encodes_in_step(self.E, self.compact_obs):
-                # (env_step: the launch also steps the grid env, on compute units its LSTM blocks leave idle -- LargeGridBatchEnv.inkernel_step)
-                enc, ob = p._extra['ENC'][:, t], (self.buf_x[t] if env_step is None else dict(x=self.buf_x[t], genv=env_step))
-            else:
-                enc = p.encode(self.buf_x[t], self.fp, out=p._extra['ENC'][:, t])
-            p._enc_was_saved = True
-        else:
-            enc = p.encode(self.buf_x[t], self.fp, out=self.S_buf[:, t]) if self.save_acts else p.encode(self.buf_x[t], self.fp)
-        if env_step is not None and (ob is None or not isinstance(ob, dict)):
+        form = self.lock_step_form()                       # (behind refresh_wimage: a coupled net's one-launch form needs its message image)
+        one = form.launches == 1
+        if env_step is not None and (pre_encoded or form.encoders == 'none'):
             raise ValueError('env_step needs the lock-step kernel that runs the input encoders itself (policy.enc_in_kernel / encodes_in_step)')
-        draw = dict(mode=mode, u=u, seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev)
-        if self.save_acts and p.pv_one_launch(self.E):
-            # the policy step reads slot t of the state sequences and writes slot t + 1, gates into G[:, t]; the value
-            # (critic's h part) goes to the agent-major buffer, its neighbour-action term is added in update().  Coupled nets:
-            # the policy step's message terms go to their save slots, the re-step's come from the new states of ALL agents
-            p.step_policy_value(enc, self.H_all[:, t], self.C_all[:, t], done, self.buf_fp[t + 1], self.buf_act[t],
-                                self.buf_vn[:, t], h_out=self.H_all[:, t + 1], c_out=self.C_all[:, t + 1],
-                                gates=self.G_buf[:, t], defer_action_term=True,
-                                **(dict(save=self._save_slots(t), ob=ob, carry=self._msg_carry(t)) if p.coupled else
-                                   (dict(ob=ob) if ob is not None else {})),
-                                **draw)
-            return self.buf_act[t]
-        if self.save_acts:
-            # coupled nets: policy step (saves its message terms, gates, states), then the value re-step from the new
-            # states of ALL agents (its message term is recomputed from them; nothing of it is kept)
-            p.step_policy(enc, self.H_all[:, t], self.C_all[:, t], done, self.H_all[:, t + 1], self.C_all[:, t + 1],
-                          self.buf_fp[t + 1], self.buf_act[t], done_is_zero, gates=self.G_buf[:, t], save=self._save_slots(t),
-                          **draw)
-            p.step_value(enc, self.H_all[:, t + 1], self.C_all[:, t + 1], done, self._h2, self._c2, self.buf_act[t],
-                         self.buf_v[t], done_is_zero)
-            return self.buf_act[t]
-        if p.fused_pv:
-            p.step_policy_value(enc, self.h_fw, self.c_fw, done, self.buf_fp[t + 1], self.buf_act[t], self.buf_v[t], **draw)
-            return self.buf_act[t]
-        p.step_policy(enc, self.h_fw, self.c_fw, done, self.h_fw, self.c_fw, self.buf_fp[t + 1], self.buf_act[t],
-                      done_is_zero, **draw)
-        p.step_value(enc, self.h_fw, self.c_fw, done, self._h2, self._c2, self.buf_act[t], self.buf_v[t], done_is_zero)
-        return self.buf_act[t]
+        enc, ob = self._lstm_input(t, form, pre_encoded, env_step)
+        # saved activations: the policy step reads slot t of the state sequences; else the persistent state, advanced in place
+        h, c = (self.H_all[:, t], self.C_all[:, t]) if saved else (self.h_fw, self.c_fw)
+        if t < T:
+            # ... and writes slot t + 1, gates into G[:, t]; in one launch the value (critic's h part) goes to the agent-major buffer, its
+            # neighbour-action term is added in update().  Coupled nets: the POLICY step's message terms go to their save slots
+            pi, act, v = self.buf_fp[t + 1], self.buf_act[t], (self.buf_vn[:, t] if (saved and one) else self.buf_v[t])
+            h_out, c_out = (self.H_all[:, t + 1], self.C_all[:, t + 1]) if saved else (self.h_fw, self.c_fw)
+            gates, save = (self.G_buf[:, t] if saved else None), (self._save_slots(t) if (saved and p.coupled) else None)
+        else:
+            # the bootstrap step: from slot T of the sequences into the persistent state; nothing of it is kept
+            pi, act, v = self._pi_boot, act_out, self._v_boot
+            h_out, c_out, gates, save = self.h_fw, self.c_fw, None, None
+        if one:            # (without saved activations the fused step advances the state in place: no h_out / c_out)
+            p.step_policy_value(enc, h, c, done, pi, act, v, h_out=h_out if saved else None, c_out=c_out if saved else None, gates=gates,
+                                defer_action_term=saved and t < T, save=save, ob=ob,
+                                carry=self._msg_carry(t) if (saved and p.coupled) else None, **draw)
+        else:
+            p.step_policy(enc, h, c, done, h_out, c_out, pi, act, done_is_zero, gates=gates, save=save, **draw)
+            p.step_value(enc, h_out, c_out, done, self._h2, self._c2, act, v, done_is_zero)
+        return act, v
 
     _carry_buf = None
     _carry_holds = -1          # the lock-step whose policy-step message term `_carry_buf` holds (written by the re-step of the one before)
@@ -479,30 +513,30 @@ class IA2C:
         `_carry_buf` (and CommNet's mean rows in slot t + 1 of the saved means) and launch t + 1 starts from it: no neighbour rows,
         no product in front of its K loop.  Lock-step 0 computes its own (the batch boundary reset finished replicas' states)."""
         p = self.policy
-        if not p.coupled or getattr(p, 'msg_kind', 0) not in (ops.MSG_GATHER_RELU, ops.MSG_MEAN_ADD) or \
-                os.environ.get('NMARL_MSG_CARRY', '1') == '0':
+        if not self._carries_msg():
             return None
         if self._carry_buf is None:
             self._carry_buf = torch.zeros(self.n_agent, self.E, self.n_lstm, dtype=F32, device=self.device)
         d = dict(carry_in=self._carry_buf if (t > 0 and self._carry_holds == t) else None,
                  carry_out=self._carry_buf if t < self.n_step else None)
-        mm = getattr(p, '_extra_full', {}).get('MM')
+        mm = p._extra_full.get('MM')
         if mm is not None and t + 1 < self.n_step and p.msg_kind == ops.MSG_MEAN_ADD:
             d['mean_next'] = mm[:, t + 1]
         self._carry_holds = t + 1 if t < self.n_step else -1
         return d
 
+    def _carries_msg(self):
+        """The one-launch lock-steps of this net hand the re-step's message term on (NMARL_MSG_CARRY=0: every step computes its own)."""
+        return self.policy.msg_kind in (ops.MSG_GATHER_RELU, ops.MSG_MEAN_ADD) and os.environ.get('NMARL_MSG_CARRY', '1') != '0'
+
     S_bits = None
 
     def _relu_bits(self, t):
-        """Slot t of the sign image of the saved LSTM inputs ([N,T,E,4] int32, ops.relu_bits_pack's layout): written by the
-        lock-step kernel that runs the input encoders, read by the update's encoder backward instead of S itself."""
-        if os.environ.get('NMARL_FC_BWD_PAIR', '1') == '0' or not getattr(self.policy, 'enc_writes_bits', False):
-            return None
+        """Slot t of the sign image of the saved LSTM inputs ([N,T,E,4] int32, ops.relu_bits_pack's layout): written by the lock-step kernel
+        that runs the input encoders (`lock_step_form().sign_image`), read by the update's encoder backward instead of S itself."""
         if self.S_bits is None:
             self.S_bits = torch.zeros(self.n_agent, self.n_step, self.E, 4, dtype=torch.int32, device=self.device)
-        p = self.policy
-        p._bits_steps = 1 if t == 0 else p._bits_steps + 1
+        self.policy._bits_steps = 1 if t == 0 else self.policy._bits_steps + 1
         return self.S_bits[:, t]
 
     def record(self, reward, done_post):
@@ -550,45 +584,6 @@ class IA2C:
     def reward_scale_std(self):
         """The running std of the discounted return the last update divided by (host read: synchronises); None with the key off."""
         return None if self.reward_scale == 'none' else float(self.rs_state[6])
-
-    def bootstrap(self, done, action_scratch, mode=ops.SAMPLE_PHILOX, u=None, seed=0, env_id_base=0,
-                  step=0, step_dev=None, done_is_zero=False, pre_encoded=False):
-        """R for the unfinished replicas (utils.py:192-196) from buf_x[T] / buf_fp[T]: one more policy
-        step (which advances states_fw -- quirk Q2) and the double-stepped value."""
-        assert self.t == self.n_step
-        p = self.policy
-        ob = None
-        if pre_encoded:
-            enc = self.encode_target(self.n_step)
-        elif self.save_acts and p.enc_in_kernel(self.E, self.compact_obs):
-            # (nothing of the bootstrap step is kept; a coupled net's encoders hand their output to the K loop THROUGH the x slot:
-            # a scratch one here, slab n_step of the saved inputs must stay zero)
-            enc, ob = (self.encode_target(self.n_step) if p.coupled else None), dict(x=self.buf_x[self.n_step], fp=self.fp)
-        elif self.save_acts and p.encodes_in_step(self.E, self.compact_obs):
-            enc, ob = self.encode_target(self.n_step), self.buf_x[self.n_step]     # the step kernel runs the encoder itself
-        else:
-            enc = p.encode(self.buf_x[self.n_step], self.fp)
-        if self.save_acts and p.pv_one_launch(self.E):     # from slot T of the sequences into the persistent state
-            T = self.n_step
-            p.step_policy_value(enc, self.H_all[:, T], self.C_all[:, T], done, self._pi_boot, action_scratch, self._v_boot,
-                                h_out=self.h_fw, c_out=self.c_fw, mode=mode, u=u, seed=seed, env_id_base=env_id_base,
-                                step=step, step_dev=step_dev, **(dict(ob=ob) if ob is not None else {}),
-                                **(dict(carry=self._msg_carry(T)) if p.coupled else {}))
-            return self._v_boot
-        if self.save_acts:
-            T = self.n_step
-            p.step_policy(enc, self.H_all[:, T], self.C_all[:, T], done, self.h_fw, self.c_fw, self._pi_boot, action_scratch,
-                          done_is_zero, mode=mode, u=u, seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev)
-            return p.step_value(enc, self.h_fw, self.c_fw, done, self._h2, self._c2, action_scratch, self._v_boot,
-                                done_is_zero)
-        if p.fused_pv:
-            p.step_policy_value(enc, self.h_fw, self.c_fw, done, self._pi_boot, action_scratch, self._v_boot, mode=mode, u=u,
-                                seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev)
-            return self._v_boot
-        p.step_policy(enc, self.h_fw, self.c_fw, done, self.h_fw, self.c_fw, self._pi_boot, action_scratch,
-                      done_is_zero, mode=mode, u=u, seed=seed, env_id_base=env_id_base, step=step, step_dev=step_dev)
-        return p.step_value(enc, self.h_fw, self.c_fw, done, self._h2, self._c2, action_scratch, self._v_boot,
-                            done_is_zero)
 
     def _policy_adv(self):
         """The advantage of the policy-gradient term [N,T,E]: Adv, or under the opt-in adv_norm its standardised copy."""
@@ -721,7 +716,7 @@ class IA2C:
         if self.reward_scale != 'none' and self._rs_pending:
             # the one-replica path (`record` per step kept the raw rewards): the same one call the batched path makes in load_rewards
             self._scale_rewards(self._rs_raw)
-        if self.save_acts and self.policy.pv_one_launch(self.E):
+        if self.save_acts and self.lock_step_form().launches == 1:
             # the critic's neighbour-action term of all T lock-steps in one launch (policies.py:59-77), then the values
             # in the [T,N,E] order the return scan reads
             with torch.no_grad():
@@ -744,11 +739,10 @@ class IA2C:
         FP = self.buf_fp[:T].permute(1, 0, 2, 3).reshape(self.n_agent, T * self.E, self.n_a)
         X = self.buf_x[:T]            # compact [T,E,N,n_feat] slab: the encoders' kernels gather the neighbours themselves
         if self.save_acts:
-            kw = {}
-            if self.S_bits is not None and self.policy._bits_steps == T:      # every lock-step of this batch went through the kernel that writes them
-                kw['S_bits'] = self.S_bits
+            # (the sign image: only if every lock-step of this batch went through the kernel that writes it)
+            bits = dict(S_bits=self.S_bits) if (self.S_bits is not None and self.policy._bits_steps == T) else {}
             Hs = self.policy.unroll_saved(X, FP, self.S_buf, self.G_buf, self.H_all, self.C_all,
-                                          self.buf_done_pre, masked_steps=self.masked_steps, S_ext=self.S_ext, **kw)
+                                          self.buf_done_pre, masked_steps=self.masked_steps, S_ext=self.S_ext, **bits)
         else:
             Hs = self.policy.unroll(X, FP, self.buf_done_pre, self.h_bw, self.c_bw, masked_steps=self.masked_steps)
         if self.ppo_epochs > 1:          # opt-in: the behaviour policy's log-probabilities, from the hidden states this epoch's loss reads
@@ -904,9 +898,7 @@ class IA2C:
     def update_end(self):
         """Host only: the batch is consumed."""
         self.t = 0
-        self.policy._enc_was_saved = False       # the saved encoder outputs belonged to this batch (the next rollout sets it again)
-        self.policy._bits_steps = 0
-        self.policy._mm_was_saved = False
+        self.policy.set_rollout_saved((False, False, 0))     # what the rollout saved belonged to this batch (the next one sets it again)
 
     # ------------------------------------------------------------------ reference API (E = 1)
     def _obs_to_slab(self, obs):

@@ -21,6 +21,7 @@ and the RMSProp slot use the same layout, so clip + RMSProp is one fused kernel
 and the data-parallel exchange is one RCCL all-reduce of the gradient buffer.
 """
 import os
+import types
 import warnings
 
 import numpy as np
@@ -471,7 +472,19 @@ class BatchedPolicy:
         """The one-launch step of this net also runs the observation encoder (no separate encoder launch per lock-step)."""
         return False
 
-    _bits_steps = 0          # lock-steps of the running batch whose encoder sign image the rollout wrote (models._relu_bits)
+    # -- what the running batch's rollout saved for its update: set lock-step by lock-step, cleared by models.update_end
+    _enc_was_saved = False   # CommNet's encoder outputs (the ENC slots)
+    _mm_was_saved = False    # CommNet's mean_nbr(h) rows, by every policy step
+    _bits_steps = 0          # lock-steps whose encoder sign image was written (models._relu_bits)
+    _extra = _extra_full = types.MappingProxyType({})      # a coupled net's further saved terms {name: [N,T,E,w]} / the buffers behind them
+    save_next = save_pad = ()      # their keys with a slot t + 1 filled by lock-step t / with one zero slab more
+
+    def rollout_saved(self):
+        """The three flags: a replayed graph runs no Python, a capture runs it without a batch -- both put them back (`set_rollout_saved`)."""
+        return self._enc_was_saved, self._mm_was_saved, self._bits_steps
+
+    def set_rollout_saved(self, flags):
+        self._enc_was_saved, self._mm_was_saved, self._bits_steps = flags
 
     def invalidate_cached_msg(self):
         """(lstm_dial keeps message vectors of the last policy step: see DIALMultiAgentPolicy)"""
@@ -497,19 +510,20 @@ class BatchedPolicy:
         carry (coupled nets, one launch): dict(carry_in, carry_out[, mean_next]) -- the re-step's message term is the next lock-step's
         policy-step message term (the neighbours' un-masked new h, Q3); see include/nmarl.h nmarl_msg_t."""
         with torch.no_grad():
+            # ob, one shape from here on: dict(x[, fp][, env][, bits][, genv]) or None -- `fp` tells both encoders from the observation one
+            ob = ob if (ob is None or isinstance(ob, dict)) else dict(x=ob)
             if self.coupled:
                 z1, z2, xs = self._recur_addends(enc, h, save=save, fuse_msg=True)
-                xs[4]['sync'] = self._sync_words(h.shape[1])
-                if carry:
-                    xs[4].update(carry)
-                if isinstance(ob, dict) and 'genv' in ob:      # lstm_ic3 on the grid: observation encoder AND env step inside the launch
-                    xs[4]['ob'], xs[4]['genv'] = self._ob_spec(ob['x']), ob['genv']
-                elif isinstance(ob, dict):       # lstm_comm: both input encoders (and the env step) inside the launch, see `enc_in_kernel`
-                    xs[4]['enc_spec'] = self._enc_spec(ob['x'], ob['fp'], None, ob.get('env'), ob.get('bits'))
+                # the one-launch step's part of the message description: the hand-off words, the carried term, the encoders inside the launch
+                # -- lstm_comm: both (and the CACC env step), `enc_in_kernel`; lstm_ic3: the observation one (and the grid env step), `encodes_in_step`
+                more = dict(carry or {}, sync=self._sync_words(h.shape[1]))
+                if ob is not None and ob.get('fp') is not None:
+                    more['enc_spec'] = self._enc_spec(ob['x'], ob['fp'], None, ob.get('env'), ob.get('bits'))
                 elif ob is not None:
-                    xs[4]['ob'] = self._ob_spec(ob)
+                    more.update(ob=self._ob_spec(ob['x']), genv=ob.get('genv'))
+                xs[4].update(more)
             elif ob is not None:
-                # the encoders run inside the launch: ob = dict(x = compact observation [E,N,5], fp = previous policies [N,E,4]);
+                # the encoders run inside the launch: x = compact observation [E,N,5], fp = previous policies [N,E,4];
                 # `enc` = where their output (the LSTM input) is kept for the update, or None
                 z1, z2, xs = None, None, (self._enc_spec(ob['x'], ob['fp'], enc, ob.get('env'), ob.get('bits')), self.params[self.k_wx],
                                           self._step_img)
@@ -561,12 +575,12 @@ class BatchedPolicy:
         kind, wx, w_msg, b_msg, mfc_w, mfc_b = self._seq_args()
         # (S_bits: the sign image of the encoders' output, written by the lock-step kernel that ran them -- lstm_comm's one-launch form)
         enc = self._enc_saved(Xv, FP, S) if S_bits is None else self._enc_saved(Xv, FP, S, bits=S_bits.view(self.N, T * E, 4))
-        extra = dict(getattr(self, '_extra', {}))
-        if kind == 'dial' and 'A2' in getattr(self, '_extra_full', {}) and extra.get('A2') is not None:
+        extra = dict(self._extra)
+        if kind == 'dial' and 'A2' in self._extra_full and extra.get('A2') is not None:
             extra['A2'] = self._extra_full['A2']          # the (T + 1)-slab buffer itself: the weight gradient reads it in place
         if kind == 'ic3':
             # the rollout's mean_nbr(h_{t-1}) rows ((T + 1)-slab buffer, last slab zero) if every policy step of this batch kept them
-            mm = getattr(self, '_extra_full', {}).get('MM') if getattr(self, '_mm_was_saved', False) else None
+            mm = self._extra_full.get('MM') if self._mm_was_saved else None
             extra['A1'] = mm if (mm is not None and mm.shape[1] == T + 1) else None
         Hs = sequence.coupled_sequence_saved(kind, self.nbr_idx, masked_steps, enc.view(self.N, T, E, enc.shape[-1]), done,
                                              self.params[self.k_wx], self.params[self.k_wh], self.params[self.k_b],
@@ -997,15 +1011,12 @@ class IC3MultiAgentPolicy(BatchedPolicy):
         return {'ENC': self.n_h, 'MM': self.n_h}
 
     save_pad = ('MM',)
-    _mm_was_saved = False
 
     def _enc_saved(self, xv, fp, S):
-        enc = getattr(self, '_extra', {}).get('ENC')
+        enc = self._extra.get('ENC')
         if enc is None or not self._enc_was_saved:
             return self._enc(xv, fp)         # recomputed (one streaming pass)
         return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b')], ops.BIAS_TANH, saved=enc.view(self.N, -1, self.n_h))
-
-    _enc_was_saved = False
 
     def _enc_infer(self, xv, fp, out=None):
         return self._fc_ob_infer(xv, 'w_ob', 'w_ob_b', ops.BIAS_TANH, out=out)

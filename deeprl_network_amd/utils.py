@@ -392,33 +392,27 @@ class BatchedTrainer:
 
     # -- the n_step rollout (graph body): every kernel reads / writes rollout-buffer slots directly
     def _rollout(self):
-        env, model = self.env, self.model
-        T = self.n_step
+        env, model, T = self.env, self.model, self.n_step
         model.t = 0
         if self.handoff_guard:                # what the rollout mutates and a re-run must start from: ONE launch, and none of it
             ops.copy_multi(zip(self._shadow, self._shadow_tensors()), skip_if=self._status[:1])    # once the status word is raised
         # Philox step = batch base (device counter, advanced once per batch) + slot offset baked into the graph
         fused = self.fused_encode
+        draw = dict(mode=ops.SAMPLE_PHILOX, seed=env.seed, env_id_base=env.env_id_base, step_dev=self.step_dev)
         for t in range(T):
             outs = dict(obs_out=model.buf_x[t + 1], reward_out=self.buf_rraw[t], done_out=model.buf_done_post[t], greward_out=self.buf_g[t])
-            if self.env_in_kernel:            # the whole lock-step -- encoders, policy step, draw, value re-step, env step -- in ONE launch
-                model.act(self.done_pre if t == 0 else self.zero_done, mode=ops.SAMPLE_PHILOX, seed=env.seed,
-                          env_id_base=env.env_id_base, step=t, step_dev=self.step_dev, done_is_zero=(t > 0),
-                          env_step=env.inkernel_step(auto_reset=(t == T - 1), **outs))
-                model.t = t + 1
-                continue
-            action = model.act(self.done_pre if t == 0 else self.zero_done, mode=ops.SAMPLE_PHILOX, seed=env.seed,
-                               env_id_base=env.env_id_base, step=t, step_dev=self.step_dev, done_is_zero=(t > 0),
-                               pre_encoded=fused and t > 0)
-            # fused: the env kernel also runs lock-step t + 1's input encoders on the observation it just produced and on the
-            # policies the step above wrote (the next fingerprints) -- one launch instead of two per lock-step
-            enc = model.policy.fused_env_encode(model.buf_fp[t + 1], model.encode_target(t + 1)) if fused else None
-            env.step(action, auto_reset=(t == T - 1), obs_out=model.buf_x[t + 1], reward_out=self.buf_rraw[t],
-                     done_out=model.buf_done_post[t], greward_out=self.buf_g[t], **({'encode': enc} if fused else {}))
+            # env_in_kernel: the whole lock-step -- encoders, policy step, draw, value re-step, env step -- in ONE launch
+            inside = env.inkernel_step(auto_reset=(t == T - 1), **outs) if self.env_in_kernel else None
+            action = model.act(self.done_pre if t == 0 else self.zero_done, step=t, done_is_zero=(t > 0),
+                               pre_encoded=fused and t > 0 and inside is None, env_step=inside, **draw)
+            if inside is None:
+                # fused: the env kernel also runs lock-step t + 1's input encoders on the observation it just produced and on the
+                # policies the step above wrote (the next fingerprints) -- one launch instead of two per lock-step
+                enc = {'encode': model.policy.fused_env_encode(model.buf_fp[t + 1], model.encode_target(t + 1))} if fused else {}
+                env.step(action, auto_reset=(t == T - 1), **outs, **enc)
             model.t = t + 1
         # bootstrap value for unfinished replicas (utils.py:192-196); finished ones get R = 0
-        v = model.bootstrap(self.zero_done, self.action_boot, mode=ops.SAMPLE_PHILOX, seed=env.seed,
-                            env_id_base=env.env_id_base, step=T, step_dev=self.step_dev, done_is_zero=True, pre_encoded=fused)
+        v = model.bootstrap(self.zero_done, self.action_boot, step=T, done_is_zero=True, pre_encoded=fused, **draw)
         self.step_dev.add_(T + 1)
         torch.mul(v, (1.0 - self.last_done.to(torch.float32)).view(1, -1), out=self.R_end)     # (out=: no temporary + memcpy node)
 
@@ -442,12 +436,11 @@ class BatchedTrainer:
             self._restore(snap)
             # host-side per-batch state the captured rollout set (a replay runs no Python): the update's "the rollout saved the
             # encoder outputs" flag is cleared by every update and must be raised again after every replay
-            self._graph_flags = {k: getattr(self.model.policy, k, False) for k in ('_enc_was_saved', '_mm_was_saved', '_bits_steps')}
+            self._graph_flags = self.model.policy.rollout_saved()
         self.model.t = 0
         self.graph.replay()
         self.model.t = self.n_step
-        for k, v in self._graph_flags.items():
-            setattr(self.model.policy, k, v)
+        self.model.policy.set_rollout_saved(self._graph_flags)
 
     def _new_graph(self):
         return torch.cuda.CUDAGraph(keep_graph=True) if self.keep_graphs else torch.cuda.CUDAGraph()
@@ -456,24 +449,23 @@ class BatchedTrainer:
         """How many launches a lock-step is (decided at construction and again whenever the in-launch hand-off kernels are switched
         off / on: a coupled net's one-launch form exists only with them)."""
         env, model = self.env, self.model
-        if env.device.type == 'cuda' and self.saved_acts:
+        on_device = env.device.type == 'cuda'
+        if on_device and self.saved_acts:
             model.policy.refresh_wimage()     # (a coupled net's one-launch forms exist once its message image does)
+        # the model's own description of its lock-step; here only what belongs to the env is added (saved activations, compact observation, device)
+        inside = model.lock_step_form().encoders if (self.saved_acts and self.compact_obs and on_device) else 'none'
         # CACC: the env kernel runs the next lock-step's input encoders behind its step (csrc/cacc.hip cacc_step_encode_kernel)
         # ... unless the lock-step kernel runs the encoders itself (csrc/lstm_mfma.hip ENC: IA2C-FP, NeurComm), then the env step stays alone
-        self.enc_in_kernel = self.saved_acts and self.compact_obs and env.device.type == 'cuda' and \
-            model.policy.enc_in_kernel(env.E, True)
+        self.enc_in_kernel = inside == 'both'
         # ... and the env step as well, behind the action draw of the same launch: ONE launch per lock-step (ENV block of the kernel)
         self.env_in_kernel = self.enc_in_kernel and hasattr(env, 'inkernel_step') and env.n_agent == 8 and ops.step_env_supported() and \
             model.policy.env_step_in_kernel
         # the synthetic grid under CommNet: the env step is a ROLE of the one-launch lock-step (its observation encoder is inside
         # already), run by the compute units the 25 x ceil(E / 128) LSTM blocks leave idle (csrc/lstm_mfma.hip GENV)
-        if not self.env_in_kernel and self.saved_acts and self.compact_obs and env.device.type == 'cuda' and \
-                getattr(env, 'inkernel_step_supported', None) is not None and model.policy.coupled and \
-                getattr(model.policy, 'encodes_in_step', None) is not None and 'ENC' in model.policy._extra and \
-                os.environ.get('NMARL_GRID_ENV_IN_KERNEL', '1') != '0':
-            self.env_in_kernel = bool(model.policy.encodes_in_step(env.E, True) and env.inkernel_step_supported())
+        if inside == 'ob' and hasattr(env, 'inkernel_step_supported') and os.environ.get('NMARL_GRID_ENV_IN_KERNEL', '1') != '0':
+            self.env_in_kernel = bool(env.inkernel_step_supported())
         self.fused_encode = self._want_fused_encode and self.saved_acts and self.compact_obs and not self.enc_in_kernel and \
-            getattr(env, 'supports_fused_encode', False) and env.device.type == 'cuda' and \
+            getattr(env, 'supports_fused_encode', False) and on_device and \
             model.policy.fused_env_encode(model.buf_fp[1], model.encode_target(1)) is not None
 
     def _shadow_tensors(self):
@@ -499,13 +491,14 @@ class BatchedTrainer:
     def _restore(self, snap):
         for t, s in zip(self._state_tensors(), snap):
             t.copy_(s)
+        self.model.invalidate_carried()
 
     def _epilogue(self):
         """Episode statistics, then the hand-over to the next batch in one call: finished replicas start a new episode (the
         env already auto-reset them) with zero recurrent state and uniform fingerprints -- what the reference does at its
         next `env.reset(); model.reset()` --, states_bw <- states_fw, slot T of the rollout buffers -> slot 0."""
         m, T = self.model, self.n_step
-        m.policy.invalidate_cached_msg()       # (the epilogue kernel zeroes finished replicas' h through raw pointers)
+        m.invalidate_carried()                 # (the epilogue kernel zeroes finished replicas' h through raw pointers)
         ops.batch_epilogue(self.buf_g, self.last_done, self.ep_sum, self.ep_sq, self.ep_len, self.fin, self.env.T,
                            m.h_fw, m.c_fw, m.h_bw, m.c_bw, m.buf_fp[T], m.buf_fp[0], m.fp_uniform, m.buf_x[T], m.buf_x[0],
                            self.done_pre, skip_if=self._status[:1] if self.handoff_guard else None)
@@ -535,7 +528,7 @@ class BatchedTrainer:
                 tunable.tuning_enable(False)          # a timing loop inside a capture would invalidate it (every shape is tuned by now)
         except Exception:
             tun = None
-        host = (m.t, m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps)
+        host = (m.t, m.policy.rollout_saved())
         ops.keepalive_begin(self._keepalive)
         try:
             torch.cuda.synchronize()
@@ -570,7 +563,8 @@ class BatchedTrainer:
                 self._upd['chain'] = chain
         finally:
             ops.keepalive_end()
-            m.t, m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps = host
+            m.t = host[0]
+            m.policy.set_rollout_saved(host[1])
             if tun is not None:
                 tun.tuning_enable(True)
 
@@ -681,7 +675,7 @@ class BatchedTrainer:
             self.env.clear_inkernel_words()
         for s_, t_ in zip(self._shadow, self._shadow_tensors()):
             t_.copy_(s_)
-        m.policy.invalidate_cached_msg()
+        m.invalidate_carried()
         m.lr_scheduler.rewind(self.n_step * batches)       # the refused updates advanced the schedule
         self.n_batches -= batches
         if self.recorder is not None:

@@ -262,10 +262,9 @@ def main():
     if '--phases' in sys.argv:
         m = model
         m.t = tr.n_step
-        host = (m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps)
-        flags = getattr(tr, '_graph_flags', {})
-        for k, v in flags.items():
-            setattr(m.policy, k, v)
+        host = m.policy.rollout_saved()
+        flags = getattr(tr, '_graph_flags', host)          # what a replayed rollout leaves (BatchedTrainer.rollout)
+        m.policy.set_rollout_saved(flags)
         phases = [('load_rewards', lambda: m.load_rewards(tr.buf_rraw)),
                   ('update_grads', lambda: m.update_grads(tr.R_end)),
                   ('update_apply', lambda: m.update_apply(0.0, rotate=False, lr_dev=tr.lr_dev)),
@@ -278,14 +277,12 @@ def main():
             m.load_rewards(tr.buf_rraw)
             m.update_grads(tr.R_end)
         torch.cuda.synchronize()
-        for k, v in flags.items():
-            setattr(m.policy, k, v)
+        m.policy.set_rollout_saved(flags)
         keep = []
         ops.keepalive_begin(keep)
         try:
             for name, fn in phases:
-                for k, v in flags.items():
-                    setattr(m.policy, k, v)
+                m.policy.set_rollout_saved(flags)
                 m.t = tr.n_step if name != 'rollout' else 0
                 g, where = trace_non_kernel(fn)
                 print(' phase %-13s\n%s' % (name, describe(g, names)))
@@ -294,7 +291,7 @@ def main():
                 keep.append(g)
         finally:
             ops.keepalive_end()
-        m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps = host
+        m.policy.set_rollout_saved(host)
 
 
 if __name__ == '__main__':

@@ -1,4 +1,7 @@
-"""Is the batch loop host-bound?  Host enqueue time vs device time per batch (headline config)."""
+"""Is the batch loop host-bound?  Host enqueue time vs device time per batch (headline config).
+    python tools/host_time.py [config.ini] [--eager]
+--eager: the rollout's own host code -- a trainer without graphs, the time `_rollout()` takes to issue one batch's launches on an idle
+device (median and minimum of 10 batches), per batch and per lock-step."""
 import os
 import sys
 import time
@@ -16,7 +19,9 @@ from deeprl_network_amd.utils import BatchedTrainer, Counter  # noqa: E402
 
 
 def main():
-    cfg = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini')
+    args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    eager = '--eager' in sys.argv
+    cfg = args[0] if args else os.path.join(ROOT, 'config', 'config_ia2c_fp_catchup.ini')
     cp = configparser.ConfigParser()
     cp.read(cfg)
     E = cp.getint('TRAIN_CONFIG', 'num_envs', fallback=4096)
@@ -24,11 +29,25 @@ def main():
     np.random.seed(env.seed)
     model = AGENTS[env.agent](env.n_s_ls, env.n_a_ls, env.neighbor_mask, env.distance_mask, env.coop_gamma, 10 ** 6,
                               cp['MODEL_CONFIG'], seed=env.seed, num_envs=E, device='cuda')
-    tr = BatchedTrainer(env, model, Counter(10 ** 9, 10 ** 9, 10 ** 9), use_graph=True)
+    tr = BatchedTrainer(env, model, Counter(10 ** 9, 10 ** 9, 10 ** 9), use_graph=not eager)
     for _ in range(3):
         tr.run_batch()
     torch.cuda.synchronize()
     K = 10
+    if eager:
+        ts = []
+        for _ in range(K):
+            a = time.perf_counter()
+            tr._rollout()
+            ts.append(time.perf_counter() - a)
+            if not tr._update():
+                tr._epilogue()
+            tr.n_batches += 1
+            torch.cuda.synchronize()
+        ts.sort()
+        print('eager rollout host time %s E=%d n_step=%d: median %.3f ms, min %.3f ms per batch (%.1f us per lock-step)'
+              % (os.path.basename(cfg), E, tr.n_step, 1e3 * ts[K // 2], 1e3 * ts[0], 1e6 * ts[K // 2] / (tr.n_step + 1)))
+        return
     t0 = time.perf_counter()
     host = []
     for _ in range(K):

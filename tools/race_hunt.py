@@ -37,7 +37,7 @@ def rollout_outputs():
     p = m.policy
     out = dict(act=m.buf_act, v=m.buf_v, vn=m.buf_vn, H=m.H_all, C=m.C_all, G=m.G_buf, S=m.S_buf, fp=m.buf_fp, x=m.buf_x, R_end=tr.R_end,
                rraw=tr.buf_rraw, done=m.buf_done_post, h_fw=m.h_fw, c_fw=m.c_fw)
-    for k, v in getattr(p, '_extra', {}).items():
+    for k, v in p._extra.items():
         out['extra_' + k] = v
     return out
 
@@ -56,12 +56,12 @@ for b in range(B):
         print('batch %d: ROLLOUT differs between two replays from the same state in %s' % (b, diff), flush=True)
     # the update's gradient twice from the same buffers (eager launches of the kernels the update graph replays)
     vn0 = m.buf_vn.clone()
-    host = (m.t, getattr(m.policy, '_enc_was_saved', False), getattr(m.policy, '_mm_was_saved', False), m.policy._bits_steps)
+    host = (m.t, m.policy.rollout_saved())
     g = []
     for k in range(2):
         m.buf_vn.copy_(vn0)
         m.t = tr.n_step
-        m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps = host[1], host[2], host[3]
+        m.policy.set_rollout_saved(host[1])
         m.load_rewards(tr.buf_rraw)
         m.update_grads(tr.R_end)
         g.append(m.policy.params.grad.clone())
@@ -71,7 +71,8 @@ for b in range(B):
         d = (g[0] - g[1]).abs()
         print('batch %d: GRADIENT differs between two backward passes over the same buffers: %d entries, max |d| %.3g (max |g| %.3g)'
               % (b, int((g[0] != g[1]).sum()), float(d.max()), float(g[0].abs().max())), flush=True)
-    m.t, m.policy._enc_was_saved, m.policy._mm_was_saved, m.policy._bits_steps = host
+    m.t = host[0]
+    m.policy.set_rollout_saved(host[1])
     tr._restore(snap)
     tr.run_batch()
 print('%s %s E=%d: %d batches, rollout differed %d times, gradient differed %d times; hand-off fallbacks %d' % (
