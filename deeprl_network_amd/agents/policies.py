@@ -556,13 +556,12 @@ class BatchedPolicy:
         S_ext: the [N,T+1,E,KX] buffer S is the first T slabs of (last slab zero), see ops.seq_input_in_place."""
         T, E = done.shape
         Xv = X.reshape(T * E, self.N, X.shape[-1]).transpose(0, 1)          # gathered [.., n_obs] or compact [.., n_feat] slab
+        # S_bits: the sign image of the encoders' output, written by the lock-step kernel that ran them (the two-layer nets): with it
+        # the saved output is not re-read
+        enc = self._enc(Xv, FP, saved=S, bits=None if S_bits is None else S_bits.view(self.N, T * E, 4))
         if self.coupled:
-            return self._unroll_saved_coupled(Xv, FP, S, G, Hall, Call, done, masked_steps, S_ext, S_bits)
-        if S_bits is not None:           # the sign image of S the lock-step kernel's encoders wrote (FPPolicy): S is not re-read
-            s = self._enc(Xv, FP, saved=S.view(self.N, T * E, S.shape[-1]), bits=S_bits.view(self.N, T * E, 4))
-        else:
-            s = self._enc(Xv, FP, saved=S.view(self.N, T * E, S.shape[-1]))
-        Hs = ops.lstm_sequence_saved(s.view(self.N, T, E, s.shape[-1]), self.params[self.k_wx], self.params[self.k_wh],
+            return self._unroll_saved_coupled(enc, S, G, Hall, Call, done, masked_steps, S_ext)
+        Hs = ops.lstm_sequence_saved(enc.view(self.N, T, E, enc.shape[-1]), self.params[self.k_wx], self.params[self.k_wh],
                                      self.params[self.k_b], G, Hall, Call, done, masked_steps, s_ext=S_ext)
         return Hs.reshape(self.N, T * E, self.n_h)
 
@@ -570,11 +569,10 @@ class BatchedPolicy:
         """Extra per-step tensors a coupled net saves besides S / G / Hall / Call: {name: width}."""
         return {}
 
-    def _unroll_saved_coupled(self, Xv, FP, S, G, Hall, Call, done, masked_steps, S_ext=None, S_bits=None):
+    def _unroll_saved_coupled(self, enc, S, G, Hall, Call, done, masked_steps, S_ext=None):
         T, E = done.shape
-        kind, wx, w_msg, b_msg, mfc_w, mfc_b = self._seq_args()
-        # (S_bits: the sign image of the encoders' output, written by the lock-step kernel that ran them -- lstm_comm's one-launch form)
-        enc = self._enc_saved(Xv, FP, S) if S_bits is None else self._enc_saved(Xv, FP, S, bits=S_bits.view(self.N, T * E, 4))
+        # (`_seq_args`' wx is the part of Wx `unroll`'s recurrence applies per step; the saved LSTM inputs S are whole: all of Wx below)
+        kind, _, w_msg, b_msg, mfc_w, mfc_b = self._seq_args()
         extra = dict(self._extra)
         if kind == 'dial' and 'A2' in self._extra_full and extra.get('A2') is not None:
             extra['A2'] = self._extra_full['A2']          # the (T + 1)-slab buffer itself: the weight gradient reads it in place
@@ -601,43 +599,122 @@ class BatchedPolicy:
                 self.value(h_out, ops.nbr_onehot(action, self.nbr_idx, self.n_a), out=v_out)
         return v_out
 
-    def fused_env_encode(self, fp_next, out):
-        """Arguments for the env kernel to run THIS policy's input encoders behind its step (envs/cacc_env.py `encode`), or
-        None if the encoders do not have that shape: relu layers of 64 outputs over the compact CACC observation
-        ([own | 2 neighbours] x 5 features) and, optionally, the 2 neighbours' 4-wide fingerprints."""
-        return None
+    # -- the input encoders: declared once per class, every form derived from the declaration ("The input encoders")
+    enc_layers = None           # ((w_key, b_key, own_only), (w_key, b_key) or None): the observation layer over [own | neighbours] (own_only:
+    #                             over the agent's own features) and the fingerprint layer over the neighbours' previous policies
+    enc_act = ops.BIAS_RELU     # the activation both layers share
+    enc_is_input = False        # the layers' output IS the LSTM input (NeurComm: its first columns): the env kernel (`fused_env_encode`) and
+    #                             the lock-step kernel's pre-phase (`_enc_spec`) may write it in place of the fc kernels
 
-    def _fused_spec(self, ob, fp_keys, fp_next, out):
-        """ob = (weight key, bias key) of the observation layer, fp_keys likewise for the fingerprint layer or None."""
-        p = self.params
-        if self.hetero or self.n_feat != 5 or self.m_max != 2 or self.n_a != 4 or p[ob[0]].shape[1:] != (15, 64):
-            return None
-        d = dict(w_ob=p[ob[0]], b_ob=p[ob[1]], nbr_idx=self.nbr_idx, out=out, act=ops.BIAS_RELU)
-        if fp_keys is not None:
-            if p[fp_keys[0]].shape[1:] != (8, 64):
-                return None
-            d.update(w_fp=p[fp_keys[0]], b_fp=p[fp_keys[1]], fp=fp_next)
-        return d
+    k_ob = property(lambda self: self.enc_layers[0][0], doc="the observation encoder's weight")
+    enc_writes_bits = property(lambda self: self.enc_layers[1] is not None,
+                               doc='the in-kernel encoders write the 16-byte sign image of a row: it belongs to the two-layer encodings')
 
-    def _enc_one_launch(self, xv, width):
-        """Observation and fingerprint encoders fit the multi-layer fc kernel (inputs <= 64 wide, 64 outputs)."""
-        return width == ops.FC_J and self.n_obs <= ops.FC_MAX_F and self.n_na <= ops.FC_MAX_F
+    @property
+    def _enc_width(self):
+        """Outputs of an encoder layer -- the declared weight's own shape (n_fc for IA2C / IA2C-FP, n_h for the others)."""
+        return self.params[self.k_ob].shape[2]
 
     def _compact(self, xv):
         """xv holds each agent's OWN features only ([N,rows,n_feat], the env's compact observation): the observation
         encoder gathers [own | neighbours] through `nbr_self` inside the fc kernel."""
         return xv.shape[2] == self.n_feat and self.n_obs != self.n_feat
 
-    def _ob_part(self, xv, w_key, b_key):
+    def _enc_parts(self, xv, fp):
+        """The declared layers on (xv, fp) as the `parts` of ops.fc_concat / ops.fc_fwd_multi: [(x, w, b, nbr table or None), ...]
+        (policies.py:145, 177; agents/utils.py:186-197, 395-399) -- the observation layer on the gathered slab, on the compact
+        observation (gathered through `nbr_self` inside the kernel) or on the own features alone; the fingerprints gathered in the kernel."""
         p = self.params
-        return (xv, p[w_key], p[b_key], self.nbr_self if self._compact(xv) else None)
+        (w, b, own_only), fpl = self.enc_layers
+        if own_only:
+            parts = [(xv[:, :, :self.n_feat], p[w], p[b], None)]          # (compact observation: all of xv)
+        else:
+            parts = [(xv, p[w], p[b], self.nbr_self if self._compact(xv) else None)]
+        if fpl is not None:
+            parts.append((fp, p[fpl[0]], p[fpl[1]], self.nbr_idx))
+        return parts
 
-    def _fc_ob_infer(self, xv, w_key, b_key, act, out=None):
-        """The observation encoder layer act([x_i, x_nbr] W + b) (policies.py:145, 177; agents/utils.py:186-197, 395-399)
-        on the gathered slab or on the compact observation."""
-        if self._compact(xv):
-            return ops.fc_fwd_multi([self._ob_part(xv, w_key, b_key)], act, out=out)
-        return self._fc_infer(xv, w_key, b_key, act, out=out)
+    def _enc(self, xv, fp, saved=None, bits=None):
+        """The differentiable form: the h-independent part of the recurrence's input for all rows of a batch -- the layers, then the
+        class's `_enc_post`.  saved: the LSTM inputs S the rollout kept -- only the layers' backward is set up, over the output
+        `_enc_saved_in` finds there (None: recomputed, one streaming pass), and nothing comes after the layers: S and the saved
+        sequences already hold it.  bits: the sign image of that output."""
+        if saved is None:
+            return self._enc_post(ops.fc_concat(self._enc_parts(xv, fp), self.enc_act), fp, False)
+        return ops.fc_concat(self._enc_parts(xv, fp), self.enc_act, saved=self._enc_saved_in(saved), bits=bits)
+
+    def _enc_saved_in(self, S):
+        """Where the layers' output of this batch lives in what the rollout saved (S [N,T,E,KX]): the LSTM inputs themselves."""
+        return S.view(self.N, -1, S.shape[-1])
+
+    def _enc_post(self, s, fp, infer, slot=None):
+        """What a class adds after the layers.  infer: the rollout (no autograd; `slot`: what `_enc_slot` named as the result)."""
+        return s
+
+    def _enc_slot(self, xv, out):
+        """(the rollout form's result in the x-side mode, where the layers write) for `encode(out=)`; None: fresh tensors."""
+        return out, out
+
+    def _enc_one_launch(self, xv, width):
+        """Observation and fingerprint encoders fit the multi-layer fc kernel (inputs <= 64 wide, 64 outputs)."""
+        return width == ops.FC_J and self.n_obs <= ops.FC_MAX_F and self.n_na <= ops.FC_MAX_F
+
+    def _enc_infer(self, xv, fp, out=None):
+        """The rollout form (no autograd): both layers by ONE kernel where they fit it (the fingerprint gather folded into the
+        second), else a launch per layer into its column block of the concatenation; then `_enc_post`."""
+        parts = self._enc_parts(xv, fp)
+        slot, s = self._enc_slot(xv, out)
+        if len(parts) == 1:
+            s = self._fc_part_infer(parts[0], self.enc_act, out=s)
+        elif self._enc_one_launch(xv, self._enc_width):
+            s = ops.fc_fwd_multi(parts, self.enc_act, out=s)
+        else:
+            W = self._enc_width
+            if s is None:
+                s = torch.empty(self.N, xv.shape[1], W * len(parts), dtype=F32, device=xv.device)
+            for k, part in enumerate(parts):
+                self._fc_part_infer(part, self.enc_act, out=s[:, :, k * W:(k + 1) * W])
+        return self._enc_post(s, fp, True, slot)
+
+    def _fc_part_infer(self, part, act, out=None):
+        """One layer of a `parts` list, act(x W + b) with the bias / activation fused in one pass (no autograd); `out` may be a
+        column block of a wider buffer, which concatenates partial encodings without a copy."""
+        x, w, b, idx = part
+        if idx is self.nbr_self:                              # the compact observation: gathered inside the kernel
+            return ops.fc_fwd_multi([part], act, out=out)
+        if idx is not None:
+            x = ops.nbr_gather(x, idx)
+        if ops.fc_supported(x, w):
+            return ops.fc_fwd(x, w, b, act, out=out)          # small-K layer: one streaming kernel (csrc/fc.hip)
+        return ops.bias_act_(torch.bmm(x, w), b, act, out=out)
+
+    def _fc_infer(self, x, w_key, b_key, act, out=None):
+        return self._fc_part_infer((x, self.params[w_key], self.params[b_key], None), act, out=out)
+
+    def fused_env_encode(self, fp_next, out):
+        """Arguments for the env kernel to run THIS policy's input encoders behind its step (envs/cacc_env.py `encode`), or
+        None if the encoders do not have that shape: relu layers of 64 outputs over the compact CACC observation
+        ([own | 2 neighbours] x 5 features) and, optionally, the 2 neighbours' 4-wide fingerprints."""
+        p = self.params
+        (w, b, _), fpl = self.enc_layers
+        if not (self.enc_is_input and self.xside) or self.hetero or self.n_feat != 5 or self.m_max != 2 or self.n_a != 4 or \
+                p[w].shape[1:] != (15, 64):
+            return None
+        d = dict(w_ob=p[w], b_ob=p[b], nbr_idx=self.nbr_idx, out=out, act=self.enc_act)
+        if fpl is not None:
+            if p[fpl[0]].shape[1:] != (8, 64):
+                return None
+            d.update(w_fp=p[fpl[0]], b_fp=p[fpl[1]], fp=fp_next)
+        return d
+
+    def _enc_spec(self, x, fp, out, env=None, bits=None):
+        """The layers for the lock-step kernel's pre-phase (`enc_in_kernel`; ops.step_enc_spec).  self.nbrs: the SLAB's slot order
+        (ascending), which the rows of both weights follow whatever order the env concatenates in (`_L_slots`, `_L_fp_obs`)."""
+        p = self.params
+        (w, b, _), fpl = self.enc_layers
+        if fpl is None:                                       # (the sign image belongs to the two-layer encodings)
+            return ops.step_enc_spec(x, fp, p[w], p[b], None, None, self.nbrs, out=out, env=env, bits=None)
+        return ops.step_enc_spec(x, fp, p[w], p[b], p[fpl[0]], p[fpl[1]], self.nbrs, out=out, env=env, bits=bits)
 
     def expand_obs(self, X):
         """Compact observations [..., N, n_feat] -> the gathered slab [..., N, n_obs] ([own | neighbours ascending],
@@ -645,14 +722,6 @@ class BatchedPolicy:
         idx = self.nbr_self.long()
         g = X[..., idx.clamp(min=0), :] * (idx >= 0).to(X.dtype).unsqueeze(-1)       # [..., N, 1+m, n_feat]
         return g.reshape(*X.shape[:-1], self.n_obs)
-
-    def _fc_infer(self, x, w_key, b_key, act, out=None):
-        """act(x @ W + b) with the bias/activation fused in one pass (no autograd); `out` may be a column
-        block of a wider buffer, which concatenates partial encodings without a copy."""
-        w, b = self.params[w_key], self.params[b_key]
-        if ops.fc_supported(x, w):
-            return ops.fc_fwd(x, w, b, act, out=out)          # small-K layer: one streaming kernel (csrc/fc.hip)
-        return ops.bias_act_(torch.bmm(x, w), b, act, out=out)
 
     def _recur_addends(self, enc, h, second=False, save=None, fuse_msg=False):
         """(zadd1, zadd2, xs): everything of the LSTM pre-activation except (h*(1-done)) @ Wh and the bias -- as
@@ -763,44 +832,37 @@ class LstmPolicy(BatchedPolicy):
     name = 'lstm'
     summary_name = 'lstm_0'      # IA2C hands the writer to policy 0 alone (models.py:38-42)
     k_wh, k_b, k_wx = 'lstm_wh', 'lstm_b', 'lstm_wx'
-    k_ob = 'fc_w'                 # the observation encoder's weight
+    enc_layers = (('fc_w', 'fc_b', False), None)
+    enc_is_input = True
     coupled = False               # the recurrence has no cross-agent term -> fused sequence op
 
     def _phases(self):
-        nf, H, F = self.n_fc, self.n_h, self.n_feat
+        nf, H = self.n_fc, self.n_h
         return [[('fc_w', 'lstm_%d/fc/w', (self.n_obs, nf), self._L_slots),
                  ('fc_b', 'lstm_%d/fc/b', (nf,), None),
                  ('lstm_wx', 'lstm_%d/lstm/wx', (nf, 4 * H), None),
                  ('lstm_wh', 'lstm_%d/lstm/wh', (H, 4 * H), None),
                  ('lstm_b', 'lstm_%d/lstm/b', (4 * H,), None)] + self._head_phase('lstm_%d/pi', 'lstm_%d/v')]
 
-    def _enc(self, xv, fp, saved=None):
-        """The LSTM input s (x-side mode), else the x-side pre-activation s @ Wx [N,rows,4H] (bias is added in the
-        cell kernel).  saved: s as the rollout computed it (x-side mode) -- only the backward is set up."""
-        p = self.params
-        s = ops.fc_concat([self._ob_part(xv, 'fc_w', 'fc_b')], ops.BIAS_RELU, saved=saved)
-        return s if self.xside else ops.linear(s, p['lstm_wx'])
-
-    def _enc_infer(self, xv, fp, out=None):
-        s = self._fc_ob_infer(xv, 'fc_w', 'fc_b', ops.BIAS_RELU, out=out)
-        return s if self.xside else torch.bmm(s, self.params['lstm_wx'])
-
-    def fused_env_encode(self, fp_next, out):
-        return self._fused_spec(('fc_w', 'fc_b'), None, fp_next, out) if self.xside else None
-
-    enc_writes_bits = False       # (the 16-byte sign image belongs to the two-layer encodings: FPPolicy, NCMultiAgentPolicy)
+    def _enc_post(self, s, fp, infer, slot=None):
+        """The LSTM input s itself (x-side mode), else the x-side pre-activation s @ Wx [N,rows,4H] -- tf.concat([hx, hp]) @ wx as ONE
+        GEMM (the bias is added in the cell kernel)."""
+        if self.xside:
+            return s
+        return torch.bmm(s, self.params[self.k_wx]) if infer else ops.linear(s, self.params[self.k_wx])
 
     def enc_in_kernel(self, E, compact):
-        """IA2C / ConseNet: the policy + value launch runs the observation encoder itself (csrc/lstm_mfma.hip ENC 2 on the CACC input
-        layout, ENC 4 on the general one: the ATSC grid's 12 features x (1 + 4 neighbours))."""
-        m_enc = self.m_max if self.params['fc_w'].shape[1] == self.n_obs else 0       # ConseNet: own features only
-        return bool(compact) and self.xside and self.fused_pv and not self.hetero and \
-            ops.step_enc1_supported(self.n_feat, m_enc, self.n_fc, self.n_h, self.N)
-
-    def _enc_spec(self, x, fp, out, env=None, bits=None):
-        # self.nbrs: the SLAB's slot order (ascending) -- the weight rows follow it whatever order the env concatenates in (`_L_slots`)
-        p = self.params
-        return ops.step_enc_spec(x, fp, p['fc_w'], p['fc_b'], None, None, self.nbrs, out=out, env=env, bits=None)
+        """The policy + value launch runs the input encoders itself (csrc/lstm_mfma.hip).  IA2C / ConseNet: the observation encoder,
+        ENC 2 on the CACC input layout, ENC 4 on the general one (the ATSC grid's 12 features x (1 + 4 neighbours)); IA2C-FP: both,
+        ENC 1 / ENC 3 (the grid's 60 observation and 20 fingerprint inputs)."""
+        (_, _, own_only), fpl = self.enc_layers
+        W = self._enc_width
+        # (ConseNet's layer is n_h wide, yet num_fc has always been asked too: kept, DESIGN.md 4)
+        if not (bool(compact) and self.xside and self.fused_pv and not self.hetero and self.n_fc == W):
+            return False
+        if fpl is None:
+            return ops.step_enc1_supported(self.n_feat, 0 if own_only else self.m_max, W, self.n_h, self.N)
+        return ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, W, self.n_h, self.N)
 
     def _recur_in(self, enc, h):
         return enc
@@ -808,11 +870,10 @@ class LstmPolicy(BatchedPolicy):
 
 class FPPolicy(LstmPolicy):
     """IA2C_FP: fcs(obs) || fcp(neighbour fingerprints) -> LSTM(2 n_fc) (policies.py:163-185)."""
-    k_ob = 'fcs_w'
-    enc_writes_bits = True
+    enc_layers = (('fcs_w', 'fcs_b', False), ('fcp_w', 'fcp_b'))
 
     def _phases(self):
-        nf, H, F, A = self.n_fc, self.n_h, self.n_feat, self.n_a
+        nf, H = self.n_fc, self.n_h
         return [[('fcs_w', 'lstm_%d/fcs/w', (self.n_obs, nf), self._L_slots),
                  ('fcs_b', 'lstm_%d/fcs/b', (nf,), None),
                  ('fcp_w', 'lstm_%d/fcp/w', (self.n_na, nf), self._L_fp_obs),
@@ -821,42 +882,6 @@ class FPPolicy(LstmPolicy):
                  ('lstm_wh', 'lstm_%d/lstm/wh', (H, 4 * H), None),
                  ('lstm_b', 'lstm_%d/lstm/b', (4 * H,), None)] + self._head_phase('lstm_%d/pi', 'lstm_%d/v')]
 
-    def _enc(self, xv, fp, saved=None, bits=None):
-        p = self.params
-        nf = self.n_fc
-        # tf.concat([hx, hp]) @ wx as ONE K = 2 nf GEMM; both layers write their block of the concatenation in place; the
-        # neighbour gathers of the (compact) observation and of the fingerprints happen inside the fc kernels
-        s = ops.fc_concat([self._ob_part(xv, 'fcs_w', 'fcs_b'), (fp, p['fcp_w'], p['fcp_b'], self.nbr_idx)], ops.BIAS_RELU, saved=saved,
-                          bits=bits)
-        return s if self.xside else ops.linear(s, p['lstm_wx'])
-
-    def _enc_infer(self, xv, fp, out=None):
-        p = self.params
-        nf = self.n_fc
-        if self._enc_one_launch(xv, nf):
-            # [hx | hp] (policies.py:181) by ONE kernel: both layers, the fingerprint gather folded into the second
-            s = ops.fc_fwd_multi([self._ob_part(xv, 'fcs_w', 'fcs_b'), (fp, p['fcp_w'], p['fcp_b'], self.nbr_idx)],
-                                 ops.BIAS_RELU, out=out)
-        else:
-            s = torch.empty(self.N, xv.shape[1], 2 * nf, dtype=F32, device=xv.device) if out is None else out
-            self._fc_ob_infer(xv, 'fcs_w', 'fcs_b', ops.BIAS_RELU, out=s[:, :, :nf])
-            self._fc_infer(ops.nbr_gather(fp, self.nbr_idx), 'fcp_w', 'fcp_b', ops.BIAS_RELU, out=s[:, :, nf:])
-        return s if self.xside else torch.bmm(s, p['lstm_wx'])                          # else ONE K = 2 nf GEMM
-
-    def fused_env_encode(self, fp_next, out):
-        return self._fused_spec(('fcs_w', 'fcs_b'), ('fcp_w', 'fcp_b'), fp_next, out) if self.xside else None
-
-    def enc_in_kernel(self, E, compact):
-        """IA2C-FP: both input encoders inside the policy + value launch (csrc/lstm_mfma.hip ENC 1 on the CACC input layout, ENC 3
-        on the general one: the ATSC grid's 60 observation and 20 fingerprint inputs)."""
-        return bool(compact) and self.xside and self.fused_pv and not self.hetero and \
-            ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, self.n_fc, self.n_h, self.N)
-
-    def _enc_spec(self, x, fp, out, env=None, bits=None):
-        # self.nbrs: the slab's slot order, which the rows of fcs_w AND fcp_w follow (`_L_slots`, `_L_fp_obs`)
-        p = self.params
-        return ops.step_enc_spec(x, fp, p['fcs_w'], p['fcs_b'], p['fcp_w'], p['fcp_b'], self.nbrs, out=out, env=env, bits=bits)
-
 
 class NCMultiAgentPolicy(BatchedPolicy):
     """NeurComm: s = [relu(x~ W_ob), relu(p~ W_fp), relu(m~ W_msg)] -> LSTM(3H) (agents/utils.py:182-208).
@@ -864,14 +889,14 @@ class NCMultiAgentPolicy(BatchedPolicy):
     name = 'nc'
     summary_name = 'nc'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
-    k_ob = 'w_ob'
+    enc_layers = (('w_ob', 'w_ob_b', False), ('w_fp', 'w_fp_b'))
+    enc_is_input = True
     scope = 'nc/lstm_comm_%d'
     coupled = True                # messages: neighbours' h_{t-1} enter every step
     msg_kind = ops.MSG_GATHER_RELU
-    enc_writes_bits = True
 
     def _phases(self):
-        H, F, A = self.n_h, self.n_feat, self.n_a
+        H = self.n_h
         s = self.scope
         msg = [('w_msg', s + '/w_msg', (H * self.m_max, H), self._L_nbr(H)), ('w_msg_b', s + '/b_msg', (H,), self._L_nbr())]
         ob = [('w_ob', s + '/w_ob', (self.n_obs, H), self._L_slots), ('w_ob_b', s + '/b_ob', (H,), None)]
@@ -882,20 +907,25 @@ class NCMultiAgentPolicy(BatchedPolicy):
         first = ob + fp + msg if self.hetero else msg + ob + fp
         return [first + hid, self._head_phase(self.name + '/pi_%d', self.name + '/v_%d')]
 
-    def _enc(self, xv, fp):
-        """Observation + fingerprint thirds of s, already multiplied by their rows of wx_hid."""
-        p = self.params
-        H = self.n_h
-        s = ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b'), (fp, p['w_fp'], p['w_fp_b'], self.nbr_idx)], ops.BIAS_RELU)
-        return ops.linear(s, p['wx_hid'][:, :2 * H])
+    def _enc_saved_in(self, S):
+        """[hx | hp] as the rollout wrote it: the first 2H columns of the saved LSTM inputs."""
+        return S.view(self.N, -1, S.shape[-1])[:, :, :2 * self.n_h]
 
-    def _enc_saved(self, xv, fp, S, bits=None):
-        """[hx | hp] as the rollout wrote it into the first 2H columns of the saved LSTM inputs (backward only); bits: its sign image."""
-        p = self.params
-        H = self.n_h
-        Sv = S.view(self.N, -1, S.shape[-1])[:, :, :2 * H]
-        return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b'), (fp, p['w_fp'], p['w_fp_b'], self.nbr_idx)], ops.BIAS_RELU, saved=Sv,
-                             bits=bits)
+    def _enc_slot(self, xv, out):
+        """x-side mode: the full LSTM input [hx | hp | hm] [N,E,3H] (a fresh buffer or the given slot of the saved activations), of
+        which the layers fill [hx | hp]; the recurrent step adds the message third."""
+        if not self.xside:
+            return None, None
+        full = out if out is not None else torch.empty(self.N, xv.shape[1], 3 * self.n_h, dtype=F32, device=xv.device)
+        return full, full[:, :, :2 * self.n_h]
+
+    def _enc_post(self, s, fp, infer, slot=None):
+        """Observation + fingerprint thirds of s multiplied by their rows of wx_hid -- but for the x-side rollout step, which multiplies
+        the whole input itself."""
+        if infer and self.xside:
+            return slot
+        wx = self.params['wx_hid'][:, :2 * self.n_h]
+        return torch.bmm(s, wx) if infer else ops.linear(s, wx)
 
     def _recur_in(self, enc, h):
         p = self.params
@@ -904,35 +934,13 @@ class NCMultiAgentPolicy(BatchedPolicy):
         hm = torch.relu(torch.baddbmm(p['w_msg_b'].unsqueeze(1), m, p['w_msg']))
         return torch.baddbmm(enc, hm, p['wx_hid'][:, 2 * H:])
 
-    def _enc_infer(self, xv, fp, out=None):
-        """x-side mode: the full LSTM input [hx | hp | hm] [N,E,3H] (a fresh buffer or the given slot of the saved
-        activations) with [hx | hp] filled in; the recurrent step adds the message third.  Else: [hx | hp] @ Wx[:2H]."""
-        p = self.params
-        H = self.n_h
-        full = None
-        if self.xside:
-            full = out if out is not None else torch.empty(self.N, xv.shape[1], 3 * H, dtype=F32, device=xv.device)
-        s = None if full is None else full[:, :, :2 * H]
-        if self._enc_one_launch(xv, H):
-            # [hx | hp] of agents/utils.py:199 by ONE kernel (fingerprint gather folded in)
-            s = ops.fc_fwd_multi([self._ob_part(xv, 'w_ob', 'w_ob_b'), (fp, p['w_fp'], p['w_fp_b'], self.nbr_idx)],
-                                 ops.BIAS_RELU, out=s)
-        else:
-            if s is None:
-                s = torch.empty(self.N, xv.shape[1], 2 * H, dtype=F32, device=xv.device)
-            self._fc_ob_infer(xv, 'w_ob', 'w_ob_b', ops.BIAS_RELU, out=s[:, :, :H])
-            self._fc_infer(ops.nbr_gather(fp, self.nbr_idx), 'w_fp', 'w_fp_b', ops.BIAS_RELU, out=s[:, :, H:])
-        return full if self.xside else torch.bmm(s, p['wx_hid'][:, :2 * H])
-
-    def fused_env_encode(self, fp_next, out):
-        return self._fused_spec(('w_ob', 'w_ob_b'), ('w_fp', 'w_fp_b'), fp_next, out) if self.xside else None
-
     def enc_in_kernel(self, E, compact):
         """The one-launch lock-step also runs the two input encoders (and, for the batched CACC engine, the env step): ONE launch per
         lock-step (csrc/lstm_mfma.hip <4,1,1>).  NMARL_NC_ONE_LAUNCH=0: the encoders stay behind the env kernel (nmarl_cacc_step_encode)."""
+        W = self._enc_width      # (= n_h; num_fc has always been asked too although no layer here is n_fc wide: kept, DESIGN.md 4)
         return bool(compact) and self.xside and not self.hetero and self.pv_one_launch(E) and \
-            ops.step_enc_cacc_layout(self.n_feat) and \
-            ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, self.n_fc, self.n_h, self.N) and \
+            ops.step_enc_cacc_layout(self.n_feat) and self.n_fc == W and \
+            ops.step_enc_supported(self.n_feat, self.n_a, self.m_max, W, self.n_h, self.N) and \
             os.environ.get('NMARL_NC_ONE_LAUNCH', '1') != '0'
 
     @property
@@ -941,10 +949,6 @@ class NCMultiAgentPolicy(BatchedPolicy):
         # kernel behind the <4,1,1> launch -- rollout graph 5.59-5.62 vs 5.53-5.56 ms (two launches, round 5: 5.60-5.64),
         # profiles/r06_ab_lockstep_nc.txt -- so the env kernel stays a launch of its own.  NMARL_NC_ENV_IN_KERNEL=1: one launch.
         return os.environ.get('NMARL_NC_ENV_IN_KERNEL', '0') == '1'
-
-    def _enc_spec(self, x, fp, out, env=None, bits=None):
-        p = self.params
-        return ops.step_enc_spec(x, fp, p['w_ob'], p['w_ob_b'], p['w_fp'], p['w_fp_b'], self.nbrs, out=out, env=env, bits=bits)
 
     def _recur_addends(self, enc, h, second=False, save=None, fuse_msg=False):
         p = self.params
@@ -977,13 +981,14 @@ class IC3MultiAgentPolicy(BatchedPolicy):
     name = 'ic3'
     summary_name = 'ic3'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
-    k_ob = 'w_ob'
+    enc_layers = (('w_ob', 'w_ob_b', False), None)
+    enc_act = ops.BIAS_TANH       # (nothing after the layer: the message term is added inside the recurrence)
     scope = 'ic3/lstm_ic3_%d'
     coupled = True
     msg_kind = ops.MSG_MEAN_ADD
 
     def _phases(self):
-        H, F = self.n_h, self.n_feat
+        H = self.n_h
         s = self.scope
         return [[('w_msg', s + '/w_msg', (H, H), self._L_nbr()),
                  ('w_msg_b', s + '/b_msg', (H,), self._L_nbr()),
@@ -993,10 +998,6 @@ class IC3MultiAgentPolicy(BatchedPolicy):
                  ('wh_hid', s + '/wh_hid', (H, 4 * H), None),
                  ('hid_b', s + '/b_hid', (4 * H,), None)],
                 self._head_phase(self.name + '/pi_%d', self.name + '/v_%d')]
-
-    def _enc(self, xv, fp):
-        p = self.params
-        return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b')], ops.BIAS_TANH)
 
     def _recur_in(self, enc, h):
         p = self.params
@@ -1012,14 +1013,10 @@ class IC3MultiAgentPolicy(BatchedPolicy):
 
     save_pad = ('MM',)
 
-    def _enc_saved(self, xv, fp, S):
+    def _enc_saved_in(self, S):
+        """The ENC slots, if this batch's rollout filled them."""
         enc = self._extra.get('ENC')
-        if enc is None or not self._enc_was_saved:
-            return self._enc(xv, fp)         # recomputed (one streaming pass)
-        return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b')], ops.BIAS_TANH, saved=enc.view(self.N, -1, self.n_h))
-
-    def _enc_infer(self, xv, fp, out=None):
-        return self._fc_ob_infer(xv, 'w_ob', 'w_ob_b', ops.BIAS_TANH, out=out)
+        return enc.view(self.N, -1, self.n_h) if (enc is not None and self._enc_was_saved) else None
 
     def _x_target(self, h, second, save):
         """Where the LSTM input of this step goes: the slot of the saved activations (policy step of the batched
@@ -1056,18 +1053,19 @@ class IC3MultiAgentPolicy(BatchedPolicy):
 
     def encodes_in_step(self, E, compact):
         return compact and not self.hetero and self.n_obs != self.n_feat and \
-            ops.ob_encoder_supported(self.n_feat, self.n_obs, self.n_h) and self.pv_one_launch(E)
+            ops.ob_encoder_supported(self.n_feat, self.n_obs, self._enc_width) and self.pv_one_launch(E)
 
     def refresh_wimage(self):
         super().refresh_wimage()
-        if self.xside and not self.hetero and ops.ob_encoder_supported(self.n_feat, self.n_obs, self.n_h):
+        if self.xside and not self.hetero and ops.ob_encoder_supported(self.n_feat, self.n_obs, self._enc_width):
             if self._ob_pad is None:
                 self._ob_pad = torch.zeros(self.N, ops.FC_J, self.n_h, dtype=F32, device=self.device)
-            self._ob_img = ops.lstm_ob_wimage(self.params['w_ob'], self._ob_pad, out=self._ob_img)
+            self._ob_img = ops.lstm_ob_wimage(self.params[self.k_ob], self._ob_pad, out=self._ob_img)
 
     def _ob_spec(self, ob):
         p = self.params
-        return dict(x=ob, nbr=self.nbr_self, img=self._ob_img, b=p['w_ob_b'], w=p['w_ob'])
+        (w, b, _), _ = self.enc_layers
+        return dict(x=ob, nbr=self.nbr_self, img=self._ob_img, b=p[b], w=p[w])
 
 
 class ConsensusPolicy(LstmPolicy):
@@ -1076,7 +1074,7 @@ class ConsensusPolicy(LstmPolicy):
     neighbours (`_get_critic_wts` averages only the `lstm_%da` scope)."""
     name = 'cu'
     summary_name = 'cu'
-    k_ob = 'fc_w'
+    enc_layers = (('fc_w', 'fc_b', True), None)       # the consensus net sees the agent's own features only
 
     def _phases(self):
         H, F = self.n_h, self.n_feat
@@ -1084,18 +1082,6 @@ class ConsensusPolicy(LstmPolicy):
                  ('lstm_wx', 'cu/lstm_%da/wx', (H, 4 * H), None),
                  ('lstm_wh', 'cu/lstm_%da/wh', (H, 4 * H), None),
                  ('lstm_b', 'cu/lstm_%da/b', (4 * H,), None)] + self._head_phase('cu/pi_%da' if self.hetero else 'cu/pi_%d', 'cu/v_%da')]   # policies.py:381-390: the identical branch names the actor head pi_<i>, the hetero one pi_<i>a
-
-    def _own(self, xv):
-        return xv[:, :, :self.n_feat]        # the consensus net sees the agent's own features only (compact obs: all of xv)
-
-    def _enc(self, xv, fp, saved=None):
-        p = self.params
-        s = ops.fc_concat([(self._own(xv), p['fc_w'], p['fc_b'])], ops.BIAS_RELU, saved=saved)
-        return s if self.xside else ops.linear(s, p['lstm_wx'])
-
-    def _enc_infer(self, xv, fp, out=None):
-        s = self._fc_infer(self._own(xv), 'fc_w', 'fc_b', ops.BIAS_RELU, out=out)
-        return s if self.xside else torch.bmm(s, self.params['lstm_wx'])
 
     def consensus_update(self, skip_if=None):
         """policies.py:357-364, 403-426: simultaneous neighbourhood average of (wx, wh, b) of every agent's LSTM.
@@ -1135,13 +1121,13 @@ class DIALMultiAgentPolicy(BatchedPolicy):
     name = 'dial'
     summary_name = 'dial'
     k_wh, k_b, k_wx = 'wh_hid', 'hid_b', 'wx_hid'
-    k_ob = 'w_ob'
+    enc_layers = (('w_ob', 'w_ob_b', False), None)
     coupled = True
     msg_kind = ops.MSG_DIAL
     msg_inplace_ok = True
 
     def _phases(self):
-        H, F = self.n_h, self.n_feat
+        H = self.n_h
         s = 'dial/lstm_comm_%d'
         return [[('w_msg', s + '/w_msg', (H * self.m_max, H), self._L_nbr(H)),
                  ('w_msg_b', s + '/b_msg', (H,), self._L_nbr()),
@@ -1168,24 +1154,26 @@ class DIALMultiAgentPolicy(BatchedPolicy):
         sc = self._ai_scale(fp)
         return oh if sc is None else oh * sc
 
-    def _enc(self, xv, fp):
-        p = self.params
-        return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b')], ops.BIAS_RELU) + self._own_action_onehot(fp)
+    def _enc_saved_in(self, S):
+        # recomputed (only the recurrence is saved) for the observation layer's backward; CoupledSequenceSaved never reads the
+        # VALUE of enc (the LSTM inputs S = enc + hm are saved), and the own-action one-hot is a constant: left out there
+        return None
+
+    def _enc_slot(self, xv, out):
+        return None, None         # (a fresh tensor: the slot of the saved LSTM inputs is written by the step, S = enc + hm)
+
+    def _enc_post(self, s, fp, infer, slot=None):
+        """+ the own-action one-hot."""
+        if not infer:
+            return s + self._own_action_onehot(fp)
+        sc = self._ai_scale(fp)
+        return ops.onehot_argmax_add_(s, fp, None if sc is None else sc.view(-1))
 
     def _recur_in(self, enc, h):
         p = self.params
         msg = torch.relu(torch.baddbmm(p['mfc_b'].unsqueeze(1), h, p['mfc_w']))        # sender side, un-masked h
         hm = torch.relu(torch.baddbmm(p['w_msg_b'].unsqueeze(1), ops.nbr_gather(msg, self.nbr_idx), p['w_msg']))
         return torch.bmm(enc + hm, p['wx_hid'])
-
-    def _enc_saved(self, xv, fp, S):
-        # recomputed (only the recurrence is saved) for the observation layer's backward; CoupledSequenceSaved never reads the
-        # VALUE of enc (the LSTM inputs S = enc + hm are saved), and the own-action one-hot is a constant: left out here
-        return ops.fc_concat([self._ob_part(xv, 'w_ob', 'w_ob_b')], ops.BIAS_RELU)
-
-    def _enc_infer(self, xv, fp, out=None):
-        sc = self._ai_scale(fp)
-        return ops.onehot_argmax_add_(self._fc_ob_infer(xv, 'w_ob', 'w_ob_b', ops.BIAS_RELU), fp, None if sc is None else sc.view(-1))
 
     def save_spec(self):
         return {'A1': self.n_h, 'A2': self.n_h}        # hm (post-relu), msg (post-relu): relu masks of the backward

@@ -140,7 +140,7 @@ class CACCBatchEnv:
 
     def set_compact_obs(self, flag=True):
         """Compact observation [E,N,5] (each vehicle's own features, SURVEY.md 8d's 347-B layout) instead of the
-        pre-gathered [E,N,15]: the consumer gathers the neighbours (agents/policies.py `_ob_part`).  Batched engine only
+        pre-gathered [E,N,15]: the consumer gathers the neighbours (agents/policies.py `_enc_parts`).  Batched engine only
         (the E = 1 reference duck-type keeps the reference's concatenated observations)."""
         self.compact_obs = bool(flag)
         self.params.compact_obs = 1 if flag else 0

@@ -161,7 +161,7 @@ class LargeGridBatchEnv(AtscBatchEnv):
     def set_compact_obs(self, flag=True):
         """Compact observation [E,N,12]: every node's OWN wave vector -- what the reference hands an MA2C agent
         (atsc_env.py:253-262) -- instead of the gathered [E,N,60] slab; the consumer gathers the neighbours
-        (agents/policies.py `_ob_part`).  Batched engine only: the E = 1 reference duck-type keeps the slab."""
+        (agents/policies.py `_enc_parts`).  Batched engine only: the E = 1 reference duck-type keeps the slab."""
         self.compact_obs = bool(flag)
         self.params.compact_obs = 1 if flag else 0
         self.obs = torch.zeros(self.E, self.n_agent, N_FEAT if flag else N_OBS, dtype=torch.float32, device=self.device)

@@ -81,16 +81,16 @@ def test_captured_update_equals_eager_update(agent, scenario, monkeypatch):
 def test_commnet_update_uses_the_saved_encoder_outputs_every_batch(use_graph, monkeypatch):
     """CommNet: the rollout saves the encoder outputs of every lock-step, and the update must use them in EVERY batch -- also
     when the rollout is a hipGraph replay (no Python runs then: the per-batch `_enc_was_saved` flag the update clears has to be
-    raised again by the trainer).  The recomputing encoder forward is counted; same weights as the eager run either way."""
-    from deeprl_network_amd.agents.policies import IC3MultiAgentPolicy
-    calls = {'n': 0}
-    orig = IC3MultiAgentPolicy._enc
-
-    def counting(self, xv, fp):
-        calls['n'] += 1
-        return orig(self, xv, fp)
-    monkeypatch.setattr(IC3MultiAgentPolicy, '_enc', counting)
+    raised again by the trainer).  The recomputing encoder forward (an ops.fc_concat without the saved output) is counted; same
+    weights as the eager run either way."""
     from deeprl_network_amd import ops
+    calls = {'n': 0}
+    orig = ops.fc_concat
+
+    def counting(parts, act, saved=None, bits=None):
+        calls['n'] += saved is None
+        return orig(parts, act, saved=saved, bits=bits)
+    monkeypatch.setattr(ops, 'fc_concat', counting)
     means = {'n': 0}
     orig_mean = ops.nbr_mean
 
