@@ -130,6 +130,11 @@ class TrainRecord(C.Structure):
                                            'ws')])
 
 
+class GatherDesc(C.Structure):
+    """nmarl_gather_desc_t (include/nmarl.h): one (src, dst, outer, inner_bytes) of nmarl_minibatch_gather."""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('outer', C.c_int64), ('inner_bytes', C.c_int64)]
+
+
 class BpttCoupled(C.Structure):
     """nmarl_bptt_coupled_t (include/nmarl.h): arguments of nmarl_lstm_bptt_coupled."""
     _fields_ = ([(k, C.c_int32) for k in ('kind', 'N', 'T', 'H', 'm_max', 'r_max', 'r_row', 'symmetric', 'mode', 'ring_slots')] +
@@ -290,6 +295,9 @@ SIGNATURES = {
     'nmarl_timestamp': [_p, _p],
     'nmarl_timestamp_rate_khz': [],
     'nmarl_copy_multi': [_i32, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64), _p, _p],
+    'nmarl_minibatch_perm': [_i32, _u64, _i64, _i32, _p, _p, _p, _p],
+    'nmarl_minibatch_count_advance': [_p, _p],
+    'nmarl_minibatch_gather': [_i32, C.POINTER(GatherDesc), _p, _i32, _i32, _p],
 }
 
 for _name, _args in SIGNATURES.items():

@@ -23,7 +23,9 @@ Engine (per n_step batch, E replicas, N agents):
             against the behaviour policy's log-probabilities (nmarl_ppo_logp, nmarl_ppo_loss_*) -> all-reduce -> optimiser;
             opt-in ppo_vclip: the value term of those steps clipped around the behaviour critic's values (nmarl_ppo_loss_vclip_*);
             opt-in ppo_target_kl: the steps behind the first epoch whose pooled approx_kl exceeds it change nothing, decided on
-            the device (nmarl_ppo_kl_sum -> all-reduce -> nmarl_ppo_kl_gate -> the optimiser's status word)].
+            the device (nmarl_ppo_kl_sum -> all-reduce -> nmarl_ppo_kl_gate -> the optimiser's status word);
+            opt-in ppo_minibatches = M > 1: every epoch k >= 2 permutes the replicas on the device (nmarl_minibatch_perm) and makes
+            M such steps, each on the gathered rows of E / M whole sequences (nmarl_minibatch_gather)].
 """
 import functools
 import logging
@@ -175,6 +177,24 @@ class IA2C:
         for key in ('ppo_vclip', 'ppo_target_kl'):
             if getattr(self, key) is not None and self.ppo_epochs == 1:
                 raise ValueError('%s = %r with ppo_epochs = 1: it acts on epochs 2..K only' % (key, model_config.get(key)))
+        # optional (absent: 1 = every epoch is one full-batch step, as before): M > 1 splits the replicas of every epoch k >= 2 into M
+        # groups of whole sequences along a permutation drawn on the device, one optimiser step per group
+        raw = model_config.get('ppo_minibatches', fallback='1').strip()
+        try:
+            self.ppo_minibatches = int(raw)
+        except ValueError:
+            raise ValueError('ppo_minibatches = %r: must be an integer >= 1' % raw)
+        if self.ppo_minibatches < 1:
+            raise ValueError('ppo_minibatches = %r: must be an integer >= 1' % raw)
+        if self.ppo_minibatches > 1:
+            if self.ppo_epochs == 1:
+                raise ValueError('ppo_minibatches = %d with ppo_epochs = 1: it splits epochs 2..K only' % self.ppo_minibatches)
+            if self.ppo_minibatches > int(num_envs) or int(num_envs) % self.ppo_minibatches:
+                raise ValueError('ppo_minibatches = %d does not divide the %d replica(s) of a rank into groups of whole sequences'
+                                 % (self.ppo_minibatches, int(num_envs)))
+        # test switch: M = 1 routed through the gather with the identity permutation (the plumbing must be lossless)
+        self._mb_identity = self.ppo_minibatches == 1 and self.ppo_epochs > 1 and os.environ.get('NMARL_TEST_MINIBATCH_IDENTITY') == '1'
+        self._mb_on = self.ppo_minibatches > 1 or self._mb_identity
         self.E = int(num_envs)
         self.device = torch.device(device)
         self.dist_group = dist_group
@@ -316,7 +336,23 @@ class IA2C:
                 self.ppo_gate = torch.tensor(ops.PPO_GATE_RESET, dtype=torch.int32, device=d)
                 self._ppo_gate_reset = torch.tensor(ops.PPO_GATE_RESET, dtype=torch.int32, device=d)
                 self._ppo_gate_pending = False
-        self.dist_dev = torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
+            if self._mb_on:
+                # opt-in replica minibatches: the permutation of an epoch, its Philox keys, the count of updates made so far (what
+                # the draw is keyed by, beside the epoch: advanced on the device once per update) and the dense operands of one
+                # step -- every [.., E, ..] buffer of the update with E / M replicas in E's place (ops.minibatch_gather)
+                Em, H = E // self.ppo_minibatches, self.n_lstm
+                self.mb_env_id_base = 0              # (BatchedTrainer: the env's, so every rank permutes its shard with its own draws)
+                self.mb_perm = torch.arange(E, dtype=torch.int32, device=d)
+                self.mb_count = torch.zeros(1, dtype=torch.int32, device=d)
+                self._mb = dict(keys=torch.zeros(E, dtype=torch.int32, device=d),
+                                x=torch.zeros(T, Em, N, p.n_obs, dtype=F32, device=d), fp=torch.zeros(T, N, Em, self.n_a, dtype=F32, device=d),
+                                act=torch.zeros(T, Em, N, dtype=torch.uint8, device=d), done=torch.zeros(T, Em, dtype=F32, device=d),
+                                adv=torch.zeros(N, T * Em, dtype=F32, device=d), R=torch.zeros(N, T * Em, dtype=F32, device=d),
+                                logp=torch.zeros(N, T * Em, dtype=F32, device=d), h=torch.zeros(N, Em, H, dtype=F32, device=d),
+                                c=torch.zeros(N, Em, H, dtype=F32, device=d))
+                if self.ppo_vclip is not None:
+                    self._mb['v_old'] = torch.zeros(N, T * Em, dtype=F32, device=d)
+        self.dist_dev =torch.from_numpy(self.distance_mask.astype(np.int32)).to(d)
         self.t = 0
         self.grad_norm = torch.zeros(N, dtype=F32, device=d)
         self.last_loss = None
@@ -363,6 +399,8 @@ class IA2C:
             return False          # the gathering encoder kernel (nmarl_fc_fwd_multi) is 64 outputs wide, inputs <= 64
         T, E, N = self.n_step, self.E, self.n_agent
         self.buf_x = torch.zeros(T + 1, E, N, p.n_feat, dtype=F32, device=self.device)
+        if self._mb_on:           # opt-in replica minibatches: the gathered slab follows the buffer it is gathered from
+            self._mb['x'] = torch.zeros(T, E // self.ppo_minibatches, N, p.n_feat, dtype=F32, device=self.device)
         self.compact_obs = True
         return True
 
@@ -685,11 +723,20 @@ class IA2C:
         self.update_grads(R_end)
         self.update_reduce()
         self.update_apply(lr, rotate=rotate and K == 1)
-        for k in range(2, K + 1):         # opt-in PPO epochs: the same batch, returns, advantages and lr; one all-reduce per step
-            self.update_ppo_grads(k)
+        steps = self.ppo_steps()          # opt-in PPO epochs: the same batch, returns, advantages and lr; one all-reduce per step
+        for i, step in enumerate(steps):
+            self.update_ppo_grads(*step)
             self.update_reduce()
-            self.update_apply(lr, rotate=rotate and k == K)
+            self.update_apply(lr, rotate=rotate and i == len(steps) - 1)
         self.update_end()
+
+    def ppo_steps(self):
+        """The optimiser steps of an update behind the first, as the arguments of `update_ppo_grads` in order: (k,) for k = 2..K, or
+        under the opt-in ppo_minibatches = M > 1 (k, j) for every epoch's groups j = 0..M-1."""
+        K, M = self.ppo_epochs, self.ppo_minibatches
+        if M == 1:
+            return [(k,) for k in range(2, K + 1)]
+        return [(k, j) for k in range(2, K + 1) for j in range(M)]
 
     def update_begin(self):
         """Host only: advance the lr schedule.  It counts lock-steps (environment steps per replica), the reference's
@@ -795,31 +842,64 @@ class IA2C:
                 log_pi = torch.log(torch.clamp(torch.softmax(logits, dim=-1), 1e-10, 1.0))
                 self.ppo_logp_old.copy_(log_pi.gather(-1, action.t().long().unsqueeze(-1)).squeeze(-1))
 
-    def update_ppo_grads(self, k):
+    def _minibatch(self, k, j):
+        """Step (k, j) under the opt-in replica minibatches: draw epoch k's permutation in front of its first group, then gather the
+        rows of the replicas perm[j E/M .. (j + 1) E/M) of every operand of `update_ppo_grads` into the dense buffers `_mb` (whole
+        sequences: all T steps of a replica and its own h_bw / c_bw).  Behind the update's last gather the count of updates moves."""
+        N, T, E, M, mb = self.n_agent, self.n_step, self.E, self.ppo_minibatches, self._mb
+        Em = E // M
+        if j == 0 and not self._mb_identity:
+            ops.minibatch_perm(int(self.seed or 0), self.mb_env_id_base, k, self.mb_count, mb['keys'], self.mb_perm)
+        pairs = [(mb['x'], self.buf_x[:T], T), (mb['fp'], self.buf_fp[:T], T * N), (mb['act'], self.buf_act, T),
+                 (mb['done'], self.buf_done_pre, T), (mb['adv'], self._loss_adv(), N * T), (mb['R'], self.R, N * T),
+                 (mb['logp'], self.ppo_logp_old, N * T), (mb['h'], self.h_bw, N), (mb['c'], self.c_bw, N)]
+        if self.ppo_vclip is not None:
+            pairs.append((mb['v_old'], self.ppo_v_old, N * T))
+        ops.minibatch_gather([(d_, s_) for d_, s_, _ in pairs], self.mb_perm[j * Em:(j + 1) * Em], outer_of=[o for _, _, o in pairs])
+        if k == self.ppo_epochs and j == M - 1 and not self._mb_identity:
+            ops.minibatch_count_advance(self.mb_count)
+
+    def update_ppo_grads(self, k, j=0):
         """Epoch k = 2..K of an update up to the flat gradient: the forward pass recomputed with the current weights from the state
         the batch started from, the heads, the clipped surrogate against ppo_logp_old, backward.  R, Adv and the policy term's
-        advantage are those of `update_grads`.  Capturable like it."""
-        assert 2 <= k <= self.ppo_epochs
-        N, T, E = self.n_agent, self.n_step, self.E
+        advantage are those of `update_grads`.  Capturable like it.  Under the opt-in ppo_minibatches = M > 1 this is step (k, j),
+        j = 0..M-1: the same chain on the gathered tensors of the epoch's j-th group of replicas, its means over that group's rows;
+        ppo_stats[k - 1] collects the mean of the epoch's M steps."""
+        assert 2 <= k <= self.ppo_epochs and 0 <= j < self.ppo_minibatches
+        N, T, E, M = self.n_agent, self.n_step, self.E, self.ppo_minibatches
         p = self.policy
         ps = p.params
-        ps.begin_backward()
-        FP = self.buf_fp[:T].permute(1, 0, 2, 3).reshape(N, T * E, self.n_a)
-        Hs = p.unroll(self.buf_x[:T], FP, self.buf_done_pre, self.h_bw, self.c_bw, masked_steps=self.masked_steps)
-        action = self.buf_act.view(T * E, N)
-        logits, v = p.heads(Hs, action)
-        adv, R = self._loss_adv(), self.R.view(N, T * E)
         vclip = self.ppo_vclip
-        kw = {} if vclip is None else dict(v_old=self.ppo_v_old, vclip=vclip)
-        if ops.ppo_loss_supported(self.n_a):
-            per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, self.ppo_logp_old, self.ppo_clip, self.v_coef, self.e_coef, **kw)
+        if self._mb_on:
+            self._minibatch(k, j)
+            mb, E = self._mb, E // M
+            X, FPs, done, h0, c0, action = mb['x'], mb['fp'], mb['done'], mb['h'], mb['c'], mb['act'].view(T * E, N)
+            adv, R, logp_old, v_old = mb['adv'], mb['R'], mb['logp'], mb.get('v_old')
         else:
-            per_agent, cols = self._loss_torch(logits, v, action, adv, R, self.ppo_logp_old, kw.get('v_old'))
+            X, FPs, done, h0, c0, action = self.buf_x[:T], self.buf_fp[:T], self.buf_done_pre, self.h_bw, self.c_bw, self.buf_act.view(T * E, N)
+            logp_old, v_old = self.ppo_logp_old, (None if vclip is None else self.ppo_v_old)
+        ps.begin_backward()
+        FP = FPs.permute(1, 0, 2, 3).reshape(N, T * E, self.n_a)
+        Hs = p.unroll(X, FP, done, h0, c0, masked_steps=self.masked_steps)
+        logits, v = p.heads(Hs, action)
+        if not self._mb_on:
+            adv, R = self._loss_adv(), self.R.view(N, T * E)
+        kw = {} if vclip is None else dict(v_old=v_old, vclip=vclip)
+        if ops.ppo_loss_supported(self.n_a):
+            per_agent, terms = ops.ppo_loss(logits, v, action, adv, R, logp_old, self.ppo_clip, self.v_coef, self.e_coef, **kw)
+        else:
+            per_agent, cols = self._loss_torch(logits, v, action, adv, R, logp_old, kw.get('v_old'))
             with torch.no_grad():
                 terms = torch.stack(cols, dim=1)
-        self.ppo_stats[k - 1].copy_(terms[:, 3:5])
-        if vclip is not None:
-            self.ppo_vclip_stats[k - 1].copy_(terms[:, 5])
+        # (approx_kl, clip_frac) and vclip_frac of the epoch: the mean of its M steps, summed in step order
+        stats = [(self.ppo_stats[k - 1], terms[:, 3:5])] + ([] if vclip is None else [(self.ppo_vclip_stats[k - 1], terms[:, 5])])
+        for acc, t_ in stats:
+            if j == 0:
+                acc.copy_(t_)
+            else:
+                acc.add_(t_)
+            if M > 1 and j == M - 1:
+                acc.div_(M)
         t3 = self._terms = terms[:, :3].contiguous()
         self.last_loss = (t3[:, 0], t3[:, 1], t3[:, 2], per_agent.detach())
         per_agent.sum().backward()
@@ -833,6 +913,14 @@ class IA2C:
     @property
     def ppo_epochs_done(self):
         """Optimiser steps the last update applied before the KL stop, 1..K (host read: synchronises); None with ppo_target_kl off."""
+        if not hasattr(self, 'ppo_gate'):
+            return None
+        return 1 + (int(self.ppo_gate[2]) - 1) // self.ppo_minibatches      # (under minibatches: the epochs applied in full)
+
+    @property
+    def ppo_steps_done(self):
+        """Optimiser steps the last update applied before the KL stop, 1..1 + (K - 1) M (host read: synchronises); None with
+        ppo_target_kl off.  Without minibatches it equals ppo_epochs_done."""
         return None if not hasattr(self, 'ppo_gate') else int(self.ppo_gate[2])
 
     @property
@@ -1010,6 +1098,9 @@ class IA2C:
             # opt-in reward scaling: the setting, the pooled running moments and the carried discounted returns (absent otherwise)
             slots.update({'reward_scale': self.reward_scale, 'reward_scale_state': self.rs_state.detach().cpu(),
                           'reward_scale_carry': self.rs_carry.detach().cpu()})
+        if self.ppo_minibatches > 1 and hasattr(self, 'mb_count'):
+            # opt-in replica minibatches: the updates made so far, what the next permutation is keyed by (absent otherwise)
+            slots['ppo_minibatch_count'] = self.mb_count.detach().cpu()
         torch.save({'variables': {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in ps.ref_variables()},
                     'optimizer': self.optimizer, **slots, 'name': self.name, 'global_step': int(global_step),
                     'lr_n': float(sched.n) if sched is not None else -1.0}, path)
@@ -1065,6 +1156,13 @@ class IA2C:
                     logging.warning('Checkpoint %s carries %d discounted returns, this model %d (another num_envs): moments loaded, '
                                     'the carried returns left fresh' % (save_file, blob['reward_scale_carry'].numel(),
                                                                         self.rs_carry.numel()))
+            if self.ppo_minibatches > 1 and hasattr(self, 'mb_count'):
+                if 'ppo_minibatch_count' in blob:
+                    self.mb_count.copy_(blob['ppo_minibatch_count'])
+                else:
+                    self.mb_count.zero_()
+                    logging.warning('Checkpoint %s carries no ppo_minibatch_count (written without ppo_minibatches): the permutations '
+                                    'start from count 0' % save_file)
             if blob.get('lr_n', -1.0) >= 0 and getattr(self, 'lr_scheduler', None) is not None:
                 self.lr_scheduler.n = blob['lr_n']       # resume the lr decay where it stopped
             logging.info('Checkpoint loaded: %s' % save_file)

@@ -73,6 +73,7 @@ __device__ __forceinline__ float u01_from_bits(uint32_t w) {
 #define NMARL_STREAM_RESET 0u
 #define NMARL_STREAM_ACTION 1u
 #define NMARL_STREAM_GRID 2u
+#define NMARL_STREAM_MINIBATCH 3u
 
 // The draw of nmarl_sample_actions (a2c.hip: sample_kernel) on a register-resident probability row of at
 // most MAXA entries: argmax (mode 2) or numpy's choice = searchsorted(cumsum(p)/sum, u, 'right') with the

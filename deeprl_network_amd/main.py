@@ -53,6 +53,10 @@ OVERRIDES = (
      'KL stop of steps 2..K (overrides MODEL_CONFIG ppo_target_kl; default absent = no stop).  Once the mean '
      'approx_kl of a step exceeds this, that step and the rest of the update change nothing; decided on the '
      'device, the remaining passes still run (it buys stability, not time); finite and > 0, needs ppo_epochs > 1'),
+    ('--ppo-minibatches', 'ppo_minibatches', str, dict(type=int),
+     'replica minibatches of epochs 2..K (overrides MODEL_CONFIG ppo_minibatches; default 1 = one full-batch step '
+     'per epoch).  M > 1: every epoch permutes the replicas on the device and makes M optimiser steps, each on '
+     'E / M whole sequences; M must divide the replicas per rank, needs ppo_epochs > 1'),
 )
 
 

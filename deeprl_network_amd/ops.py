@@ -2138,6 +2138,59 @@ def copy_multi(pairs, skip_if=None):
         check(lib.nmarl_copy_multi(n, dst, src, nbytes, ptr(skip_if, torch.int32, strided=True), stream()), 'nmarl_copy_multi')
 
 
+GATHER_MAX = 16            # NMARL_GATHER_MAX
+MINIBATCH_MAX_E = 65536    # NMARL_MINIBATCH_MAX_E
+STREAM_MINIBATCH = 3       # NMARL_STREAM_MINIBATCH (csrc/common.h)
+
+
+def minibatch_perm(seed, env_id_base, epoch, count, keys, out):
+    """nmarl_minibatch_perm: out [E] int32 <- the permutation of the E replicas that ascending (Philox key, index) order gives, the
+    key of replica e drawn from (env_id_base + e, epoch, count[0]) under `seed`; count [1] int32 is read on the device (a replayed
+    graph follows it), keys [E] int32 is scratch.  Two kernel launches on the current stream."""
+    E = out.numel()
+    if out.dtype != torch.int32 or keys.dtype != torch.int32 or keys.numel() < E or count.dtype != torch.int32 or count.numel() != 1:
+        raise _lib.NmarlError('minibatch_perm: out [E] int32, keys [E] int32, count [1] int32')
+    check(lib.nmarl_minibatch_perm(E, int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_id_base), int(epoch), ptr(count, torch.int32), ptr(keys),
+                                   ptr(out), stream()), 'nmarl_minibatch_perm')
+    return out
+
+
+def minibatch_count_advance(count):
+    """nmarl_minibatch_count_advance: count [1] int32 += 1 by a one-thread kernel (once per update; a kernel node when captured)."""
+    if count.dtype != torch.int32 or count.numel() != 1:
+        raise _lib.NmarlError('minibatch_count_advance: count must be one int32')
+    check(lib.nmarl_minibatch_count_advance(ptr(count, torch.int32), stream()), 'nmarl_minibatch_count_advance')
+
+
+def minibatch_gather(pairs, idx, outer_of=None):
+    """nmarl_minibatch_gather: [(dst, src), ...] contiguous device tensors of one dtype per pair; src is viewed as
+    [outer, E, inner] and dst as the dense [outer, Em, inner], dst[o, i] = src[o, idx[i]] with idx [Em] int32 on the device.
+    outer_of: each pair's `outer` (a sequence as long as pairs; None: the sources' leading dimension).  E follows from the sizes and
+    must be the same for every pair.  One kernel launch per 16 pairs on the current stream (a kernel node when captured)."""
+    pairs = list(pairs)
+    Em = idx.numel()
+    outer_of = [s_.shape[0] for _, s_ in pairs] if outer_of is None else [int(o) for o in outer_of]
+    if idx.dtype != torch.int32 or Em < 1 or len(outer_of) != len(pairs) or not pairs:
+        raise _lib.NmarlError('minibatch_gather: idx [Em] int32, one outer per pair, at least one pair')
+    descs, E = [], None
+    for (d, s_), outer in zip(pairs, outer_of):
+        nb_d, nb_s = d.numel() * d.element_size(), s_.numel() * s_.element_size()
+        if d.dtype != s_.dtype or outer < 1 or nb_d == 0 or nb_d % (outer * Em):
+            raise _lib.NmarlError('minibatch_gather: %s %s <- %s %s does not split as [%d, Em = %d, inner] <- [%d, E, inner]'
+                                  % (tuple(d.shape), d.dtype, tuple(s_.shape), s_.dtype, outer, Em, outer))
+        inner = nb_d // (outer * Em)
+        e_pair, rest = divmod(nb_s, outer * inner)
+        if rest or e_pair < 1 or (E is not None and e_pair != E):
+            raise _lib.NmarlError('minibatch_gather: source %s does not hold [%d, E, %d bytes] with one E for all pairs'
+                                  % (tuple(s_.shape), outer, inner))
+        E = e_pair
+        descs.append((ptr(s_), ptr(d), outer, inner))
+    for i in range(0, len(descs), GATHER_MAX):
+        part = descs[i:i + GATHER_MAX]
+        arr = (_lib.GatherDesc * len(part))(*[_lib.GatherDesc(*p) for p in part])
+        check(lib.nmarl_minibatch_gather(len(part), arr, ptr(idx, torch.int32), Em, E, stream()), 'nmarl_minibatch_gather')
+
+
 def timestamp(out):
     """nmarl_timestamp: out [1] int64 device tensor <- the device's constant-rate wall clock, from a one-thread kernel on the
     current stream (capturable: a kernel node).  Measurement only."""

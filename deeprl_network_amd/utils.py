@@ -114,6 +114,8 @@ def _write_ppo_scalars(writer, model, step):
             writer.add_scalar('train/%s_ppo_vclipfrac' % name, model.ppo_vclip_frac, step)
         if getattr(model, 'ppo_target_kl', None) is not None:       # opt-in KL stop: the optimiser steps the last update applied
             writer.add_scalar('train/%s_ppo_epochs_done' % name, model.ppo_epochs_done, step)
+            if getattr(model, 'ppo_minibatches', 1) > 1:            # opt-in replica minibatches: the same count in steps
+                writer.add_scalar('train/%s_ppo_steps_done' % name, model.ppo_steps_done, step)
 
 
 # ------------------------------------------------------------------ the E = 1 driver behind the reference's Trainer surface
@@ -387,6 +389,8 @@ class BatchedTrainer:
         env.train_mode = True
         model.reset_states()
         model.masked_steps = (0,)             # only the first lock-step of a batch can start an episode (Q4)
+        if hasattr(model, 'mb_env_id_base'):  # opt-in replica minibatches: this rank's replicas draw their keys under their global ids
+            model.mb_env_id_base = int(getattr(env, 'env_id_base', 0))
         model.t = 0
         model.buf_x[0].copy_(env.reset())
 
@@ -515,7 +519,9 @@ class BatchedTrainer:
         with several ranks two, around the eager gradient all-reduce.  Under the opt-in ppo_epochs = K > 1 the one graph goes on
         with {update_ppo_grads(k), update_apply} for k = 2..K in front of the record; with several ranks it is a chain of K + 1
         graphs split at every all-reduce, [grads 1] [apply k | grads k+1] .. [apply K | record | epilogue] (`_upd['chain']` holds
-        the K - 1 in the middle; with K = 1 `_upd` has the keys of before).  Capturing runs no kernel; the host-side state the
+        the K - 1 in the middle; with K = 1 `_upd` has the keys of before).  Under the opt-in ppo_minibatches = M > 1 every epoch
+        k >= 2 is M such steps {update_ppo_grads(k, j), update_apply}: (K - 1) M of them in the one graph, or in the middle of a
+        chain of 2 + (K - 1) M graphs.  Capturing runs no kernel; the host-side state the
         captured Python code touches is put back."""
         m = self.model
         split = m.dist_group is not None
@@ -533,24 +539,25 @@ class BatchedTrainer:
         try:
             torch.cuda.synchronize()
             K = getattr(m, 'ppo_epochs', 1)
+            steps = m.ppo_steps() if K > 1 else []     # (k,) per epoch, or under the opt-in ppo_minibatches (k, j) per group
             g1, g2, chain = self._new_graph(), None, []
             with torch.cuda.graph(g1):
                 m.load_rewards(self.buf_rraw)
                 m.update_grads(self.R_end)
                 if not split:
                     m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
-                    for k in range(2, K + 1):          # opt-in PPO epochs: the same graph goes on with {grads k, apply}
-                        m.update_ppo_grads(k)
+                    for step in steps:                 # opt-in PPO epochs: the same graph goes on with {grads of the step, apply}
+                        m.update_ppo_grads(*step)
                         m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
                     self._record(0.0, lr_dev=self.lr_dev)
                     if inside:
                         self._epilogue()
             if split:
-                for k in range(2, K + 1):              # [apply k-1 | grads k]: one graph between every two all-reduces
+                for step in steps:                     # [apply of the step before | grads of the step]: one graph between every two all-reduces
                     g = self._new_graph()
                     with torch.cuda.graph(g):
                         m.update_apply(0.0, rotate=False, lr_dev=self.lr_dev)
-                        m.update_ppo_grads(k)
+                        m.update_ppo_grads(*step)
                     chain.append(g)
                 g2 = self._new_graph()
                 with torch.cuda.graph(g2):

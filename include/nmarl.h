@@ -1179,6 +1179,36 @@ int nmarl_copy_multi(int32_t n, void* const* dst, const void* const* src, const 
                      void* stream);
 
 /*
+ * Replica minibatches of the opt-in PPO epochs (csrc/minibatch.hip; MODEL_CONFIG ppo_minibatches).
+ *
+ * nmarl_minibatch_perm: a permutation of the E replicas, drawn on the device.  key(e) = word x of
+ * Philox4x32-10(counter = (env_id_base + e, epoch, *count_dev, stream 3), key = seed); rank(e) = the number of e' with
+ * (key(e'), e') < (key(e), e); perm_out[rank(e)] = e.  Two launches (keys into keys_scratch [E], then rank-and-scatter with the keys
+ * staged through LDS), no atomics: equal arguments give equal bits, equal keys fall back to index order.  count_dev is read by the
+ * kernel, so a replayed graph follows it; nmarl_minibatch_count_advance (one thread) adds 1 to it.
+ * NMARL_EINVAL without a launch: E < 1, E > NMARL_MINIBATCH_MAX_E, a null pointer.
+ *
+ * nmarl_minibatch_gather: for each of n (1..NMARL_GATHER_MAX) descriptors, src viewed as [outer, E, inner_bytes] and dst as the
+ * dense [outer, Em, inner_bytes]: dst[o, i] = src[o, idx[i]], idx [Em] int32 on the device.  desc is a HOST array (read at call
+ * time); one kernel launch.  Each descriptor moves 16-byte lanes where inner_bytes and both base addresses are multiples of 16,
+ * 4-byte lanes where they are multiples of 4, bytes otherwise.  An idx entry outside [0, E) leaves its destination rows untouched.
+ * src and dst must not overlap.  NMARL_EINVAL without a launch: n outside 1..NMARL_GATHER_MAX, Em < 1, E < 1, a null pointer,
+ * outer < 1, inner_bytes < 1, Em * inner_bytes beyond 2^31 lanes.
+ */
+#define NMARL_MINIBATCH_MAX_E 65536
+#define NMARL_GATHER_MAX 16
+typedef struct nmarl_gather_desc {
+    const void* src;          /* [outer, E, inner_bytes] */
+    void* dst;                /* [outer, Em, inner_bytes] */
+    int64_t outer;
+    int64_t inner_bytes;
+} nmarl_gather_desc_t;
+int nmarl_minibatch_perm(int32_t E, uint64_t seed, int64_t env_id_base, int32_t epoch, const int32_t* count_dev,
+                         uint32_t* keys_scratch /* [E] */, int32_t* perm_out /* [E] */, void* stream);
+int nmarl_minibatch_count_advance(int32_t* count_dev, void* stream);
+int nmarl_minibatch_gather(int32_t n, const nmarl_gather_desc_t* desc, const int32_t* idx, int32_t Em, int32_t E, void* stream);
+
+/*
  * Training record (csrc/train_record.hip; specification: its header and DESIGN.md 6): behind the optimiser step of an update,
  * one row of 24 floats per agent -- the reference's per-update TensorBoard scalars (agents/policies.py:40-48, 265-273: policy /
  * value / entropy / total loss, lr, gradnorm) and critic diagnostics of the batch (return and advantage moments, mean value,
