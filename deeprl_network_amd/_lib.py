@@ -94,6 +94,11 @@ class NetTopo(C.Structure):
                 ('image', C.c_void_p)]
 
 
+class NetDemand(C.Structure):
+    """nmarl_net_demand_t (include/nmarl.h): the [4][12] activity table of a file-described network."""
+    _fields_ = [('act', (C.c_float * 12) * 4)]
+
+
 # layout of the packed network image (include/nmarl.h NMARL_NET_OFF_*)
 NET_OFF = dict(green=0, src=6144, group=7680, share=8448, fan=11520, dnptr=11648, dnpair=11728, nbr=13264)
 NET_IMAGE_BYTES = 13568
@@ -216,6 +221,8 @@ SIGNATURES = {
     'nmarl_net_reset_obj': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _u64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_net_step': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64,
                        _p, _p],
+    'nmarl_net_step_dem': [C.POINTER(NetParams), C.POINTER(NetTopo), _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _u64, _i64,
+                           _p, _p, C.POINTER(NetDemand)],
     'nmarl_atsc_traffic_begin': [_i64, _i32, _i32, _p, _p, _p, _p, _p],
     'nmarl_atsc_traffic_step': [_i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     'nmarl_atsc_greedy': [_i64, _i32, _i32, _p, _p, _p, _i64, _p, _p],

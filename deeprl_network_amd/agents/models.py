@@ -116,6 +116,12 @@ class IA2C:
         self.distance_mask = np.asarray(distance_mask)
         self.n_agent = len(self.neighbor_mask)
         self.identical_agent = max(self.n_a_ls) == min(self.n_a_ls)          # models.py:89-96
+        # agents with equal action counts and UNEQUAL own observation widths (a network read from a file whose nodes all have,
+        # say, two phases over different numbers of links; the reference's own networks have none): the reference's criterion
+        # would build identical nets of agent 0's width.  They run as the padded heterogeneous network, like Monaco
+        own = n_feat_ls if n_feat_ls is not None else (self.n_s_ls if self.name.startswith('ma2c') else None)
+        if self.identical_agent and own is not None and max(own) != min(own):
+            self.identical_agent = False
         self.n_feat_ls = None
         if not self.identical_agent:
             self.n_feat_ls = self._own_widths(n_feat_ls)

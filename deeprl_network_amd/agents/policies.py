@@ -270,8 +270,9 @@ class BatchedPolicy:
         self.n_feat, self.n_a, self.n_fc, self.n_h = n_feat, n_a, n_fc, n_h
         self.n_own = [int(x) for x in n_feat_ls] if n_feat_ls is not None else [n_feat] * self.N
         self.n_a_ls = [int(x) for x in n_a_ls] if n_a_ls is not None else [n_a] * self.N
-        # the reference's criterion (models.py:89-96): agents are "identical" iff their action counts agree
-        self.hetero = max(self.n_a_ls) != min(self.n_a_ls)
+        # the reference's criterion (models.py:89-96): agents are "identical" iff their action counts agree -- and, here, their own
+        # observation widths too (equal action counts over unequal widths need the padded layouts just the same)
+        self.hetero = max(self.n_a_ls) != min(self.n_a_ls) or max(self.n_own) != min(self.n_own)
         if self.hetero and (max(self.n_own) != n_feat or max(self.n_a_ls) != n_a):
             raise ValueError('heterogeneous agents: n_feat / n_a must be the maxima of n_feat_ls / n_a_ls')
         tab = self.nbr_idx.cpu().numpy()

@@ -18,7 +18,7 @@
 // action/prev N + 20 B + the slab 4*L*(1+m_max)*N (12.3 KB for Monaco, of which 4*sum_i(n_s_i + sum_nbr n_s_j) =
 // 5.0 KB are non-padding).  The intended bound is HBM; today the kernel is instruction-bound.
 //
-// Objectives `wait` / `hybrid` (atsc_env.py:87-96, 383-418; net_step_kernel<REPS, WAIT = true>).  SPECIFICATION -- the grid's
+// Objectives `wait` / `hybrid` (atsc_env.py:87-96, 383-418; net_step_kernel<REPS, WAIT = true, DEM>).  SPECIFICATION -- the grid's
 // step 6 (oracle/grid_ref.py:42-48) carried to links; parity unpinned like the rest of the synthetic dynamics:
 //   one more state array head_wait [E,N,L] f32 holds the seconds the front vehicle of a link has been standing.  With q the
 //   queue at the START of the step and served = D * scale the quantity of oracle/realnet_ref.py step 3,
@@ -62,13 +62,22 @@ __device__ __forceinline__ float activity_b(const int piece) {
     return (piece < 3 || piece > 10) ? 0.0f : (piece == 3 || piece == 10) ? 1.0f : (piece == 4 || piece == 9) ? 2.0f : 4.0f;
 }
 
-template <int REPS, bool WAIT>
+// The demand term as DATA (net_step_kernel<REPS, WAIT, DEM = true>, nmarl_net_step_dem): the per-group activity of a step comes from
+// the [4][12] table of a network description instead of activity_a / activity_b.  The table travels BY VALUE in the kernel arguments
+// (nmarl_net_demand_t, 192 B): the four entries of a step are read straight from the kernarg segment at [g][piece] -- no LDS, no
+// staging pass, no pointer to chase, and the host sees every entry before the launch --; DEM = false carries an empty struct there
+// and compiles to what it was (profiles/r29_net_file.txt).
+struct NoDemand {};
+template <bool DEM> struct DemandArg { typedef NoDemand type; };
+template <> struct DemandArg<true> { typedef nmarl_net_demand_t type; };
+
+template <int REPS, bool WAIT, bool DEM>
 __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
     const nmarl_net_params_t p, const nmarl_net_topo_t tp, const int64_t E, const uint8_t* __restrict__ action,
     float* __restrict__ qs, float* __restrict__ trs, uint8_t* __restrict__ prev, int32_t* __restrict__ ts,
     float* __restrict__ xi, float* __restrict__ obs, float* __restrict__ reward, uint8_t* __restrict__ done,
     float* __restrict__ greward, const int auto_reset, const uint64_t seed, const int64_t env_id_base,
-    int32_t* __restrict__ episode) {
+    int32_t* __restrict__ episode, [[maybe_unused]] const typename DemandArg<DEM>::type dem) {
     __shared__ RepShared sh[REPS];
     // the static network, staged once per block from the host-packed image (nmarl_net_topo_t.image: already in the LDS
     // layout below, so the copy is a fixed number of 16-byte loads all in flight at once; element-wise staging from the
@@ -185,8 +194,20 @@ __global__ __launch_bounds__(32 * REPS) void net_step_kernel(
         [[maybe_unused]] float hw[WAIT ? LMAX : 1];                           // WAIT: the links' standing times (registers, as q / tr)
         // external arrivals of this step per flow group: flow_rate * activity_g(t) / 3600 * DT * xi_g  (x the link's share)
         const int piece = (t * 5) / 300;
-        const float ra = p.flow_rate * activity_a(piece) / 3600.0f * DT, rb = p.flow_rate * activity_b(piece) / 3600.0f * DT;
-        const float xg0 = ra * xi[ec * 4], xg1 = ra * xi[ec * 4 + 1], xg2 = rb * xi[ec * 4 + 2], xg3 = rb * xi[ec * 4 + 3];
+        float xg0, xg1, xg2, xg3;
+        if constexpr (DEM) {                                 // a_g = act[g][piece], 0 behind the last piece; the operand order of the line below
+            const bool on = (unsigned)piece < (unsigned)NMARL_NET_PIECES;
+            const int pc = on ? piece : NMARL_NET_PIECES - 1;
+            const float a0 = on ? dem.act[0][pc] : 0.0f, a1 = on ? dem.act[1][pc] : 0.0f;
+            const float a2 = on ? dem.act[2][pc] : 0.0f, a3 = on ? dem.act[3][pc] : 0.0f;
+            xg0 = p.flow_rate * a0 / 3600.0f * DT * xi[ec * 4];
+            xg1 = p.flow_rate * a1 / 3600.0f * DT * xi[ec * 4 + 1];
+            xg2 = p.flow_rate * a2 / 3600.0f * DT * xi[ec * 4 + 2];
+            xg3 = p.flow_rate * a3 / 3600.0f * DT * xi[ec * 4 + 3];
+        } else {
+            const float ra = p.flow_rate * activity_a(piece) / 3600.0f * DT, rb = p.flow_rate * activity_b(piece) / 3600.0f * DT;
+            xg0 = ra * xi[ec * 4]; xg1 = ra * xi[ec * 4 + 1]; xg2 = rb * xi[ec * 4 + 2]; xg3 = rb * xi[ec * 4 + 3];
+        }
         if (node) {
             float delivered = out;                           // a node feeding nothing discharges out of the network
             const int f0 = t_dnptr[n], f1 = t_dnptr[n + 1];
@@ -375,10 +396,13 @@ inline bool topo_ok(const nmarl_net_topo_t* tp) {
 
 }  // namespace
 
-extern "C" int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* action,
-                              float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
-                              float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
-                              int64_t env_id_base, int32_t* episode, void* stream) {
+namespace {
+
+template <bool DEM>
+int net_step(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* action, float* q, float* transit,
+             uint8_t* prev_action, int32_t* t, float* xi, float* obs, float* reward, uint8_t* done, float* global_reward,
+             int32_t auto_reset, uint64_t seed, int64_t env_id_base, int32_t* episode, void* stream,
+             const typename DemandArg<DEM>::type& dem) {
     if (!objective_ok(p) || !topo_ok(tp) || p->T <= 0 || p->norm_wave <= 0.f || E < 0 ||
         (E > 0 && (!action || !q || !transit || !prev_action || !t || !xi || !obs || !reward || !done || !global_reward)))
         return NMARL_EINVAL;
@@ -386,9 +410,9 @@ extern "C" int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_
     if (E == 0) return NMARL_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // replicas per block: enough blocks to cover the 256 CUs a few times at small E, 8 per block at large E
-#define NMARL_NET_LAUNCH(R, WAIT) hipLaunchKernelGGL((net_step_kernel<R, WAIT>), dim3(net_blocks(E, R)), dim3(32 * R), 0, st, *p, *tp, E, \
+#define NMARL_NET_LAUNCH(R, WAIT) hipLaunchKernelGGL((net_step_kernel<R, WAIT, DEM>), dim3(net_blocks(E, R)), dim3(32 * R), 0, st, *p, *tp, E, \
                                                      action, q, transit, prev_action, t, xi, obs, reward, done, global_reward,      \
-                                                     auto_reset, seed, env_id_base, episode)
+                                                     auto_reset, seed, env_id_base, episode, dem)
     static int reps_env = -1;
     if (reps_env < 0) { const char* ev = getenv("NMARL_NET_REPS"); reps_env = ev ? atoi(ev) : 0; }
     const int reps = reps_env ? reps_env : (E <= 2048 ? 4 : 8);
@@ -399,6 +423,28 @@ extern "C" int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_
     }
 #undef NMARL_NET_LAUNCH
     return nmarl_check_launch();
+}
+
+}  // namespace
+
+extern "C" int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* action,
+                              float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
+                              float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
+                              int64_t env_id_base, int32_t* episode, void* stream) {
+    return net_step<false>(p, tp, E, action, q, transit, prev_action, t, xi, obs, reward, done, global_reward, auto_reset, seed,
+                           env_id_base, episode, stream, NoDemand());
+}
+
+extern "C" int nmarl_net_step_dem(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* action,
+                                  float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
+                                  float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
+                                  int64_t env_id_base, int32_t* episode, void* stream, const nmarl_net_demand_t* dem) {
+    if (!dem) return NMARL_EINVAL;
+    for (int g = 0; g < NMARL_NET_GROUPS; ++g)
+        for (int k = 0; k < NMARL_NET_PIECES; ++k)
+            if (!(dem->act[g][k] >= 0.0f) || !(dem->act[g][k] <= 3.0e38f)) return NMARL_EINVAL;      // negative, NaN or infinite
+    return net_step<true>(p, tp, E, action, q, transit, prev_action, t, xi, obs, reward, done, global_reward, auto_reset, seed,
+                          env_id_base, episode, stream, *dem);
 }
 
 namespace {

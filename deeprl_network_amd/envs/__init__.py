@@ -1,8 +1,10 @@
 """Environment factory (main.py:43-51 of the reference)."""
+from . import net_file
 
 
 def make_batch_env(config, num_envs, device='cuda', seed=None, env_id_base=0):
     """ENV_CONFIG section -> batched device-resident environment."""
+    net_file.check_scenario(config)
     scenario = config.get('scenario')
     if scenario.startswith('atsc') or scenario == 'large_grid':          # (config_greedy.ini names the scenario `large_grid`)
         if scenario.endswith('large_grid'):
@@ -16,6 +18,7 @@ def make_batch_env(config, num_envs, device='cuda', seed=None, env_id_base=0):
 
 def init_env(config, port=0, device='cuda'):
     """Single-replica env with the reference duck-type (main.py:43-51)."""
+    net_file.check_scenario(config)
     scenario = config.get('scenario')
     if scenario.startswith('atsc') or scenario == 'large_grid':
         if scenario.endswith('large_grid'):

@@ -88,7 +88,7 @@ def net_pressure_table(topo):
     src[i, k] = j in the order of `dn_pair`; every link of such a node carries the one term (that group, 1.0).  A node that feeds
     nothing has no terms."""
     from .real_net_env import net_greedy_table
-    n_a, mask = net_greedy_table(topo.node_names)
+    n_a, mask = net_greedy_table(topo.node_names, topo.phases)
     h = topo.host
     groups, terms = [], {}
     for j in range(topo.N):

@@ -10,6 +10,9 @@ array, head_wait: csrc/realnet.hip header), the flow_rate demand schedule (real_
 `greedy` agent (real_net_env.py:112-145) -- and replaces the microsimulation by the store-and-forward link-graph model specified in oracle/realnet_ref.py, stepped
 by csrc/realnet.hip for E lock-stepped replicas.  Observations come out already padded to the widest node and
 gathered over the listed neighbours: the input layout of the heterogeneous (identical=False) nets.
+
+The network is a description (envs/net_file.py): the built-in Monaco one made from NODE_DEFS / PHASE_SETS below, or the file that
+ENV_CONFIG `net_file` names (2..32 nodes), which also carries the demand's activity table (nmarl_net_step_dem).
 """
 import ctypes
 
@@ -18,7 +21,8 @@ import torch
 
 from .. import _lib
 from .atsc import N_GROUP, OBJECTIVES, RULE_AGENTS, AtscBatchEnv, AtscEnv, RuleController, atsc_params_from_config  # noqa: F401
-from .traffic_record import net_demand, net_mult
+from . import net_file
+from .traffic_record import net_mult
 
 # (node, phase-set key, listed neighbours): real_net_env.py:21-49
 NODE_DEFS = (
@@ -67,17 +71,37 @@ PHASE_SETS = {
 }
 
 
+def builtin_description():
+    """The built-in Monaco network (NODE_DEFS / PHASE_SETS, links by the rule, Monaco's activity) as a checked description."""
+    return net_file.parse({'nodes': {name: {'phases': list(PHASE_SETS[key]), 'neighbors': list(nbrs)} for name, key, nbrs in NODE_DEFS}})
+
+
+def _phases_of(node_names, phases):
+    """Per node of `node_names` its phase strings: `phases` (a topology's, in that order), or -- None -- the built-in network's by
+    name; a name the built-in network does not have is refused (a file-described network hands over its own phases)."""
+    if phases is not None:
+        if len(phases) != len(node_names):
+            raise ValueError('phases: one entry per node (%d nodes, %d entries)' % (len(node_names), len(phases)))
+        return [tuple(p) for p in phases]
+    key = {name: k for name, k, _ in NODE_DEFS}
+    unknown = [name for name in node_names if name not in key]
+    if unknown:
+        raise ValueError('node %r is not a node of the built-in network: pass the phases of the network (NetTopology.phases)' % unknown[0])
+    return [PHASE_SETS[key[name]] for name in node_names]
+
+
 class RealNetController(RuleController):
     """The reference's rule-based `greedy` agent (real_net_env.py:112-145): per node the phase whose green links hold the most
     vehicles.  A link counts for a phase where its signal is the capital 'G' (the reference tests `signal == 'G'`: a permitted
     'g' does not count); the reference adds every incoming lane once per phase, and in the synthetic network every link is its
-    own lane, so nothing is de-duplicated.  `ob` is the node's own wave vector, one entry per link.  Same `forward(obs) ->
-    actions` duck-type as LargeGridController."""
+    own lane, so nothing is de-duplicated.  `ob` is the node's own wave vector, one entry per link.  `phases`: the nodes' phase
+    strings in the order of `node_names` (NetTopology.phases); None = the built-in network's.  Same `forward(obs) -> actions`
+    duck-type as LargeGridController."""
     name = 'greedy'
 
-    def __init__(self, node_names):
+    def __init__(self, node_names, phases=None):
         self.node_names = list(node_names)
-        self._phases = {name: PHASE_SETS[key] for name, key, _ in NODE_DEFS}
+        self._phases = dict(zip(self.node_names, _phases_of(self.node_names, phases)))
 
     def greedy(self, ob, node_name):
         flows = [sum(ob[k] for k, signal in enumerate(phase) if signal == 'G') for phase in self._phases[node_name]]
@@ -87,16 +111,14 @@ class RealNetController(RuleController):
         return [self.greedy(ob, node_name) for ob, node_name in zip(obs, self.node_names)]
 
 
-def net_greedy_table(node_names):
+def net_greedy_table(node_names, phases=None):
     """(n_a [N] i32, mask [N,8] u32) of nmarl_atsc_greedy for the network's nodes in the given order: bit k of mask[i][a] is set
-    where link k of node i shows the capital 'G' in phase a -- the links RealNetController.greedy adds."""
-    key = {name: k for name, k, _ in NODE_DEFS}
+    where link k of node i shows the capital 'G' in phase a -- the links RealNetController.greedy adds.  `phases` as there."""
     n_a = np.zeros(len(node_names), dtype=np.int32)
     mask = np.zeros((len(node_names), 8), dtype=np.uint32)
-    for i, name in enumerate(node_names):
-        phases = PHASE_SETS[key[name]]
-        n_a[i] = len(phases)
-        for a, phase in enumerate(phases):
+    for i, node_phases in enumerate(_phases_of(node_names, phases)):
+        n_a[i] = len(node_phases)
+        for a, phase in enumerate(node_phases):
             mask[i, a] = sum(1 << k for k, signal in enumerate(phase) if signal == 'G')
     return n_a, mask
 
@@ -104,16 +126,18 @@ def net_greedy_table(node_names):
 class NetTopology:
     """Static arrays of the network (host NumPy + device copies + the nmarl_net_topo_t handed to the kernels)."""
 
-    def __init__(self, device):
-        defs = {name: (key, nbrs) for name, key, nbrs in NODE_DEFS}
-        self.node_names = sorted(defs)                                   # real_net_env.py:189
+    def __init__(self, device, desc=None):
+        """desc: a net_file.NetDescription (a parsed `net_file`); None = the built-in Monaco network."""
+        self.builtin = desc is None
+        desc = self.desc = builtin_description() if desc is None else desc
+        self.node_names = list(desc.names)                               # sorted: real_net_env.py:189
         N = self.N = len(self.node_names)
-        pos = {name: i for i, name in enumerate(self.node_names)}
-        self.phases = [PHASE_SETS[defs[name][0]] for name in self.node_names]
+        self.phases = [tuple(p) for p in desc.phases]
+        self.activity = np.array(desc.activity, dtype=np.float64)        # [4,12]: x flow_rate = veh/h of a flow group in a piece
         self.n_a_ls = [len(p) for p in self.phases]
         self.n_s_ls = [len(p[0]) for p in self.phases]                   # one `wave` entry per signal link
         self.A, self.L = max(self.n_a_ls), max(self.n_s_ls)
-        listed = [[pos[m] for m in defs[name][1]] for name in self.node_names]
+        listed = [list(js) for js in desc.listed]
         self.neighbor_mask = np.zeros((N, N), dtype=int)                 # real_net_env.py:175-181 (directed)
         for i, js in enumerate(listed):
             self.neighbor_mask[i, js] = 1
@@ -137,20 +161,14 @@ class NetTopology:
         for i, p in enumerate(self.phases):
             for a, s in enumerate(p):
                 green[i, a, :len(s)] = [code[ch] for ch in s]
-        src = -np.ones((N, self.L), dtype=np.int32)
+        src = -np.ones((N, self.L), dtype=np.int32)                      # the description's feeders and flow groups (net_file.parse:
+        group = -np.ones((N, self.L), dtype=np.int32)                    # the file's `links`, or the rule of oracle/realnet_ref.py)
         for i in range(N):
-            m = len(self.nbrs[i])
-            for k in range(self.n_s_ls[i]):
-                if k % (m + 1) < m:
-                    src[i, k] = self.nbrs[i][k % (m + 1)]
+            src[i, :self.n_s_ls[i]] = desc.feeder[i]
+            group[i, :self.n_s_ls[i]] = desc.group[i]
         fan = np.array([(src == j).sum() for j in range(N)], dtype=np.int32)
-        group = -np.ones((N, self.L), dtype=np.int32)
-        for i in range(N):
-            for k in range(self.n_s_ls[i]):
-                if src[i, k] < 0:
-                    group[i, k] = (i + k) % N_GROUP
-        n_ext = np.array([(group == g).sum() for g in range(N_GROUP)])
-        ext_share = np.where(group >= 0, 1.0 / n_ext[np.maximum(group, 0)], 0.0).astype(np.float32)
+        n_ext = np.array([(group == g).sum() for g in range(N_GROUP)])   # a group without an entry has no share: nothing is divided by 0
+        ext_share = np.where(group >= 0, 1.0 / np.maximum(n_ext, 1)[np.maximum(group, 0)], 0.0).astype(np.float32)
         dn_ptr, dn_pair = [0], []
         for j in range(N):
             for i in range(N):
@@ -202,6 +220,20 @@ class NetTopology:
         t = self.c = _lib.NetTopo()
         t.N, t.L, t.A, t.m_max = N, self.L, self.A, self.m_max
         t.n_s, t.image = self.dev['n_s'].data_ptr(), self.dev['image'].data_ptr()
+        # a file-described network hands its activity table to the step kernel (nmarl_net_step_dem); the built-in one keeps the
+        # kernel's own arithmetic (nmarl_net_step)
+        self.dem = None if self.builtin else _lib.NetDemand()
+        if self.dem is not None:
+            for g in range(N_GROUP):
+                for piece in range(net_file.N_PIECE):
+                    self.dem.act[g][piece] = self.activity[g, piece]
+
+
+def net_topology_from_config(config, device):
+    """ENV_CONFIG section -> NetTopology: the network of the file `net_file` names (an absolute path, or one relative to the working
+    directory: `net_file.read_ini` has resolved the ini's own against the ini's directory), or the built-in one."""
+    path = config.get('net_file', fallback=None)
+    return NetTopology(device, net_file.load(path) if path else None)
 
 
 def net_params_from_config(config):
@@ -214,7 +246,7 @@ def net_params_from_config(config):
 class RealNetBatchEnv(AtscBatchEnv):
     def _scenario(self, config):
         self.params = net_params_from_config(config)
-        tp = self.topo = NetTopology(self.device)
+        tp = self.topo = net_topology_from_config(config, self.device)
         self.n_agent, self.n_a, self.n_a_ls = tp.N, tp.A, list(tp.n_a_ls)
         self.n_feat, self.n_feat_ls = tp.L, list(tp.n_s_ls)               # own observation widths (heterogeneous)
         self.neighbor_mask, self.distance_mask = tp.neighbor_mask, tp.distance_mask
@@ -226,12 +258,12 @@ class RealNetBatchEnv(AtscBatchEnv):
 
     def traffic_model(self):
         """(mult [N,L] i32, demand [4,12] f64) of the traffic record (envs/traffic_record.py)."""
-        return net_mult(self.topo.n_s_ls, self.topo.L), net_demand(float(self.params.flow_rate))
+        return net_mult(self.topo.n_s_ls, self.topo.L), float(self.params.flow_rate) * self.topo.activity
 
     def greedy_rule(self):
         """(host controller, own observation width, n_a, mask) of the batched greedy agent (envs/greedy.py)."""
-        names = self.topo.node_names
-        return (RealNetController(names), int(self.topo.L)) + net_greedy_table(names)
+        names, phases = self.topo.node_names, self.topo.phases
+        return (RealNetController(names, phases), int(self.topo.L)) + net_greedy_table(names, phases)
 
     def pressure_table(self):
         from .maxpressure import net_pressure_table
@@ -245,7 +277,11 @@ class RealNetBatchEnv(AtscBatchEnv):
             _lib.check(_lib.lib.nmarl_net_reset_obj(ctypes.byref(params), topo, *args), 'nmarl_net_reset_obj')
 
     def _step_call(self, args):
-        _lib.check(_lib.lib.nmarl_net_step(ctypes.byref(self.params), ctypes.byref(self.topo.c), *args), 'nmarl_net_step')
+        p, topo = ctypes.byref(self.params), ctypes.byref(self.topo.c)
+        if self.topo.dem is None:
+            _lib.check(_lib.lib.nmarl_net_step(p, topo, *args), 'nmarl_net_step')
+        else:                                                            # the same step with the demand's activity table as data
+            _lib.check(_lib.lib.nmarl_net_step_dem(p, topo, *args, ctypes.byref(self.topo.dem)), 'nmarl_net_step_dem')
 
 
 class RealNetEnv(AtscEnv):

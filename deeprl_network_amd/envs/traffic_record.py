@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib
 from .atsc import described
+from .net_file import MONACO_ACTIVITY
 
 TRAFFIC_COLUMNS = ('number_total_car', 'number_departed_car', 'number_arrived_car', 'avg_wait_sec', 'avg_speed_mps', 'std_queue',
                    'avg_queue', 'time_sec')                       # the 8 floats of a row, in the kernel's order
@@ -24,7 +25,6 @@ DT, WAIT_EPS = 5.0, 1e-3
 GRID_MULT = (3, 2, 1, 3, 2, 1)                                    # signal links per lane (oracle/grid_ref.py LINK_LANE)
 _GRID_RATIOS1 = (0.4, 0.7, 0.9, 1.0, 0.75, 0.5, 0.25)             # large_grid_data/build_file.py:298
 _GRID_RATIOS2 = (0.3, 0.8, 0.9, 1.0, 0.8, 0.6, 0.2)               # large_grid_data/build_file.py:299
-_NET_ACTIVITY = ((1, 2, 4, 4, 4, 4, 2, 1, 0, 0, 0, 0),) * 2 + ((0, 0, 0, 1, 2, 4, 4, 4, 4, 2, 1, 0),) * 2    # real_net_data/build_file.py:70-72
 
 
 def grid_mult(n_node=25):
@@ -53,7 +53,7 @@ def grid_demand(peak1, peak2, n_entry=(3, 3, 3, 3)):
 
 def net_demand(flow_rate):
     """[4,12] f64 veh/h: flow_rate x the number of active flows of the group (real_net_data/build_file.py:70-96)."""
-    return float(flow_rate) * np.array(_NET_ACTIVITY, dtype=np.float64)
+    return float(flow_rate) * np.array(MONACO_ACTIVITY, dtype=np.float64)
 
 
 class TrafficRecorder:

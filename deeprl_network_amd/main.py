@@ -1,6 +1,5 @@
 """train / evaluate drivers -- the reference's main.py (21-163) on the MI355X path."""
 import argparse
-import configparser
 import logging
 import os
 
@@ -8,7 +7,7 @@ import numpy as np
 import torch
 
 from .agents.models import IA2C, IA2C_CU, IA2C_FP, MA2C_DIAL, MA2C_IC3, MA2C_NC
-from .envs import init_env, make_batch_env
+from .envs import init_env, make_batch_env, net_file
 from .envs.atsc import RULE_AGENTS
 from .envs.greedy import GreedyBatchController
 from .envs.maxpressure import MaxPressureBatchController
@@ -127,11 +126,13 @@ def train(args):
     world, rank, local, group = _dist()
     dirs = init_dir(args.base_dir)
     init_log(dirs['log'], rank)
-    config = configparser.ConfigParser()
-    config.read(args.config_dir)
+    config = net_file.read_ini(args.config_dir)           # (an ENV_CONFIG net_file resolves against the ini's directory)
     if rank == 0:
         copy_file(args.config_dir, dirs['data'])
-    apply_overrides(config, args, os.path.join(dirs['data'], os.path.basename(args.config_dir)) if rank == 0 else None)
+    run_ini = os.path.join(dirs['data'], os.path.basename(args.config_dir))
+    apply_overrides(config, args, run_ini if rank == 0 else None)
+    if rank == 0:                                         # the network's file travels with the run: `evaluate` needs nothing else
+        net_file.copy_into_run(config, dirs['data'], run_ini)
     env_cfg = config['ENV_CONFIG']
     if env_cfg.get('agent') in RULE_AGENTS:
         # the rule-based ATSC baselines have nothing to train (no add_transition / backward / save): say so instead of dying on an
@@ -177,9 +178,7 @@ def _open_run(run_dir):
     ini = find_file(os.path.join(run_dir, 'data') + '/')
     if not ini:
         return None
-    cfg = configparser.ConfigParser()
-    cfg.read(ini)
-    return cfg
+    return net_file.read_ini(ini)
 
 
 def model_config(cfg):

@@ -288,6 +288,22 @@ int nmarl_net_step(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int6
                    float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
                    float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
                    int64_t env_id_base, int32_t* episode, void* stream);
+/* The demand of a network read from a file (ENV_CONFIG net_file): act[g][piece] is the factor of flow_rate that
+ * flow group g carries in the 300-s piece `piece` (Monaco: the number of active flows, real_net_data/build_file.py:70-72). */
+#define NMARL_NET_GROUPS 4
+#define NMARL_NET_PIECES 12
+typedef struct nmarl_net_demand {
+    float act[NMARL_NET_GROUPS][NMARL_NET_PIECES];
+} nmarl_net_demand_t;
+/* nmarl_net_step with the demand term as data: its arguments, then the table (host memory, handed to the kernel by value).
+ * In a step at time t (control steps), piece = (5 t) / 300 and a_g = piece < 12 ? dem->act[g][piece] : 0; an external link of
+ * group g receives  flow_rate * a_g / 3600 * 5 * xi_g * share  vehicles, in this operand order -- with Monaco's table the bits
+ * of nmarl_net_step.  Everything else (replicas per block by E and NMARL_NET_REPS, the objective's forms, every other check)
+ * is nmarl_net_step's.  NMARL_EINVAL for a NULL dem and for an entry that is negative or not finite. */
+int nmarl_net_step_dem(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* action,
+                       float* q, float* transit, uint8_t* prev_action, int32_t* t, float* xi, float* obs,
+                       float* reward, uint8_t* done, float* global_reward, int32_t auto_reset, uint64_t seed,
+                       int64_t env_id_base, int32_t* episode, void* stream, const nmarl_net_demand_t* dem);
 /* nmarl_net_reset for an env with an objective: the same reset, which also clears p->head_wait of the reset replicas when
  * p->objective != 0 (then p->head_wait must not be NULL; objective outside 0..2 is NMARL_EINVAL). */
 int nmarl_net_reset_obj(const nmarl_net_params_t* p, const nmarl_net_topo_t* tp, int64_t E, const uint8_t* mask, const float* u0,
